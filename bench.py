@@ -15,6 +15,34 @@ Weak scaling: each GPU processes its own minibatch of --batch rows per step;
 the keys are sharded over all GPUs (ps-lite server group -> xGMI all-to-all).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model difacto|linear]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+every figure of that line is read from the timed steps themselves (counters
+the step keeps anyway), none takes a run of its own. ``--full`` is where
+measurements beyond the headline belong (further configurations, baselines,
+comparisons); today there are none, so it runs the same steps.
+
+``--dump-outputs DIR`` writes, after the timed steps and the result line,
+float32 / float64 ``DIR/<name>.npy`` files (``<name>_rank<r>`` with more than
+one rank; 48 MB at most over all ranks) by which two builds run with the same
+arguments can be compared file by file. The data is seeded and the step is
+the one the run times, whatever ``WH_DETERMINISTIC`` says (the result line
+reports it as ``"deterministic"``). The default step sums hot keys' gradients
+with float atomics, and over a run's training steps (1000 to the warm state,
+the warm-up, the timed ones) those rounding differences grow -- FTRL's L1
+threshold switches weights, and with them embedding rows, on and off -- until
+two runs of one build differ by 1.6e-3 at the median of the predictions and
+0.45 at most. Such values say nothing about a build, so the files hold
+
+* from the timed steps, what stays exact: for a fixed sample of the last
+  timed minibatch's keys, whether the table holds them and their feature
+  counts (``timed_found``, ``timed_cnt``);
+* from a probe, the same step run PROBE_STEPS times from an empty model on
+  seeded minibatches of the same shape, where only the rounding itself
+  differs between runs: its progress vector, the model entries (w, z, sq,
+  cnt, V rows) of a sample of its last minibatch's keys, and its predictions
+  for that minibatch (``probe_*``).
 
 ``--gpus N`` with N > 1 and no launcher around it starts the N ranks itself
 (``torch.distributed.run`` on 127.0.0.1, one process per GPU, the launch the
@@ -57,6 +85,76 @@ def build(args, comm, device):
     return LinearLearner(conf, comm, device, cap=args.cap, seed=1)
 
 
+DUMP_BYTES = 48 << 20  # all files of all ranks together (the limit is 64 MB)
+PROBE_STEPS = 4
+
+
+def dump_rows(dim, nranks):
+    """Keys sampled per rank: each costs 2 (timed) + 5 + dim (probe) floats,
+    and the predictions are cut to 4 floats per sampled key."""
+    return max(1, min(1 << 16, DUMP_BYTES // 4 // max(nranks, 1) // (11 + dim)))
+
+
+def model_sample(store, keys, rows):
+    """The model entries of a fixed sample of `keys`: their sorted unique
+    values, every k-th of them (k fixed by their number) so that at most
+    `rows` remain, looked up by key -- the table slot of a key depends on the
+    insertion order, its entry does not. float32: found [n] (1 where this
+    shard holds the key), cnt w z sq [n], V [n, dim] (zeros where no row)."""
+    dim = int(getattr(store, "dim", 0) or 0)
+    uniq = torch.unique(keys)
+    if uniq.numel() > rows:
+        uniq = uniq[::(uniq.numel() + rows - 1) // rows].contiguous()
+    slots = store.find(uniq, False).long()
+    found = slots >= 0
+    at = slots.clamp_min(0)
+    out = {"found": found.float()}
+    for name in ("cnt", "w", "z", "sq"):
+        t = getattr(store, name)
+        t = t[at.to(t.device)].float()
+        out[name] = torch.where(found.to(t.device), t, torch.zeros_like(t))
+    if dim > 0 and store.V.numel():
+        vrow = store.vrow[at.to(store.vrow.device)].long()
+        has = (found.to(vrow.device) & (vrow >= 0)).to(store.V.device)
+        V = store.V[vrow.clamp_min(0).to(store.V.device)][:, :dim].float()
+        out["V"] = torch.where(has.unsqueeze(1), V, torch.zeros_like(V))
+    return out
+
+
+def dump_outputs(path, comm, timed, last, probe, probe_last):
+    """--dump-outputs: DIR/<name>.npy (<name>_rank<r> with more than one rank).
+
+    From the timed learner, for a sample of the last timed minibatch's keys
+    (model_sample): timed_found, timed_cnt -- the entries of the table that
+    are whole numbers and so repeat from run to run.
+    From the probe learner (PROBE_STEPS steps of the same default step from an
+    empty model), for a sample of its last minibatch's keys: probe_found,
+    probe_cnt, probe_w, probe_z, probe_sq, probe_V; probe_progress (float64,
+    take_progress); probe_pred, its predictions for that minibatch."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = "_rank%d" % comm.rank if comm.size > 1 else ""
+
+    def save(name, t, dtype=torch.float32):
+        np.save(os.path.join(path, name + tag + ".npy"),
+                t.detach().to("cpu", dtype).contiguous().numpy())
+
+    rows = dump_rows(int(getattr(timed.store, "dim", 0) or 0), comm.size)
+    s = model_sample(timed.store, last[0], rows)
+    save("timed_found", s["found"])
+    save("timed_cnt", s["cnt"])
+    keys, label, offset = probe_last
+    save("probe_progress", torch.tensor(probe.take_progress(), dtype=torch.float64),
+         torch.float64)
+    for name, t in model_sample(probe.store, keys, rows).items():
+        save("probe_" + name, t)
+    py = probe.process(keys, offset, None, label, 2, 0)  # (a collective with > 1 rank)
+    if py is not None:
+        py = py.reshape(-1)
+        save("probe_pred", py[::(py.numel() + 4 * rows - 1) // (4 * rows)]
+             if py.numel() > 4 * rows else py)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -90,6 +188,14 @@ def main():
                          "the multi-shard step is pipelined one minibatch deep")
     ap.add_argument("--host-profile", default=None,
                     help="write a cProfile of the timed steps' host (Python) side to PATH.<rank>")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write float32 / float64 DIR/<name>.npy files "
+                         "for comparing two builds: the exact table entries of a sample of the "
+                         "last timed minibatch's keys, and progress, model sample and "
+                         "predictions of a few more steps of the same step from an empty model")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that go beyond the headline figure "
+                         "(none today: every reported figure comes from the timed steps)")
     ap.add_argument("--launch-timeout", type=int, default=540,
                     help="self-launched multi-rank runs are killed after this many seconds "
                          "(below the driver's 600 s bench limit, so a stuck run still ends "
@@ -162,13 +268,13 @@ def main():
         out[1].record_stream(main)  # the label (keys / offsets: recorded by the learner)
         return out, evs.record(gen)
 
-    def run(first, n):
+    def run(first, n, lr=learner):
         nxt, ev = batch(first), None
         for s in range(first, first + n):
             keys, label, offset = nxt
             nxt, ev = batch_async(s + 1) if s + 1 < first + n else (None, None)
-            learner.process(keys, offset, None, label, 0, 0,
-                            next_batch=(nxt[0], nxt[2], None, ev) if nxt is not None else None)
+            lr.process(keys, offset, None, label, 0, 0,
+                       next_batch=(nxt[0], nxt[2], None, ev) if nxt is not None else None)
 
     def sync():
         if device.type == "cuda":
@@ -224,7 +330,7 @@ def main():
     sizes = getattr(learner, "last_sizes", None)
     if sizes is not None:  # last minibatch: unique keys and embedding rows per GPU
         sizes = [int(sizes[0]), int(sizes[1].reshape(-1)[0].item()) if torch.is_tensor(sizes[1]) else int(sizes[1])]
-    ex = args.batch * args.steps * n
+    ex =args.batch * args.steps * n
     value = ex / dt
     if args.model == "difacto":
         metric = "examples/sec, DiFacto FM on Criteo-1TB-shaped sparse at 1/2/4/8 MI355X"
@@ -253,6 +359,7 @@ def main():
             "uniq_keys_per_gpu_step": sizes[0] if sizes else None,
             "emb_rows_per_gpu_step": sizes[1] if sizes else None,
             "prewarm_steps": args.prewarm,
+            "deterministic": os.environ.get("WH_DETERMINISTIC") == "1",
             "table_keys_per_gpu": guard.keys, "table_load": guard.keys / learner.store.cap,
             "table_grows": guard.grows, "vslab_rows_per_gpu": guard.vused,
             "dropped_keys": 0, "max_concurrency": args.max_concurrency,
@@ -268,6 +375,20 @@ def main():
             "watchdog_deadline_s": nat.watchdog_deadline if nat else None,
             "localize_retries": (_native.hip().loc_retries() if device.type == "cuda" else 0),
         }), flush=True)
+    if args.dump_outputs:
+        # Only here, after every reported figure is read (take_progress, the
+        # guard, the localize retry count): the probe's steps and the
+        # prediction pass go through the counters those figures come from.
+        # Every rank runs them (they are collectives with more than one rank).
+        last = batch(args.warmup + max(args.steps, 1) - 1)  # (again: the generator is seeded)
+        pargs = argparse.Namespace(**vars(args))
+        pargs.cap, pargs.vcap = min(args.cap, 1 << 23), min(args.vcap, 1 << 21)
+        probe = build(pargs, comm, device)
+        seed = 9000000 + comm.rank
+        run(0, PROBE_STEPS, probe)
+        probe.flush()
+        dump_outputs(args.dump_outputs, comm, learner, last, probe, batch(PROBE_STEPS - 1))
+        sync()
     comm.finalize()
     return 0
 

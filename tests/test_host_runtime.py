@@ -13,7 +13,6 @@ from wormhole_amd import _native, config
 from wormhole_amd.config.schema import DifactoConfig, LinearConfig
 from wormhole_amd.ops import ref
 
-REF = "/root/reference/learn"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DATA = os.path.join(ROOT, "learn", "data")
 
