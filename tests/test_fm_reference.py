@@ -1,0 +1,176 @@
+"""CPU tests of tests/_fm_cases.py, the float64 references and error bounds
+that test_fm_kernels_gpu.py holds the HIP kernels to.
+
+The project's fp32 reference (ops/ref.py) must lie inside ONE bound of the
+float64 reference on the deep batch (the GPU tests allow two), the batch must
+have the structure the GPU tests rely on, and the check must reject the
+perturbations a kernel bug would cause: a dropped 65th term of a long row,
+a row computed with the previous row's headers, a key whose x*x*p*V term is
+skipped.
+"""
+import pytest
+import torch
+
+import _fm_cases as fc
+from wormhole_amd.ops import ref
+
+
+@pytest.fixture(scope="module")
+def deep():
+    """The deep valued batch, localized by the reference."""
+    b = fc.deep_batch(True)
+    loc = ref.localize(b.keys, b.off, b.val, 1)
+    return b, loc
+
+
+def _fp32_and_ref64(b, loc, vstride):
+    uniq, ucnt, oc, lid, csc_off, csc_row, csc_val = loc
+    hdr, vc = fc.make_model(b, uniq, vstride, 5)
+    met = torch.zeros(5, dtype=torch.float64)
+    py, dual, xv = ref.fm_forward(b.off, lid, b.val, hdr, vc, vstride, b.label, 2, met)
+    fr = fc.fm_forward_ref64(b.off, lid, b.val, hdr, vc, vstride)
+    gw, gvc = ref.fm_backward(csc_off, csc_row, csc_val, dual, xv, hdr, vc, vstride)
+    br = fc.fm_backward_ref64(csc_off, csc_row, csc_val, dual, xv, hdr, vc, vstride)
+    return hdr, vc, (py, dual, xv, met), fr, (gw, gvc), br
+
+
+def test_localize_check_accepts_reference(deep):
+    b, loc = deep
+    fc.check_localize(b, loc)
+    bad = list(loc)
+    bad[5] = loc[5].clone()
+    p = int(loc[4][fc.local_id(loc[0], b.hot_a)])  # first occurrence of hot A
+    bad[5][p] = 0 if int(bad[5][p]) != 0 else 1  # one occurrence moved to an empty row
+    with pytest.raises(AssertionError):
+        fc.check_localize(b, bad)
+
+
+@pytest.mark.parametrize("vstride", [4, 16, 64])
+def test_fp32_reference_inside_one_bound(deep, vstride):
+    b, loc = deep
+    hdr, vc, (py, dual, xv, met), fr, (gw, gvc), br = _fp32_and_ref64(b, loc, vstride)
+    m = fc.check_structure(b, loc[0], loc[4], hdr, deep=True)
+    assert m >= 5 * 8192 and vc.shape[0] == m + 7
+    n = b.nrows
+    live = fc.live_rows(hdr)
+    r = {"py": fc.assert_within("ref32 py", py, fr.py, fr.bound_py, 1.0),
+         "xv": fc.assert_within("ref32 xv", xv.reshape(n, vstride), fr.xv, fr.bound_xv, 1.0),
+         "gw": fc.assert_within("ref32 gw", gw, br.gw, br.bound_gw, 1.0),
+         "gV": fc.assert_within("ref32 gV", gvc[live], br.gvc[live], br.bound_gvc[live], 1.0)}
+    print("vstride %d: |err|/bound of the fp32 reference: %s" % (vstride, r))
+    # empty rows and the row without any embedded id have bound 0 (-> exact)
+    assert float(fr.bound_py[b.lens == 0].abs().max()) == 0
+    assert float(fr.bound_xv[b.scalar_row].abs().max()) == 0 and float(fr.bound_py[b.scalar_row]) > 0
+    assert float(fr.bound_xv[:, vstride - 1].abs().max()) == 0  # the padding column
+    assert float(fr.bound_xv[b.embed_row, :vstride - 1].min()) > 0
+    # the whole forward check (loss, dual, metrics of 5 slots) accepts it too
+    fc.check_forward("ref32 ", fr, b.label, 2, py, dual, xv, met, vstride)
+    fc.check_backward("ref32 ", br, hdr, gw, gvc, vstride)
+
+
+def test_check_rejects_kernel_like_errors(deep):
+    b, loc = deep
+    vs = 16
+    uniq, ucnt, oc, lid, csc_off, csc_row, csc_val = loc
+    hdr, vc, (py, dual, xv, met), fr, (gw, gvc), br = _fp32_and_ref64(b, loc, vs)
+    xv = xv.reshape(b.nrows, vs)
+    w = hdr[:, 0]
+    vid = ref.hdr_vidx(hdr).long()
+
+    def row_forward(r, lids):
+        """fp32 forward of row r with the headers of `lids` (one per non-zero,
+        -1: none) in place of its own."""
+        j0, j1 = int(b.off[r]), int(b.off[r + 1])
+        x = b.val[j0:j1]
+        ok = lids >= 0
+        l = lids.clamp(min=0)
+        wl = torch.where(ok, w[l], torch.zeros(()))
+        v = torch.where(ok, vid[l], torch.full((), -1))
+        V = torch.where((v >= 0)[:, None], vc[v.clamp(min=0)], torch.zeros(()))
+        s = (x[:, None] * V).sum(0)
+        q = ((x * x)[:, None] * V * V).sum(0)
+        return (x * wl).sum() + 0.5 * (s * s - q).sum(), s
+
+    # sanity: the row's own headers reproduce the reference and pass
+    r = b.embed_row
+    own = lid[int(b.off[r]):int(b.off[r + 1])].long()
+    p_ok, s_ok = row_forward(r, own)
+    fc.assert_within("row py", p_ok.reshape(1), fr.py[r:r + 1], fr.bound_py[r:r + 1])
+    fc.assert_within("row xv", s_ok, fr.xv[r], fr.bound_xv[r])
+
+    # 1. the 65th term of a long row dropped (first id of the second pass)
+    drop = own.clone()
+    drop[64] = -1
+    p_bad, s_bad = row_forward(r, drop)
+    bad_py, bad_xv = py.clone(), xv.clone()
+    bad_py[r], bad_xv[r] = p_bad, s_bad
+    with pytest.raises(AssertionError):
+        fc.assert_within("dropped term py", bad_py, fr.py, fr.bound_py)
+    with pytest.raises(AssertionError):
+        fc.assert_within("dropped term xv", bad_xv, fr.xv, fr.bound_xv)
+
+    # 2. one row computed with the previous row's headers (a missed rotation)
+    cand = ((b.lens[1:] >= 3) & (b.lens[1:] <= 7) & (b.lens[:-1] >= 1)).nonzero().reshape(-1) + 1
+    r = int(cand[len(cand) // 2])
+    n = int(b.lens[r])
+    prev = lid[int(b.off[r - 1]):int(b.off[r])].long()
+    stale = torch.full((n,), -1, dtype=torch.int64)
+    stale[:min(n, prev.numel())] = prev[:n]
+    p_bad, s_bad = row_forward(r, stale)
+    bad_py, bad_xv = py.clone(), xv.clone()
+    bad_py[r], bad_xv[r] = p_bad, s_bad
+    with pytest.raises(AssertionError):
+        fc.assert_within("stale header py", bad_py, fr.py, fr.bound_py)
+    with pytest.raises(AssertionError, match="k_fm_fwd py: largest"):
+        fc.check_forward("stale header ", fr, b.label, 2, bad_py, dual, xv, met, vs)
+    bad_gw = gw.clone()
+    bad_gw[fc.local_id(uniq, b.hot_b)] *= 1.01  # a chunk of 64 lost of the scalar hot key
+    with pytest.raises(AssertionError, match="k_bwd_scalar gw: largest .* occurrences"):
+        fc.check_backward("lost chunk ", br, hdr, bad_gw, gvc, vs)
+
+    # 3. x*x*p*V skipped for one key (a cold key: one occurrence)
+    cnt = csc_off[1:] - csc_off[:-1]
+    k = int(((cnt == 1) & (vid >= 0)).nonzero()[0])
+    bad_gvc = gvc.clone()
+    bad_gvc[vid[k]] += float(br.xxp[k]) * vc[vid[k]]
+    with pytest.raises(AssertionError, match="k_bwd_v gV: largest .* of 1 occurrences"):
+        fc.check_backward("skipped xxp ", br, hdr, gw, bad_gvc, vs)
+    # ... and for the hot key
+    k = fc.local_id(uniq, b.hot_a)
+    bad_gvc = gvc.clone()
+    bad_gvc[vid[k]] += float(br.xxp[k]) * vc[vid[k]]
+    with pytest.raises(AssertionError):
+        fc.check_backward("skipped xxp ", br, hdr, gw, bad_gvc, vs)
+    # an untouched copy passes
+    fc.check_backward("ref32 ", br, hdr, gw, gvc.clone(), vs)
+
+
+def test_underflow_term_is_inert_at_normal_scale():
+    bound = torch.tensor([0.0, 1e-45, 1e-20], dtype=torch.float64)
+    w = fc._with_underflow(bound, torch.tensor([1, 1, 1]))
+    assert float(w[0]) == 0.0  # a zero bound stays zero: exact match required
+    assert float(w[1]) >= 9 * 2.0 ** -126
+    assert float(w[2]) == pytest.approx(1e-20, rel=1e-12)
+
+
+def test_loss64_saturates_cleanly():
+    py = torch.tensor([-800.0, -100.0, -1.0, 0.0, 1.0, 100.0, 800.0])
+    for lab in (0.0, 1.0):
+        objv, dual = fc.loss64(2, torch.full_like(py, lab), py)
+        assert bool(torch.isfinite(objv).all()) and bool(torch.isfinite(dual).all())
+        y = 1.0 if lab > 0 else -1.0
+        assert float(objv[3]) == pytest.approx(0.6931471805599453)
+        assert float(objv[0 if y > 0 else 6]) == pytest.approx(800.0)
+        assert float(dual[0 if y > 0 else 6]) == pytest.approx(-y)
+        assert float(dual[6 if y > 0 else 0]) == pytest.approx(0.0, abs=1e-300)
+
+
+def test_grad_post_reference_mask():
+    gvc = torch.randn(70, 8, generator=torch.Generator().manual_seed(1))
+    exp, zeroed = fc.grad_post_ref64(gvc, 60, 5, 0.0, 0.3, 77, False)
+    frac = float(zeroed.double().mean())
+    assert 0.2 < frac < 0.4 and zeroed.shape == (60, 5)
+    assert torch.equal(exp[zeroed], torch.zeros(int(zeroed.sum()), dtype=torch.float64))
+    assert torch.equal(exp[~zeroed], gvc[:60, :5].double()[~zeroed])
+    exp, _ = fc.grad_post_ref64(gvc, 60, 5, 0.5, 0.0, 77, True)
+    assert float((exp * exp).sum()) == pytest.approx(1.0)
