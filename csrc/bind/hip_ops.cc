@@ -110,11 +110,11 @@ struct DevWs {
   // heavy-id hints, double-buffered by job parity: keys [2][kPartMaxHeavy]
   // u64, then counts [2][kPartMaxOwners] u32
   Tensor heavy_ws;
-  // the backward's scratch (chunk lists, bucket histograms, offsets) per
-  // stream, grow-only: reused in stream order by the next backward on the
-  // same stream (eight allocations per call were ~20 us of host time, the
-  // bound of the small-minibatch multi-shard step)
-  std::map<hipStream_t, std::vector<Tensor>> bwd_scratch;
+  // the backward's scratch (wh::fm_bwd_layout bytes) per stream, grow-only:
+  // reused in stream order by the next backward on the same stream (eight
+  // allocations per call were ~20 us of host time, the bound of the
+  // small-minibatch multi-shard step)
+  std::map<hipStream_t, Tensor> bwd_scratch;
   int heavy_parity = 0;
   int64_t heavy_layout = -1;  // nshard * 65536 + nho of the set the last job elected
   int part_inflight = 0;
@@ -1125,17 +1125,25 @@ class KVStore {
 };
 
 // --------------------------------------------------------------------- FM
+// The row strides fm.hip has kernels for: 0 (linear) or 4 * 2^k <= 256 floats
+// (a lane group of 1..64 lanes, a float4 each). Checked before anything
+// else, so no tensor of a call with another stride is ever looked at.
+static void check_vstride(int64_t vstride) {
+  TORCH_CHECK(vstride == 0 || (vstride >= 4 && vstride <= 256 && (vstride & (vstride - 1)) == 0),
+              "vstride must be 0 or 4 * 2^k <= 256, got ", vstride);
+}
+
 // difacto: w_or_hdr = hdr [U,2], vc = [m, vstride]; linear: w_or_hdr = w [U]
 std::vector<Tensor> fm_forward(const Tensor& offset, const Tensor& lid,
                                const c10::optional<Tensor>& val, const Tensor& w_or_hdr,
                                const c10::optional<Tensor>& vc, int64_t vstride,
                                const Tensor& label, int64_t loss, const Tensor& met) {
+  check_vstride(vstride);
   CHECK_IN(offset, torch::kInt64);
   CHECK_IN(lid, torch::kInt32);
   CHECK_IN(w_or_hdr, torch::kFloat32);
   CHECK_IN(label, torch::kFloat32);
   CHECK_IN(met, torch::kFloat64);
-  TORCH_CHECK(vstride >= 0 && vstride <= 256 && vstride % 4 == 0, "bad vstride");
   TORCH_CHECK(met.numel() >= 4, "met needs 4 doubles");
   const int64_t nrows = offset.numel() - 1;
   TORCH_CHECK(label.numel() == nrows, "label size mismatch");
@@ -1174,75 +1182,70 @@ std::vector<Tensor> fm_forward(const Tensor& offset, const Tensor& lid,
   return {py, dual, xv};
 }
 
-// Backward scratch + outputs, allocated by phase 1 (the plan):
-// {gw, gvc, chunk_key, chunk_beg, meta_v, bucket_hist, chunk_cnt, chunk_off,
-//  scan_tmp, det (empty unless deterministic)}
-static std::vector<Tensor> fm_bwd_alloc(const Tensor& csc_off, int64_t nnz, int64_t U,
-                                        int64_t vc_rows, int64_t vstride) {
+// The backward's outputs and scratch: {gw [U], gvc [vc_rows, vstride] (linear:
+// empty), scratch [wh::fm_bwd_layout bytes]}. from_ws: the scratch is the
+// current stream's grow-only workspace, good until the next backward on that
+// stream; otherwise fresh memory (a plan outlives the call, and L-BFGS's
+// spmv_t must not pin a data-set-sized buffer).
+static std::vector<Tensor> fm_bwd_alloc(const Tensor& csc_off, int64_t nnz, int64_t vc_rows,
+                                        int64_t vstride, bool from_ws) {
   auto f32 = csc_off.options().dtype(torch::kFloat32);
-  auto i32 = csc_off.options().dtype(torch::kInt32);
-  auto i64 = csc_off.options().dtype(torch::kInt64);
-  auto gw = torch::empty({U}, f32);
-  Tensor gvc = vstride > 0 ? torch::empty({vc_rows, vstride}, f32) : torch::empty({0}, f32);
-  const int64_t cap = wh::fm_bwd_chunks_bound(U, nnz);
-  const int64_t mb = vstride > 0 ? wh::fm_bwd_meta_bound(U, nnz) : 1;
-  Tensor det = deterministic() ? torch::empty({wh::fm_bwd_det_floats(U, nnz, (int)vstride)}, f32)
-                               : torch::empty({0}, f32);
-  return {gw, gvc, torch::empty({cap}, i32), torch::empty({cap}, i32),
-          torch::empty({2 * 4 * mb}, i32), torch::empty({wh::fm_bwd_bucket_scratch()}, i32),
-          torch::empty({std::max<int64_t>(2 * U, 1)}, i64), torch::empty({2 * (U + 1)}, i64),
-          torch::empty({wh::scan_tmp_elems(U)}, i64), det};
+  auto u8 = csc_off.options().dtype(torch::kUInt8);
+  const int64_t U = csc_off.numel() - 1;
+  const int64_t need = wh::fm_bwd_layout(U, nnz, (int)vstride, deterministic());
+  Tensor fresh;
+  Tensor& scratch = from_ws ? dev_ws(csc_off.device()).bwd_scratch[cur_stream(csc_off)] : fresh;
+  if (!scratch.defined() || scratch.numel() < need)
+    scratch = torch::empty({from_ws ? need + need / 4 : need}, u8);
+  return {torch::empty({U}, f32),
+          vstride > 0 ? torch::empty({vc_rows, vstride}, f32) : torch::empty({0}, f32), scratch};
 }
 
-// fm_bwd_alloc's layout with the scratch entries (2..9) taken from the
-// stream's grow-only workspace (only gw / gvc are fresh: they are outputs)
-static std::vector<Tensor> fm_bwd_alloc_ws(const Tensor& csc_off, int64_t nnz, int64_t U,
-                                           int64_t vc_rows, int64_t vstride) {
-  auto f32 = csc_off.options().dtype(torch::kFloat32);
-  auto i32 = csc_off.options().dtype(torch::kInt32);
-  auto i64 = csc_off.options().dtype(torch::kInt64);
-  const int64_t cap = wh::fm_bwd_chunks_bound(U, nnz);
-  const int64_t mb = vstride > 0 ? wh::fm_bwd_meta_bound(U, nnz) : 1;
-  const int64_t need[8] = {cap, cap, 2 * 4 * mb, wh::fm_bwd_bucket_scratch(),
-                           std::max<int64_t>(2 * U, 1), 2 * (U + 1), wh::scan_tmp_elems(U),
-                           deterministic() ? wh::fm_bwd_det_floats(U, nnz, (int)vstride) : 0};
-  const c10::TensorOptions opt[8] = {i32, i32, i32, i32, i64, i64, i64, f32};
-  auto& ws = dev_ws(csc_off.device()).bwd_scratch[cur_stream(csc_off)];
-  if (ws.size() != 8) ws.assign(8, Tensor());
-  std::vector<Tensor> pl(10);
-  pl[0] = torch::empty({U}, f32);
-  pl[1] = vstride > 0 ? torch::empty({vc_rows, vstride}, f32) : torch::empty({0}, f32);
-  for (int i = 0; i < 8; ++i) {
-    if (!ws[i].defined() || ws[i].numel() < need[i])
-      ws[i] = torch::empty({std::max<int64_t>(need[i] + need[i] / 4, 1)}, opt[i]);
-    pl[2 + i] = need[i] == 0 ? ws[i].narrow(0, 0, 0) : ws[i];
-  }
-  return pl;
-}
-
+// two_pass: plan without the look-back scan (count -> scan -> fill), the
+// path of more keys than the scan has tiles
 static void fm_bwd_launch(const std::vector<Tensor>& pl, const Tensor& csc_off,
                           const Tensor& csc_row, const float* csc_val, const float* dual,
-                          const float* xv, const Tensor& w_or_hdr, const float* vcp,
-                          int64_t vstride, int64_t nrows, int phase) {
-  const int64_t U = csc_off.numel() - 1;
+                          const float* xv, const float* hdr, const float* vc, int64_t vstride,
+                          int64_t nrows, wh::FmBwdPhase phase, bool two_pass = false) {
+  wh::FmBwdProblem p;
+  p.nuniq = csc_off.numel() - 1;
+  p.nnz = csc_row.numel();
+  p.nrows = nrows;
+  p.csc_off = ptr<int64_t>(csc_off);
+  p.csc_row = ptr<int32_t>(csc_row);
+  p.csc_val = csc_val;
+  p.dual = dual;
+  p.xv = xv;
+  p.hdr = hdr;
+  p.vc = vc;
+  p.vstride = (int)vstride;
+  p.gw = ptr<float>(pl[0]);
+  p.gvc = pl[1].numel() ? ptr<float>(pl[1]) : nullptr;
+  p.deterministic = deterministic();
   const wh::Lookback lb = lookback(csc_off.device());
-  const Tensor& gvc = pl[1];
-  wh::fm_backward(U, csc_row.numel(), nrows, ptr<int64_t>(csc_off), ptr<int32_t>(csc_row),
-                  csc_val, dual, xv, ptr<float>(w_or_hdr), vcp, (int)vstride, ptr<float>(pl[0]),
-                  gvc.numel() ? ptr<float>(gvc) : nullptr, ptr<int32_t>(pl[2]),
-                  ptr<int32_t>(pl[3]), ptr<int32_t>(pl[4]), ptr<int32_t>(pl[5]),
-                  ptr<int64_t>(pl[6]), ptr<int64_t>(pl[7]), ptr<int64_t>(pl[8]), &lb,
-                  cur_stream(csc_off), pl[9].numel() ? ptr<float>(pl[9]) : nullptr, phase);
+  wh::fm_backward(p, pl[2].data_ptr(), two_pass ? nullptr : &lb, cur_stream(csc_off), phase);
 }
 
 static void fm_bwd_check(const Tensor& csc_off, const Tensor& csc_row, const Tensor& w_or_hdr,
                          int64_t vstride) {
+  check_vstride(vstride);
   CHECK_IN(csc_off, torch::kInt64);
   CHECK_IN(csc_row, torch::kInt32);
   CHECK_IN(w_or_hdr, torch::kFloat32);
-  TORCH_CHECK(vstride >= 0 && vstride <= 256 && vstride % 4 == 0, "bad vstride");
   TORCH_CHECK(w_or_hdr.numel() == (csc_off.numel() - 1) * (vstride > 0 ? 2 : 1),
               "w/hdr must have U rows");
+}
+
+// the dual / xv dependent inputs of fm_backward and fm_backward_run; returns
+// the rows of vc
+static int64_t fm_bwd_check_run(const Tensor& dual, const c10::optional<Tensor>& xv,
+                                const c10::optional<Tensor>& vc, int64_t vstride) {
+  CHECK_IN(dual, torch::kFloat32);
+  if (vstride == 0) return 0;
+  TORCH_CHECK(vc.has_value() && vc->defined() && xv.has_value() && xv->defined(), "vc/xv required");
+  CHECK_IN((*vc), torch::kFloat32);
+  CHECK_IN((*xv), torch::kFloat32);
+  return vc->numel() ? vc->size(0) : 0;
 }
 
 // returns (gw [U], gvc [like vc]) (linear: gvc is empty)
@@ -1251,35 +1254,29 @@ std::vector<Tensor> fm_backward(const Tensor& csc_off, const Tensor& csc_row,
                                 const c10::optional<Tensor>& xv, const Tensor& w_or_hdr,
                                 const c10::optional<Tensor>& vc, int64_t vstride) {
   fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
-  CHECK_IN(dual, torch::kFloat32);
+  const int64_t vrows = fm_bwd_check_run(dual, xv, vc, vstride);
   c10::DeviceGuard g(csc_off.device());
-  const float* vcp = nullptr;
-  int64_t vrows = 0;
-  if (vstride > 0) {
-    TORCH_CHECK(vc.has_value() && vc->defined() && xv.has_value() && xv->defined(), "vc/xv required");
-    CHECK_IN((*vc), torch::kFloat32);
-    CHECK_IN((*xv), torch::kFloat32);
-    vrows = vc->numel() ? vc->size(0) : 0;
-    vcp = vc->numel() ? ptr<float>(*vc) : nullptr;
-  }
-  auto pl = fm_bwd_alloc_ws(csc_off, csc_row.numel(), csc_off.numel() - 1, vrows, vstride);
+  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vrows, vstride, true);
   fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
-                vstride > 0 ? optptr<float>(xv) : nullptr, w_or_hdr, vcp, vstride, dual.numel(), 0);
+                vstride > 0 ? optptr<float>(xv) : nullptr, ptr<float>(w_or_hdr),
+                vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
+                wh::FmBwdPhase::kAll);
   return {pl[0], pl[1]};
 }
 
 // Phase 1 of the backward on the CURRENT stream (the planning that needs no
 // dual: chunk lists, zeroed multi-chunk gradients, V-chunk bucketing); the
 // returned plan is finished by fm_backward_run (same CSC / header / vc).
+// two_pass (tests): see fm_bwd_launch.
 std::vector<Tensor> fm_backward_plan(const Tensor& csc_off, const Tensor& csc_row,
                                      const Tensor& w_or_hdr, int64_t vc_rows, int64_t nrows,
-                                     int64_t vstride) {
+                                     int64_t vstride, bool two_pass) {
   fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
   TORCH_CHECK(vc_rows >= 0 && nrows >= 0, "bad sizes");
   c10::DeviceGuard g(csc_off.device());
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), csc_off.numel() - 1, vc_rows, vstride);
-  fm_bwd_launch(pl, csc_off, csc_row, nullptr, nullptr, nullptr, w_or_hdr, nullptr, vstride,
-                nrows, 1);
+  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vc_rows, vstride, false);
+  fm_bwd_launch(pl, csc_off, csc_row, nullptr, nullptr, nullptr, ptr<float>(w_or_hdr), nullptr,
+                vstride, nrows, wh::FmBwdPhase::kPlan, two_pass);
   return pl;
 }
 
@@ -1289,22 +1286,35 @@ std::vector<Tensor> fm_backward_run(const std::vector<Tensor>& plan, const Tenso
                                     const Tensor& w_or_hdr, const c10::optional<Tensor>& vc,
                                     int64_t vstride) {
   fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
-  CHECK_IN(dual, torch::kFloat32);
-  TORCH_CHECK(plan.size() == 10, "fm_backward_run: not a backward plan");
+  const int64_t vrows = fm_bwd_check_run(dual, xv, vc, vstride);
+  // the plan is fm_bwd_alloc's fresh triple for this call's sizes. The
+  // scratch must have exactly the layout's bytes: with U and vstride fixed
+  // by gw / gvc, every region grows with nnz, so equal totals mean equal
+  // region offsets, and the kernels find the lists where the plan wrote them
+  TORCH_CHECK(plan.size() == 3, "fm_backward_run: not a backward plan");
+  const Tensor &gw = plan[0], &gvc = plan[1], &scratch = plan[2];
+  CHECK_IN(gw, torch::kFloat32);
+  CHECK_IN(gvc, torch::kFloat32);
+  CHECK_IN(scratch, torch::kUInt8);
+  const int64_t U = csc_off.numel() - 1;
+  TORCH_CHECK(gw.numel() == U, "fm_backward_run: U differs from the plan's");
+  TORCH_CHECK(vstride > 0 ? gvc.dim() == 2 && gvc.size(0) == vrows && gvc.size(1) == vstride
+                          : gvc.numel() == 0,
+              "fm_backward_run: vc rows or vstride differ from the plan's");
+  TORCH_CHECK(scratch.numel() == wh::fm_bwd_layout(U, csc_row.numel(), (int)vstride, deterministic()),
+              "fm_backward_run: the plan was made for a CSC of another size");
   c10::DeviceGuard g(csc_off.device());
-  const float* vcp = nullptr;
-  if (vstride > 0) {
-    TORCH_CHECK(vc.has_value() && vc->defined() && xv.has_value() && xv->defined(), "vc/xv required");
-    CHECK_IN((*vc), torch::kFloat32);
-    CHECK_IN((*xv), torch::kFloat32);
-    TORCH_CHECK(plan[1].dim() == 2 && plan[1].size(0) == (vc->numel() ? vc->size(0) : 0),
-                "fm_backward_run: vc rows differ from the plan's");
-    vcp = vc->numel() ? ptr<float>(*vc) : nullptr;
-  }
-  TORCH_CHECK(plan[0].numel() == csc_off.numel() - 1, "fm_backward_run: U differs from the plan's");
+  // a plan allocated on a side stream is finished on this one, and the
+  // caller may drop it as soon as the call returns
+  for (const Tensor& t : plan)
+    if (t.numel())
+      c10::hip::HIPCachingAllocator::recordStream(
+          t.storage().data_ptr(), c10::hip::getCurrentHIPStream(csc_off.device().index()));
   fm_bwd_launch(plan, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
-                vstride > 0 ? optptr<float>(xv) : nullptr, w_or_hdr, vcp, vstride, dual.numel(), 2);
-  return {plan[0], plan[1]};
+                vstride > 0 ? optptr<float>(xv) : nullptr, ptr<float>(w_or_hdr),
+                vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
+                wh::FmBwdPhase::kRun);
+  return {gw, gvc};
 }
 
 // gvc [mcap, vstride]; m: device int64 tensor holding the live row count
@@ -2407,11 +2417,9 @@ Tensor spmv_t(const Tensor& csc_off, const Tensor& csc_row, const c10::optional<
   // (one Criteo value in a third of all rows) costs what its chunk count
   // costs -- one lane per column serialised such a column (298 ms per
   // L-BFGS gradient pass at 4M Criteo rows)
-  const int64_t ncol = csc_off.numel() - 1;
-  auto wdummy = torch::empty({ncol}, p.options());  // (vstride 0: never read)
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), ncol, 0, 0);
-  fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(p), nullptr, wdummy,
-                nullptr, 0, p.numel(), 0);
+  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), 0, 0, false);
+  fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(p), nullptr, nullptr,
+                nullptr, 0, p.numel(), wh::FmBwdPhase::kAll);
   return pl[0];
 }
 
@@ -3820,7 +3828,9 @@ PYBIND11_MODULE(_hip, m) {
         "CUs the persistent FM kernels leave free for concurrent collectives");
   m.def("cu_reserve", []() { return (int64_t)wh::fm_cu_reserve(); });
   m.def("fm_backward", &fm_backward);
-  m.def("fm_backward_plan", &fm_backward_plan);
+  m.def("fm_backward_plan", &fm_backward_plan, py::arg("csc_off"), py::arg("csc_row"),
+        py::arg("hdr"), py::arg("vc_rows"), py::arg("nrows"), py::arg("vstride"),
+        py::arg("two_pass") = false);
   m.def("fm_backward_run", &fm_backward_run);
   m.def("fm_grad_post", &fm_grad_post);
   m.def("vidx_renumber", &vidx_renumber);

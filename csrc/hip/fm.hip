@@ -139,13 +139,11 @@ __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_
   auto load_hdr = [&](int l) {
     return l >= 0 ? hdr[l] : make_float2(0.f, __int_as_float(-1));
   };
-  // gather the embedding rows of one 64-id pass and accumulate them
   int2* st = stage[threadIdx.x >> 6];
   // gather the embedding rows of one 64-id pass and accumulate them
-  auto gather = [&](int n, int vid, float x, float4& s, float4& q2, bool prefetch_first,
+  auto gather = [&](int vid, float x, float4& s, float4& q2, bool prefetch_first,
                     auto&& prefetch) {
-    (void)n;
-    n = stage_pairs_compact<G>(st, lane, vid, x);
+    const int n = stage_pairs_compact<G>(st, lane, vid, x);
 #pragma unroll
     for (int t0 = 0; t0 < S::NI; t0 += S::TI) {
       if (t0 * S::SUB >= n) break;
@@ -182,7 +180,6 @@ __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_
   for (; r < nrows; r += nw) {
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q2 = s;
     float wl = xc * hc.x;
-    const int nc = (int)(ec - bc < 64 ? ec - bc : 64);
     bool fetched = false;
     auto prefetch = [&]() {
       hn = load_hdr(ln);
@@ -190,16 +187,15 @@ __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_
       bounds(r + 3 * nw, b3, e3);
       fetched = true;
     };
-    gather(nc, __float_as_int(hc.y), xc, s, q2, true, prefetch);
+    gather(__float_as_int(hc.y), xc, s, q2, true, prefetch);
     if (!fetched) prefetch();  // empty row
     for (int64_t pb = bc + 64; pb < ec; pb += 64) {  // rest of a long row, unpipelined
-      const int n = (int)(ec - pb < 64 ? ec - pb : 64);
       int l;
       float x;
       load_ids(pb, ec, l, x);
       const float2 h = load_hdr(l);
       wl += x * h.x;
-      gather(n, __float_as_int(h.y), x, s, q2, false, prefetch);
+      gather(__float_as_int(h.y), x, s, q2, false, prefetch);
     }
     // sum the SUB partial rows: lanes gl, gl+G, gl+2G, ... hold the same dims
 #pragma unroll
@@ -244,7 +240,7 @@ __global__ __launch_bounds__(kThreads) void k_lin_fwd(int64_t nrows, const int64
                                                       float* __restrict__ dual_out, double* part,
                                                       double* met, unsigned int* ticket, int acc5) {
   __shared__ double sh[kThreads / 64];
-  const int lane = threadIdx.x & 63, gl = lane & (G - 1);
+  const int gl = threadIdx.x & (G - 1);
   const int64_t ngroups = (int64_t)gridDim.x * (kThreads / G);
   double m_objv = 0, m_corr = 0, m_n = 0;
   for (int64_t row = ((int64_t)blockIdx.x * kThreads + threadIdx.x) / G; row < nrows;
@@ -267,7 +263,6 @@ __global__ __launch_bounds__(kThreads) void k_lin_fwd(int64_t nrows, const int64
       m_n += 1.0;
     }
   }
-  (void)lane;
   block_partials(part, sh, m_objv, m_objv, m_corr, m_n, met, ticket, acc5);
 }
 
@@ -279,82 +274,108 @@ __global__ __launch_bounds__(kThreads) void k_lin_fwd(int64_t nrows, const int64
 // more than one chunk accumulates its chunks with float atomics.
 constexpr int kChunkV = 64;
 
-__global__ __launch_bounds__(kThreads) void k_chunk_count(int64_t nuniq,
-                                                          const int64_t* __restrict__ csc_off,
-                                                          const float2* __restrict__ hdr,
-                                                          int64_t* cnt_s, int64_t* cnt_v) {
-  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (k < nuniq) {
-    const int64_t c = csc_off[k + 1] - csc_off[k];
-    const bool has_v = hdr && __float_as_int(hdr[k].y) >= 0;
-    cnt_s[k] = has_v ? 0 : (c + kChunk - 1) / kChunk;
-    cnt_v[k] = has_v ? (c + kChunkV - 1) / kChunkV : 0;
-  }
+// chunks of a key with cnt occurrences
+__device__ __forceinline__ int64_t key_chunks(int64_t cnt, bool isv) {
+  return isv ? (cnt + kChunkV - 1) / kChunkV : (cnt + kChunk - 1) / kChunk;
 }
 
-// writes both chunk tables; zeroes the gradients of multi-chunk keys. Lane
-// per key for single-chunk keys; a multi-chunk (hot) key is expanded by the
-// whole wave, 64 chunks per round, so the hottest key does not serialise.
-// V chunks get one packed int4 {key, csc begin, n | multi << 8, vidx} each,
-// so the backward wave fetches a chunk's description in one load.
-__global__ __launch_bounds__(kThreads) void k_chunk_fill(int64_t nuniq,
-                                                         const int64_t* __restrict__ csc_off,
-                                                         const int64_t* __restrict__ off_s,
-                                                         const int64_t* __restrict__ off_v,
-                                                         const float2* __restrict__ hdr,
-                                                         int vstride, int32_t* key_s,
-                                                         int32_t* beg_s, int4* meta_v, float* gw,
-                                                         float* gvc) {
+// embedding row of key k, -1 without one (hdr == nullptr: the linear model)
+__device__ __forceinline__ int32_t key_vidx(const float2* __restrict__ hdr, int64_t k) {
+  return hdr ? __float_as_int(hdr[k].y) : -1;
+}
+
+// What the chunk planners write: the scalar chunk list {key, CSC begin}, the
+// V chunk list, one packed int4 {key, CSC begin, n | multi << 8, vidx} each
+// (so the backward wave fetches a chunk's description in one load), and the
+// zeroed gradients of multi-chunk keys.
+struct ChunkOut {
+  int32_t* key_s;
+  int32_t* beg_s;
+  int4* meta_v;
+  float* gw;
+  float* gvc;
+  int vstride;
+};
+
+// The chunks [c0, c0 + nc) of key k (CSC begin b0, cnt occurrences, embedding
+// row vid when isv). Called by all 64 lanes, each with its own key (nc == 0:
+// none): a single-chunk key is written by its lane; a multi-chunk (hot) key
+// is expanded by the whole wave, 64 chunks per round, so the hottest key does
+// not serialise.
+__device__ __forceinline__ void emit_key(const ChunkOut& o, int32_t k, int64_t c0, int32_t nc,
+                                         int32_t b0, int32_t cnt, int32_t vid, int isv) {
   const int lane = threadIdx.x & 63;
-  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  int64_t c0 = 0, nc = 0;
-  int32_t b0 = 0, cnt = 0, vid = -1;
-  int isv = 0;
-  if (k < nuniq) {
-    const int64_t ns = off_s[k + 1] - off_s[k];
-    isv = ns == 0;
-    c0 = isv ? off_v[k] : off_s[k];
-    nc = isv ? off_v[k + 1] - c0 : ns;
-    b0 = (int32_t)csc_off[k];
-    cnt = (int32_t)(csc_off[k + 1] - b0);
-    if (isv) vid = __float_as_int(hdr[k].y);
-    if (nc == 1) {
-      if (isv) {
-        meta_v[c0] = make_int4((int)k, b0, cnt, vid);
-      } else {
-        key_s[c0] = (int32_t)k;
-        beg_s[c0] = b0;
-      }
+  if (nc == 1) {
+    if (isv) {
+      o.meta_v[c0] = make_int4(k, b0, cnt, vid);
+    } else {
+      o.key_s[c0] = k;
+      o.beg_s[c0] = b0;
     }
   }
   uint64_t m = __ballot(nc > 1);
   while (m) {
     const int src = __ffsll((unsigned long long)m) - 1;
     m &= m - 1;
-    const int32_t jk = (int32_t)__shfl((int)k, src, 64);
+    const int32_t jk = __shfl(k, src, 64);
     const int64_t jc0 = __shfl(c0, src, 64);
-    const int64_t jnc = __shfl(nc, src, 64);
+    const int32_t jnc = __shfl(nc, src, 64);
     const int32_t jb0 = __shfl(b0, src, 64);
     const int32_t jcnt = __shfl(cnt, src, 64);
     const int32_t jvid = __shfl(vid, src, 64);
     const int jv = __shfl(isv, src, 64);
-    for (int64_t c = lane; c < jnc; c += 64) {
+    for (int32_t q = lane; q < jnc; q += 64) {
       if (jv) {
-        const int32_t cb = (int32_t)(c * kChunkV);
+        const int32_t cb = q * kChunkV;
         const int32_t n = jcnt - cb < kChunkV ? jcnt - cb : kChunkV;
-        meta_v[jc0 + c] = make_int4(jk, jb0 + cb, n | (1 << 8), jvid);
+        o.meta_v[jc0 + q] = make_int4(jk, jb0 + cb, n | (1 << 8), jvid);
       } else {
-        key_s[jc0 + c] = jk;
-        beg_s[jc0 + c] = jb0 + (int32_t)(c * kChunk);
+        o.key_s[jc0 + q] = jk;
+        o.beg_s[jc0 + q] = jb0 + q * kChunk;
       }
     }
-    if (lane == 0) gw[jk] = 0.f;
+    if (lane == 0) o.gw[jk] = 0.f;
     if (jv) {
-      for (int d = lane * 4; d < vstride; d += 256)
-        *reinterpret_cast<float4*>(gvc + (int64_t)jvid * vstride + d) =
+      for (int d = lane * 4; d < o.vstride; d += 256)
+        *reinterpret_cast<float4*>(o.gvc + (int64_t)jvid * o.vstride + d) =
             make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
+}
+
+// Two-pass plan, for more keys than the look-back scan has tiles:
+// k_chunk_count -> one scan per list -> k_chunk_fill.
+__global__ __launch_bounds__(kThreads) void k_chunk_count(int64_t nuniq,
+                                                          const int64_t* __restrict__ csc_off,
+                                                          const float2* __restrict__ hdr,
+                                                          int64_t* cnt_s, int64_t* cnt_v) {
+  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (k < nuniq) {
+    const bool isv = key_vidx(hdr, k) >= 0;
+    const int64_t n = key_chunks(csc_off[k + 1] - csc_off[k], isv);
+    cnt_s[k] = isv ? 0 : n;
+    cnt_v[k] = isv ? n : 0;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void k_chunk_fill(int64_t nuniq,
+                                                         const int64_t* __restrict__ csc_off,
+                                                         const int64_t* __restrict__ off_s,
+                                                         const int64_t* __restrict__ off_v,
+                                                         const float2* __restrict__ hdr,
+                                                         ChunkOut out) {
+  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  int64_t c0 = 0;
+  int32_t nc = 0, b0 = 0, cnt = 0, vid = -1;
+  if (k < nuniq) {
+    vid = key_vidx(hdr, k);
+    const int64_t* off = vid >= 0 ? off_v : off_s;
+    c0 = off[k];
+    nc = (int32_t)(off[k + 1] - c0);
+    b0 = (int32_t)csc_off[k];
+    cnt = (int32_t)(csc_off[k + 1] - b0);
+  }
+  emit_key(out, (int32_t)k, c0, nc, b0, cnt, vid, vid >= 0);
 }
 
 // Single-pass version of k_chunk_count -> 2 scans -> k_chunk_fill: each tile
@@ -368,33 +389,25 @@ constexpr int kPlanTile = kThreads * kPlanPer;
 __global__ __launch_bounds__(kThreads) void k_chunk_plan(int64_t nuniq,
                                                          const int64_t* __restrict__ csc_off,
                                                          const float2* __restrict__ hdr,
-                                                         int vstride, Lookback lb, int ntiles,
+                                                         Lookback lb, int ntiles,
                                                          int64_t* off_s_tot, int64_t* off_v_tot,
-                                                         int32_t* key_s, int32_t* beg_s,
-                                                         int4* meta_v, float* gw, float* gvc) {
+                                                         ChunkOut out) {
   __shared__ uint32_t shs[16];
   __shared__ int sht;
   const int tile = lb_tile(lb, ntiles, &sht);
-  const int lane = threadIdx.x & 63;
   const int64_t k0 = (int64_t)tile * kPlanTile + threadIdx.x * kPlanPer;
   int64_t co[kPlanPer + 1];
 #pragma unroll
   for (int r = 0; r <= kPlanPer; ++r) co[r] = k0 + r <= nuniq ? csc_off[k0 + r] : 0;
   int32_t vid[kPlanPer];
 #pragma unroll
-  for (int r = 0; r < kPlanPer; ++r)
-    vid[r] = (hdr && k0 + r < nuniq) ? __float_as_int(hdr[k0 + r].y) : -1;
+  for (int r = 0; r < kPlanPer; ++r) vid[r] = k0 + r < nuniq ? key_vidx(hdr, k0 + r) : -1;
   uint32_t c[2] = {0u, 0u};
   uint32_t nc[kPlanPer];
 #pragma unroll
   for (int r = 0; r < kPlanPer; ++r) {
-    nc[r] = 0;
-    if (k0 + r < nuniq) {
-      const int64_t cnt = co[r + 1] - co[r];
-      nc[r] = vid[r] >= 0 ? (uint32_t)((cnt + kChunkV - 1) / kChunkV)
-                          : (uint32_t)((cnt + kChunk - 1) / kChunk);
-      c[vid[r] >= 0 ? 1 : 0] += nc[r];
-    }
+    nc[r] = k0 + r < nuniq ? (uint32_t)key_chunks(co[r + 1] - co[r], vid[r] >= 0) : 0u;
+    c[vid[r] >= 0 ? 1 : 0] += nc[r];
   }
   uint32_t ex[2], tot[2];
   lb_block_scan<2>(lb, tile, c, ex, tot, shs);
@@ -404,48 +417,10 @@ __global__ __launch_bounds__(kThreads) void k_chunk_plan(int64_t nuniq,
   }
 #pragma unroll
   for (int r = 0; r < kPlanPer; ++r) {
-    const int64_t k = k0 + r;
     const int isv = vid[r] >= 0;
-    const int64_t c0 = isv ? ex[1] : ex[0];
+    emit_key(out, (int32_t)(k0 + r), isv ? ex[1] : ex[0], (int32_t)nc[r], (int32_t)co[r],
+             (int32_t)(co[r + 1] - co[r]), vid[r], isv);
     ex[isv ? 1 : 0] += nc[r];
-    const int32_t b0 = (int32_t)co[r];
-    const int32_t cnt = (int32_t)(co[r + 1] - co[r]);
-    if (nc[r] == 1) {
-      if (isv) {
-        meta_v[c0] = make_int4((int)k, b0, cnt, vid[r]);
-      } else {
-        key_s[c0] = (int32_t)k;
-        beg_s[c0] = b0;
-      }
-    }
-    uint64_t m = __ballot(nc[r] > 1);
-    while (m) {  // hot keys: the whole wave expands one key's chunk list
-      const int src = __ffsll((unsigned long long)m) - 1;
-      m &= m - 1;
-      const int32_t jk = (int32_t)__shfl((int)k, src, 64);
-      const int64_t jc0 = __shfl(c0, src, 64);
-      const int64_t jnc = __shfl((int)nc[r], src, 64);
-      const int32_t jb0 = __shfl(b0, src, 64);
-      const int32_t jcnt = __shfl(cnt, src, 64);
-      const int32_t jvid = __shfl(vid[r], src, 64);
-      const int jv = __shfl(isv, src, 64);
-      for (int64_t q = lane; q < jnc; q += 64) {
-        if (jv) {
-          const int32_t cb = (int32_t)(q * kChunkV);
-          const int32_t n = jcnt - cb < kChunkV ? jcnt - cb : kChunkV;
-          meta_v[jc0 + q] = make_int4(jk, jb0 + cb, n | (1 << 8), jvid);
-        } else {
-          key_s[jc0 + q] = jk;
-          beg_s[jc0 + q] = jb0 + (int32_t)(q * kChunk);
-        }
-      }
-      if (lane == 0) gw[jk] = 0.f;
-      if (jv) {
-        for (int d = lane * 4; d < vstride; d += 256)
-          *reinterpret_cast<float4*>(gvc + (int64_t)jvid * vstride + d) =
-              make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
   }
 }
 
@@ -622,8 +597,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
   __shared__ int2 stage[kThreads / 64][64];
   int2* st = stage[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63, gl = lane & (G - 1), sub = lane / G;
-  const int64_t nch_all = *nchunk_p;
-  const int64_t nch = nch_all, nw = (int64_t)gridDim.x * (kThreads / 64);
+  const int64_t nch = *nchunk_p, nw = (int64_t)gridDim.x * (kThreads / 64);
   const int64_t w0 =
       __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6));
   auto get_meta = [&](int64_t c) {
@@ -813,16 +787,23 @@ __global__ __launch_bounds__(kThreads) void k_grad_scale(const int64_t* __restri
 
 }  // namespace
 
-#define WH_DISPATCH_G(G, KERNEL, ...)                                            \
-  switch (G) {                                                                   \
-    case 1: hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__); break;                   \
-    case 2: hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__); break;                   \
-    case 4: hipLaunchKernelGGL(KERNEL<4>, __VA_ARGS__); break;                   \
-    case 8: hipLaunchKernelGGL(KERNEL<8>, __VA_ARGS__); break;                   \
-    case 16: hipLaunchKernelGGL(KERNEL<16>, __VA_ARGS__); break;                 \
-    case 32: hipLaunchKernelGGL(KERNEL<32>, __VA_ARGS__); break;                 \
-    default: hipLaunchKernelGGL(KERNEL<64>, __VA_ARGS__); break;                 \
+// Calls f(std::integral_constant<int, G>) for the lane-group width G =
+// vstride / 4 of an embedding row; the bindings admit no other width.
+template <typename F>
+static void dispatch_g(int G, F&& f) {
+  switch (G) {
+    case 1: f(std::integral_constant<int, 1>()); break;
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 8: f(std::integral_constant<int, 8>()); break;
+    case 16: f(std::integral_constant<int, 16>()); break;
+    case 32: f(std::integral_constant<int, 32>()); break;
+    case 64: f(std::integral_constant<int, 64>()); break;
+    default:
+      fprintf(stderr, "fm.hip: no kernel for vstride %d (4 * 2^k <= 256 only)\n", 4 * G);
+      abort();
   }
+}
 
 int64_t fm_fwd_partials() { return 4 * kFwdBlocks; }
 int64_t fwd_ticket_words() { return kArriveWords; }
@@ -860,12 +841,6 @@ static int resident_blocks(K kernel, int cap) {
   return n < cap ? n : cap;
 }
 
-#define WH_RESIDENT(G, KERNEL, CAP)                                            \
-  ((G) == 1 ? resident_blocks(KERNEL<1>, CAP) : (G) == 2 ? resident_blocks(KERNEL<2>, CAP) \
-   : (G) == 4 ? resident_blocks(KERNEL<4>, CAP) : (G) == 8 ? resident_blocks(KERNEL<8>, CAP) \
-   : (G) == 16 ? resident_blocks(KERNEL<16>, CAP) : (G) == 32 ? resident_blocks(KERNEL<32>, CAP) \
-   : resident_blocks(KERNEL<64>, CAP))
-
 void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const float* val,
                 const float* w_or_hdr, const float* vc, int vstride, const float* label, int loss,
                 float* py, float* dual, float* xv, double* met, double* part,
@@ -873,20 +848,21 @@ void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const 
   if (nrows <= 0) return;
   const int acc5 = (loss >> 8) & 1;  // kLossAcc5: met[4] += flipped accuracy
   loss &= 0xff;
-  int nblk;
   if (vstride == 0) {
     constexpr int G = 8;
-    nblk = grid_for(nrows * G, kThreads, kFwdBlocks);
+    const int nblk = grid_for(nrows * G, kThreads, kFwdBlocks);
     hipLaunchKernelGGL(k_lin_fwd<G>, dim3(nblk), dim3(kThreads), 0, s, nrows, offset, lid, val,
                        w_or_hdr, 1, label, loss, py, dual, part, met, ticket, acc5);
-  } else {
-    const int G = vstride / 4;  // vstride <= 256 enforced by the binding
-    const float2* hdr = reinterpret_cast<const float2*>(w_or_hdr);
-    nblk = grid_for(nrows * 64, kThreads, WH_RESIDENT(G, k_fm_fwd, kFwdBlocks));
-    const dim3 grid(nblk), block(kThreads);
-    WH_DISPATCH_G(G, k_fm_fwd, grid, block, 0, s, nrows, offset, lid, val, hdr, vc, vstride,
-                  label, loss, py, dual, xv, part, met, ticket, acc5);
+    return;
   }
+  const float2* hdr = reinterpret_cast<const float2*>(w_or_hdr);
+  dispatch_g(vstride / 4, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    const int nblk =
+        grid_for(nrows * 64, kThreads, resident_blocks(k_fm_fwd<G>, kFwdBlocks));
+    hipLaunchKernelGGL(k_fm_fwd<G>, dim3(nblk), dim3(kThreads), 0, s, nrows, offset, lid, val,
+                       hdr, vc, vstride, label, loss, py, dual, xv, part, met, ticket, acc5);
+  });
 }
 
 void lin_forward_strided(int64_t nrows, const int64_t* offset, const int32_t* lid,
@@ -906,98 +882,117 @@ void lin_forward_strided(int64_t nrows, const int64_t* offset, const int32_t* li
 static int64_t scalar_cap(int64_t nuniq, int64_t nnz) { return nuniq + nnz / kChunk + 1; }
 static int64_t v_cap(int64_t nuniq, int64_t nnz) { return nuniq + nnz / kChunkV + 1; }
 
-int64_t fm_bwd_chunks_bound(int64_t nuniq, int64_t nnz) {
-  return scalar_cap(nuniq, nnz) + v_cap(nuniq, nnz);
-}
-
-int64_t fm_bwd_meta_bound(int64_t nuniq, int64_t nnz) { return v_cap(nuniq, nnz); }
-
 static int bucket_shift(int64_t nrows) {
   int shift = 0;
   while ((((nrows - 1) >> shift) >= kBuckets)) ++shift;
   return shift;
 }
 
-int64_t fm_bwd_bucket_scratch() { return (int64_t)kBuckets * kBucketBlocks; }
+int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministic,
+                      FmBwdLayout* out) {
+  int64_t at = 0;
+  auto carve = [&](int64_t bytes) {
+    const int64_t o = at;
+    at += (bytes + 255) / 256 * 256;
+    return o;
+  };
+  const int64_t cap_s = scalar_cap(nuniq, nnz), cap_v = vstride > 0 ? v_cap(nuniq, nnz) : 0;
+  FmBwdLayout l;
+  l.key_s = carve(cap_s * 4);
+  l.beg_s = carve(cap_s * 4);
+  l.meta_v = carve(2 * cap_v * 16);
+  l.hist = carve(vstride > 0 ? (int64_t)kBuckets * kBucketBlocks * 4 : 0);
+  l.det_s = carve(deterministic ? cap_s * 4 : 0);
+  l.det_vw = carve(deterministic ? cap_v * 4 : 0);
+  l.det_v = carve(deterministic ? cap_v * vstride * 4 : 0);
+  l.off = carve(2 * (nuniq + 1) * 8);
+  l.cnt = carve(2 * nuniq * 8);
+  l.scan_tmp = carve(scan_tmp_elems(nuniq) * 8);
+  if (out) *out = l;
+  return at;
+}
 
-void fm_backward(int64_t nuniq, int64_t nnz, int64_t nrows, const int64_t* csc_off,
-                 const int32_t* csc_row, const float* csc_val, const float* dual, const float* xv,
-                 const float* hdr_f, const float* vc, int vstride, float* gw, float* gvc,
-                 int32_t* chunk_key, int32_t* chunk_beg, int32_t* meta_v_i32, int32_t* bucket_hist,
-                 int64_t* chunk_cnt, int64_t* chunk_off, int64_t* scan_tmp, const Lookback* lb,
-                 hipStream_t s, float* det_part, int phase) {
-  int4* meta_v = reinterpret_cast<int4*>(meta_v_i32);
+void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipStream_t s,
+                 FmBwdPhase phase) {
+  const int64_t nuniq = p.nuniq;
   if (nuniq <= 0) return;
-  const float2* hdr = vstride > 0 ? reinterpret_cast<const float2*>(hdr_f) : nullptr;
-  int64_t* cnt_s = chunk_cnt;
-  int64_t* cnt_v = chunk_cnt + nuniq;
-  int64_t* off_s = chunk_off;
-  int64_t* off_v = chunk_off + nuniq + 1;
-  const int64_t cap_s = scalar_cap(nuniq, nnz);
-  int32_t* key_s = chunk_key;
-  int32_t* beg_s = chunk_beg;
-  const int64_t ntiles = (nuniq + kPlanTile - 1) / kPlanTile;
-  const int64_t vcap = v_cap(nuniq, nnz);
-  // V chunks ordered by first-row bucket (meta_v[cap..2cap) receives the
-  // list); deterministic mode keeps the key-major list (partials by index),
-  // and so does a minibatch whose xv rows fit in L2 many times over (the
-  // bucketing buys locality there is no need for: three launches of host
+  const int vstride = p.vstride;
+  const float2* hdr = vstride > 0 ? reinterpret_cast<const float2*>(p.hdr) : nullptr;
+  FmBwdLayout l;
+  fm_bwd_layout(nuniq, p.nnz, vstride, p.deterministic, &l);
+  char* base = static_cast<char*>(scratch);
+  int32_t* key_s = reinterpret_cast<int32_t*>(base + l.key_s);
+  int32_t* beg_s = reinterpret_cast<int32_t*>(base + l.beg_s);
+  int4* meta_v = reinterpret_cast<int4*>(base + l.meta_v);
+  int64_t* off_s = reinterpret_cast<int64_t*>(base + l.off);
+  int64_t* off_v = off_s + nuniq + 1;
+  const int64_t cap_s = scalar_cap(nuniq, p.nnz), cap_v = v_cap(nuniq, p.nnz);
+  // V chunks ordered by first-row bucket (the second half of meta_v receives
+  // the list); deterministic mode keeps the key-major list (partials by
+  // index), and so does a minibatch whose xv rows fit in L2 many times over
+  // (the bucketing buys locality there is no need for: three launches of host
   // time in a launch-bound small step)
-  const bool bucket = hdr && !det_part && nrows * (int64_t)vstride * 4 > ((int64_t)2 << 20);
-  int4* meta_sorted = bucket ? meta_v + vcap : meta_v;
-  if (phase != 2) {
-  if (lb && ntiles <= kLbMaxTiles) {  // one launch
-    hipLaunchKernelGGL(k_chunk_plan, dim3((unsigned)ntiles), dim3(kThreads), 0, s, nuniq, csc_off,
-                       hdr, vstride, *lb, (int)ntiles, off_s + nuniq, off_v + nuniq, key_s, beg_s,
-                       meta_v, gw, gvc);
-  } else {
-    hipLaunchKernelGGL(k_chunk_count, dim3(grid_for(nuniq, kThreads)), dim3(kThreads), 0, s,
-                       nuniq, csc_off, hdr, cnt_s, cnt_v);
-    scan_i64(cnt_s, off_s, nuniq, scan_tmp, s);
-    if (hdr) scan_i64(cnt_v, off_v, nuniq, scan_tmp, s);
-    hipLaunchKernelGGL(k_chunk_fill, dim3(grid_for(nuniq, kThreads)), dim3(kThreads), 0, s,
-                       nuniq, csc_off, off_s, off_v, hdr, vstride, key_s, beg_s, meta_v, gw, gvc);
+  const bool bucket =
+      hdr && !p.deterministic && p.nrows * (int64_t)vstride * 4 > ((int64_t)2 << 20);
+  int4* meta_sorted = bucket ? meta_v + cap_v : meta_v;
+  if (phase != FmBwdPhase::kRun) {
+    const ChunkOut out = {key_s, beg_s, meta_v, p.gw, p.gvc, vstride};
+    const int64_t ntiles = (nuniq + kPlanTile - 1) / kPlanTile;
+    if (lb && ntiles <= kLbMaxTiles) {  // one launch
+      hipLaunchKernelGGL(k_chunk_plan, dim3((unsigned)ntiles), dim3(kThreads), 0, s, nuniq,
+                         p.csc_off, hdr, *lb, (int)ntiles, off_s + nuniq, off_v + nuniq, out);
+    } else {
+      int64_t* cnt_s = reinterpret_cast<int64_t*>(base + l.cnt);
+      int64_t* cnt_v = cnt_s + nuniq;
+      int64_t* scan_tmp = reinterpret_cast<int64_t*>(base + l.scan_tmp);
+      const dim3 grid(grid_for(nuniq, kThreads));
+      hipLaunchKernelGGL(k_chunk_count, grid, dim3(kThreads), 0, s, nuniq, p.csc_off, hdr, cnt_s,
+                         cnt_v);
+      scan_i64(cnt_s, off_s, nuniq, scan_tmp, s);
+      if (hdr) scan_i64(cnt_v, off_v, nuniq, scan_tmp, s);
+      hipLaunchKernelGGL(k_chunk_fill, grid, dim3(kThreads), 0, s, nuniq, p.csc_off, off_s, off_v,
+                         hdr, out);
+    }
+    if (bucket) {
+      int32_t* hist = reinterpret_cast<int32_t*>(base + l.hist);
+      const int shift = bucket_shift(std::max<int64_t>(p.nrows, 1));
+      hipLaunchKernelGGL(k_vchunk_hist, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
+                         meta_v, p.csc_row, shift, hist);
+      hipLaunchKernelGGL(k_vchunk_scan, dim3(1), dim3(kBuckets * kScanParts), 0, s, hist);
+      hipLaunchKernelGGL(k_vchunk_scatter, dim3(kBucketBlocks), dim3(kThreads), 0, s,
+                         off_v + nuniq, meta_v, p.csc_row, shift, hist, meta_sorted);
+    }
   }
-  if (bucket) {
-    const int shift = bucket_shift(std::max<int64_t>(nrows, 1));
-    hipLaunchKernelGGL(k_vchunk_hist, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
-                       meta_v, csc_row, shift, bucket_hist);
-    hipLaunchKernelGGL(k_vchunk_scan, dim3(1), dim3(kBuckets * kScanParts), 0, s, bucket_hist);
-    hipLaunchKernelGGL(k_vchunk_scatter, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
-                       meta_v, csc_row, shift, bucket_hist, meta_sorted);
-  }
-  }
-  if (phase == 1) return;
+  if (phase == FmBwdPhase::kPlan) return;
   // chunk counts are device values (off[nuniq]); the scalar kernel launches
   // over the host-side bound and surplus lanes exit; the V kernel is
   // persistent. No host synchronisation in the step.
-  // deterministic scratch: [cap_s] scalar partials | [vcap] V-chunk gw | [vcap, vstride] rows
-  float* pgs = det_part;
-  float* pgv_w = det_part ? det_part + cap_s : nullptr;
-  float* pgv = det_part ? pgv_w + vcap : nullptr;
+  const bool det = p.deterministic;
+  float* pgs = det ? reinterpret_cast<float*>(base + l.det_s) : nullptr;
+  float* pgv_w = det ? reinterpret_cast<float*>(base + l.det_vw) : nullptr;
+  float* pgv = det ? reinterpret_cast<float*>(base + l.det_v) : nullptr;
   hipLaunchKernelGGL(k_bwd_scalar, dim3(grid_for(cap_s, kThreads)), dim3(kThreads), 0, s,
-                     off_s + nuniq, key_s, beg_s, csc_off, csc_row, csc_val, dual, gw, pgs);
-  if (det_part)
+                     off_s + nuniq, key_s, beg_s, p.csc_off, p.csc_row, p.csc_val, p.dual, p.gw,
+                     pgs);
+  if (det)
     hipLaunchKernelGGL(k_bwd_reduce_s, dim3(grid_for(cap_s, kThreads)), dim3(kThreads), 0, s,
-                       off_s + nuniq, key_s, beg_s, csc_off, pgs, gw);
+                       off_s + nuniq, key_s, beg_s, p.csc_off, pgs, p.gw);
   if (!hdr) return;
-  const int G = vstride / 4;
-  int64_t vblk = std::min<int64_t>((v_cap(nuniq, nnz) + 3) / 4,
-                                   WH_RESIDENT(G, k_bwd_v, 2048));
   // (an XCD-aware split of the chunk list -- group b % 8 of the blocks on
   // the b % 8-th eighth -- raised this kernel's L2 hit rate 44.5 -> 54.7 %
   // but cost the step 1.5 %: the groups' uneven ends leave a tail beside the
   // concurrent localize; measured round 4, removed)
-  const dim3 grid((unsigned)vblk), block(kThreads);
-  WH_DISPATCH_G(G, k_bwd_v, grid, block, 0, s, off_v + nuniq, meta_sorted, csc_row, csc_val,
-                dual, xv, vc, vstride, gw, gvc, pgv_w, pgv);
-  if (det_part)
-    hipLaunchKernelGGL(k_bwd_reduce_v, dim3(grid_for(vcap * 64, kThreads)), dim3(kThreads), 0, s,
-                       off_v + nuniq, meta_v, csc_off, pgv_w, pgv, vstride, gw, gvc);
-}
-
-int64_t fm_bwd_det_floats(int64_t nuniq, int64_t nnz, int vstride) {
-  return scalar_cap(nuniq, nnz) + v_cap(nuniq, nnz) * (1 + (int64_t)vstride);
+  dispatch_g(vstride / 4, [&](auto g) {
+    constexpr int G = decltype(g)::value;
+    const int64_t vblk =
+        std::min<int64_t>((cap_v + 3) / 4, resident_blocks(k_bwd_v<G>, 2048));
+    hipLaunchKernelGGL(k_bwd_v<G>, dim3((unsigned)vblk), dim3(kThreads), 0, s, off_v + nuniq,
+                       meta_sorted, p.csc_row, p.csc_val, p.dual, p.xv, p.vc, vstride, p.gw,
+                       p.gvc, pgv_w, pgv);
+  });
+  if (det)
+    hipLaunchKernelGGL(k_bwd_reduce_v, dim3(grid_for(cap_v * 64, kThreads)), dim3(kThreads), 0, s,
+                       off_v + nuniq, meta_v, p.csc_off, pgv_w, pgv, vstride, p.gw, p.gvc);
 }
 
 void fm_grad_post(const int64_t* m, int64_t m_cap, float* gvc, int vstride, int dim, float clip,

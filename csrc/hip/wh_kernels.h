@@ -325,26 +325,40 @@ void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const 
 // Backward: gw[U] for every key, gvc[m] for the keys with an embedding row
 //   gw_k = sum_i dual_i x_ik
 //   gV_k = sum_i dual_i x_ik xv_i - (sum_i dual_i x_ik^2) V_k
-int64_t fm_bwd_chunks_bound(int64_t nuniq, int64_t nnz);
-// scratch: chunk_key/chunk_beg [fm_bwd_chunks_bound], meta_v [2 x 4 fm_bwd_meta_bound]
-// int32 (16-byte aligned), bucket_hist [fm_bwd_bucket_scratch] int32,
-// chunk_cnt [2 nuniq], chunk_off [2 (nuniq + 1)], scan_tmp [scan_tmp_elems(nuniq)]
-int64_t fm_bwd_meta_bound(int64_t nuniq, int64_t nnz);
-int64_t fm_bwd_bucket_scratch();
-void fm_backward(int64_t nuniq, int64_t nnz, int64_t nrows, const int64_t* csc_off,
-                 const int32_t* csc_row, const float* csc_val, const float* dual, const float* xv,
-                 const float* hdr, const float* vc, int vstride, float* gw, float* gvc,
-                 int32_t* chunk_key, int32_t* chunk_beg, int32_t* meta_v, int32_t* bucket_hist,
-                 int64_t* chunk_cnt, int64_t* chunk_off, int64_t* scan_tmp, const Lookback* lb,
-                 hipStream_t s, float* det_part = nullptr, int phase = 0);
-// phase: 0 = the whole backward; 1 = only the planning that needs no dual
-// (chunk lists + V-chunk bucketing: CSC offsets and the pull header), so it
-// can run on a side stream concurrently with the forward; 2 = the rest
-// (dual / xv dependent), after phase 1 with the same scratch.
-// det_part (deterministic mode, WH_DETERMINISTIC=1): scratch of
-// fm_bwd_det_floats floats; hot keys' chunk partials are then summed in
-// occurrence order by a second pass instead of float atomics
-int64_t fm_bwd_det_floats(int64_t nuniq, int64_t nnz, int vstride);
+struct FmBwdProblem {
+  int64_t nuniq, nnz, nrows;
+  const int64_t* csc_off;  // [nuniq + 1]
+  const int32_t* csc_row;  // [nnz]
+  const float* csc_val;    // [nnz], null = all ones
+  const float *dual, *xv;  // [nrows], [nrows, vstride]  (with vc: unused by kPlan)
+  const float *hdr, *vc;   // float2 [nuniq] {w, vidx}, [m, vstride]  (vstride 0: unused)
+  int vstride;             // 0 (linear) or 4 * 2^k <= 256
+  float *gw, *gvc;         // out: [nuniq], [m, vstride]
+  // (WH_DETERMINISTIC=1) hot keys' chunk partials are summed in occurrence
+  // order by a second pass instead of float atomics
+  bool deterministic;
+};
+// kPlan: only the planning that needs no dual (chunk lists + V-chunk
+// bucketing: CSC offsets and the pull header), so it can run on a side stream
+// concurrently with the forward; kRun: the rest (dual / xv dependent), after
+// kPlan with the same problem sizes and scratch; kAll: both.
+enum class FmBwdPhase { kAll, kPlan, kRun };
+// The backward's scratch is ONE buffer of fm_bwd_layout(...) bytes (16-byte
+// aligned base); the regions' byte offsets, for the record:
+struct FmBwdLayout {
+  int64_t key_s, beg_s;          // scalar chunks: int32 [nuniq + nnz / 32 + 1] each
+  int64_t meta_v;                // V chunks: int4 [2][nuniq + nnz / 64 + 1] (key-major, bucketed)
+  int64_t hist;                  // V-chunk bucket histograms, int32
+  int64_t det_s, det_vw, det_v;  // deterministic partials: scalar gw, V gw, V rows
+  int64_t off;                   // int64 [2][nuniq + 1] chunk offsets; [.][nuniq] = the totals
+  int64_t cnt, scan_tmp;         // two-pass plan only: int64 [2][nuniq], scan_i64's tmp
+};
+int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministic,
+                      FmBwdLayout* out = nullptr);
+// lb == nullptr (or more keys than the look-back scan has tiles): the
+// two-pass plan (count -> scan -> fill) instead of the single-launch one
+void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipStream_t s,
+                 FmBwdPhase phase);
 // post-process the m (device count) V-gradient rows: clip to [-c, c] (c>0),
 // dropout with prob p (p>0); sumsq (optional) receives the squared norm
 void fm_grad_post(const int64_t* m, int64_t m_cap, float* gvc, int vstride, int dim, float clip,

@@ -467,10 +467,12 @@ def localize_checked(hip, dev, batch):
 
 
 def run_fm_case(hip, dev, batch, loc, vstride, loss, w_scale=1.0, deep=False, tag="",
-                repeat_bitwise=False):
+                repeat_bitwise=False, two_pass=False):
     """Forward (met of 4 and of 5 slots), one-call backward and the
     plan-on-a-side-stream + run backward of one model on a localized batch,
-    all against the float64 references. Returns the forward reference."""
+    all against the float64 references. two_pass: the plan comes from the
+    count -> scan -> fill planner (and the linear model is planned and run
+    too). Returns the forward reference."""
     uniq, ucnt, oc, lid, csc_off, csc_row, csc_val = loc
     with_val = batch.val is not None
     hdr, vc = make_model(batch, uniq, vstride, 5, w_scale)
@@ -494,18 +496,22 @@ def run_fm_case(hip, dev, batch, loc, vstride, loss, w_scale=1.0, deep=False, ta
         live = live_rows(hdr).to(dev)
         assert torch.equal(gw_a, gw_b), "gw differs between two deterministic backward calls"
         assert torch.equal(gvc_a[live], gvc_b[live]), "gV differs between two deterministic calls"
-    if vstride:
+    if vstride or two_pass:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            plan = hip.fm_backward_plan(csc_off, csc_row, hdr_d, vc.shape[0], batch.nrows, vstride)
+            plan = hip.fm_backward_plan(csc_off, csc_row, hdr_d, vc.shape[0] if vstride else 0,
+                                        batch.nrows, vstride, two_pass=two_pass)
         torch.cuda.current_stream(dev).wait_stream(side)
-        gw2, gvc2 = hip.fm_backward_run(plan, csc_off, csc_row, cv, dual, xv, hdr_d, vc_d, vstride)
+        gw2, gvc2 = hip.fm_backward_run(plan, csc_off, csc_row, cv, dual, xv_in, hdr_d, vc_d,
+                                        vstride)
+        del plan  # fm_backward_run has recorded this stream on the side stream's memory
         check_backward(tag, br, hdr, gw2, gvc2, vstride)
     return fr
 
 
-def run_depth_case(hip, dev, vstride, with_val, localized, deterministic=False, tag=""):
+def run_depth_case(hip, dev, vstride, with_val, localized, deterministic=False, tag="",
+                   two_pass=False):
     """Section "deep batch" of the FM kernel tests; `localized` caches the
     checked hip.localize outputs per batch."""
     batch = deep_batch(with_val)
@@ -516,4 +522,4 @@ def run_depth_case(hip, dev, vstride, with_val, localized, deterministic=False, 
     bucketed = batch.nrows * vstride * 4 > BUCKET_BYTES and not deterministic
     assert bucketed == (vstride >= 16 and not deterministic)
     run_fm_case(hip, dev, batch, localized[key], vstride, ref.LOSS_LOGIT, deep=True, tag=tag,
-                repeat_bitwise=deterministic)
+                repeat_bitwise=deterministic, two_pass=two_pass)

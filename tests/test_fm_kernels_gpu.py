@@ -4,7 +4,8 @@ pipeline depth (every persistent wave runs >= 5 rows / chunks), rows of 0, 1,
 63..65, 127..129, 191..193 and 500 non-zeros, runs of empty rows, all seven
 lane-group shapes (vstride 4..256), valued data, hot keys of more than 64
 chunks (embedded and scalar), both chunk orders of the backward, all three
-losses, the 5-slot metrics, saturated margins, the deterministic mode, and
+losses, the 5-slot metrics, saturated margins, the deterministic mode, the
+two-pass chunk planner, a plan run against a CSC of another size, and
 k_grad_post past one step of its capped grid with dropout.
 """
 import os
@@ -87,6 +88,52 @@ def _all_rows_empty(hip, vstride, loss):
     acc = correct / n
     assert float(met[2]) == correct and float(met[3]) == float(n)
     assert float(met[4]) == (acc if acc > 0.5 else 1.0 - acc)
+
+
+@pytest.mark.parametrize("vstride", [0, 16, 64])
+def test_fm_two_pass_plan_deep(hip, localized, vstride):
+    """fm_backward_plan(two_pass=True): k_chunk_count -> scans -> k_chunk_fill,
+    the planner of minibatches with more unique keys than the look-back scan
+    has tiles. The deep batch's planted keys (~16 000 occurrences: about 250 V
+    chunks or 500 scalar chunks) take the whole-wave expansion through more
+    than one round of 64; vstride 0 plans and runs the linear model."""
+    fc.run_depth_case(hip, DEV, vstride, False, localized, two_pass=True, tag="two-pass ")
+
+
+def test_fm_two_pass_plan_edges(hip, localized):
+    batch = fc.edge_batch(False)
+    if id(batch) not in localized:
+        localized[id(batch)] = fc.localize_checked(hip, DEV, batch)
+    fc.run_fm_case(hip, DEV, batch, localized[id(batch)], 4, ref.LOSS_LOGIT, two_pass=True,
+                   tag="two-pass ")
+
+
+@pytest.mark.parametrize("vstride", [0, 4])
+def test_fm_backward_run_rejects_a_plan_of_another_size(hip, vstride):
+    """A plan holds chunk lists sized for its CSC's non-zeros: run with a CSC
+    of the same U and 40 times the non-zeros (or the reverse) it must raise
+    before any kernel indexes the lists."""
+    U, nrows = 1000, 64
+    w = torch.zeros(U)
+    hdr = (ref.make_hdr(w, torch.arange(U)) if vstride else w).to(DEV)
+    vc = torch.zeros(U, vstride, device=DEV) if vstride else None
+    dual = torch.zeros(nrows, device=DEV)
+    xv = torch.zeros(nrows * vstride, device=DEV) if vstride else None
+
+    def csc(per):
+        off = torch.arange(U + 1, dtype=torch.int64, device=DEV) * per
+        row = (torch.arange(U * per, device=DEV) % nrows).to(torch.int32)
+        return off, row
+
+    small, big = csc(1), csc(40)
+    for a, b in ((small, big), (big, small)):
+        plan = hip.fm_backward_plan(a[0], a[1], hdr, U if vstride else 0, nrows, vstride)
+        with pytest.raises(RuntimeError, match="CSC of another size"):
+            hip.fm_backward_run(plan, b[0], b[1], None, dual, xv, hdr, vc, vstride)
+        gw, gvc = hip.fm_backward_run(plan, a[0], a[1], None, dual, xv, hdr, vc, vstride)
+        assert torch.equal(gw.cpu(), torch.zeros(U))  # the plan itself is intact
+    with pytest.raises(RuntimeError, match="not a backward plan"):
+        hip.fm_backward_run(plan[:2], big[0], big[1], None, dual, xv, hdr, vc, vstride)
 
 
 def test_fm_deterministic_matches_reference():

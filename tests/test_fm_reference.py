@@ -145,6 +145,31 @@ def test_check_rejects_kernel_like_errors(deep):
     fc.check_backward("ref32 ", br, hdr, gw, gvc.clone(), vs)
 
 
+@pytest.mark.parametrize("vstride,match", [(12, "vstride"), (260, "vstride"),
+                                           (16, "must be a GPU tensor")])
+def test_bindings_check_vstride_before_the_tensors(vstride, match):
+    """The FM bindings admit vstride 0 or 4 * 2^k <= 256 (fm.hip has no
+    kernel for another lane-group width) and check it before they look at a
+    tensor: CPU tensors of the right shapes get the vstride error at 12 and
+    260, the GPU-tensor error at 16. Nothing is launched either way."""
+    from wormhole_amd import _native
+    hip = _native.hip()
+    n = 5  # rows = unique keys = non-zeros = embedding rows
+    off = torch.arange(n + 1)
+    idx = torch.arange(n, dtype=torch.int32)
+    hdr, vc = ref.make_hdr(torch.zeros(n), torch.arange(n)), torch.zeros(n, vstride)
+    dual, xv = torch.zeros(n), torch.zeros(n * vstride)
+    met = torch.zeros(4, dtype=torch.float64)
+    with pytest.raises(RuntimeError, match=match):
+        hip.fm_forward(off, idx, None, hdr, vc, vstride, torch.zeros(n), 2, met)
+    with pytest.raises(RuntimeError, match=match):
+        hip.fm_backward(off, idx, None, dual, xv, hdr, vc, vstride)
+    with pytest.raises(RuntimeError, match=match):
+        hip.fm_backward_plan(off, idx, hdr, n, n, vstride)
+    with pytest.raises(RuntimeError, match=match):
+        hip.fm_backward_run([], off, idx, None, dual, xv, hdr, vc, vstride)
+
+
 def test_underflow_term_is_inert_at_normal_scale():
     bound = torch.tensor([0.0, 1e-45, 1e-20], dtype=torch.float64)
     w = fc._with_underflow(bound, torch.tensor([1, 1, 1]))

@@ -89,12 +89,14 @@ def fm_backward(csc_off, csc_row, csc_val, dual, xv, w_or_hdr, vc, vstride):
     return ref.fm_backward(csc_off, csc_row, csc_val, dual, xv, w_or_hdr, vc, vstride)
 
 
-def fm_backward_plan(csc_off, csc_row, hdr, vc_rows, nrows, vstride):
+def fm_backward_plan(csc_off, csc_row, hdr, vc_rows, nrows, vstride, two_pass=False):
     """GPU: phase 1 of :func:`fm_backward` on the current stream -- the
     planning that needs no dual (chunk lists, V-chunk bucketing), so it can
-    overlap the forward; :func:`fm_backward_run` finishes it."""
+    overlap the forward; :func:`fm_backward_run` finishes it. The plan is
+    opaque. two_pass (tests only): take the count -> scan -> fill planner of
+    minibatches with more than 67 M unique keys."""
     return _native.hip().fm_backward_plan(csc_off, csc_row, hdr, int(vc_rows), int(nrows),
-                                          int(vstride))
+                                          int(vstride), two_pass=bool(two_pass))
 
 
 def fm_backward_run(plan, csc_off, csc_row, csc_val, dual, xv, hdr, vc, vstride):
