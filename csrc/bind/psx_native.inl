@@ -286,7 +286,7 @@ class PsxStep {
           std::vector<double> post)
       : store_(store), P_(P), S_(S), rank_(rank), linear_(linear), lin_hp_(std::move(lin_hp)),
         hp_(std::move(hp)), threshold_(threshold), l1_shrk_(l1_shrk), seed_(seed), loss_(loss),
-        met_(std::move(met)), auc_sum_(std::move(auc_sum)), tau_(tau), max_load_(max_load) {
+        met_(std::move(met)), auc_sum_(std::move(auc_sum)), tau_(tau), guard_(store, max_load) {
     TORCH_CHECK(P >= 2 && S >= 1 && S <= P && rank >= 0 && rank < P, "PsxStep: bad P / S / rank");
     TORCH_CHECK(lin_hp_.size() == 5 && hp_.size() == 8, "PsxStep: hyper-parameter sizes");
     // filt = (fixed_bytes, filter seed): ps-lite's FIXING_FLOAT filter on the
@@ -354,7 +354,6 @@ class PsxStep {
       xs_ = c10::hip::getStreamFromExternal(xs_h_, dev_);
     }
     for (auto& e : ring_) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto& e : gev_) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (auto& p : sev_)
       for (auto& e : p) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (tx_ == kTxRccl) wh::fm_set_cu_reserve((int)cu_reserve);
@@ -385,7 +384,6 @@ class PsxStep {
     job_.reset();
     (void)hipDeviceSynchronize();
     for (auto& e : ring_) (void)hipEventDestroy(e);
-    for (auto& e : gev_) (void)hipEventDestroy(e);
     for (auto& p : sev_)
       for (auto& e : p) (void)hipEventDestroy(e);
     for (auto& e : pin_ev_) (void)hipEventDestroy(e);
@@ -533,17 +531,17 @@ class PsxStep {
     return o;
   }
   double watchdog_deadline() const { return wd_ ? wd_->deadline() : 0.0; }
-  int64_t grows() const { return grows_; }
-  int64_t vgrows() const { return vgrows_; }
+  int64_t grows() const { return guard_.grows(); }
+  int64_t vgrows() const { return guard_.vgrows(); }
   int64_t requests() const { return requests_; }
   void set_requests(int64_t r) { requests_ = r; }
   int64_t step() const { return step_; }
   void set_step(int64_t s) { step_ = s; }
   // the guard's last summary {keys, failed inserts, V overflows, V rows}
   std::vector<int64_t> guard_sync() {
-    guard_after(true);
-    guard_read();
-    return {gkeys_, 0, 0, gvused_};
+    summarise();
+    mark("store summary read (host wait)", -1);
+    return guard_.sync();
   }
 
  private:
@@ -979,7 +977,19 @@ class PsxStep {
   void open(PsxSt& st, bool insert, const Tensor& prepped = Tensor()) {
     st.w_c1.wait();
     const int64_t n = vsum(st.recv);
-    if (insert) guard_before(n);
+    if (insert) {
+      if (guard_.pending()) mark("store summary read (host wait)", -1);
+      Tensor remap = guard_.before(n);
+      if (remap.defined()) {  // the table grew: the live steps' slot ids move with it
+        std::vector<PsxSt*> live{pull_.get()};
+        for (auto& p : pushes_) live.push_back(p.get());
+        for (PsxSt* l : live)
+          if (l && l->slot.defined() && l->slot.numel()) {
+            auto s64 = l->slot.to(torch::kInt64);
+            l->slot = torch::where(s64 >= 0, remap.index_select(0, s64.clamp_min(0)), l->slot);
+          }
+      }
+    }
     const int64_t rows = linear_ ? 0 : vsum(st.Ho) + n;
     auto o = store_->ps_open(st.keys_o, st.use_cnt, st.segS_o, st.segHS_o, rows, insert, st.train,
                              hp_, threshold_, l1_shrk_, seed_,
@@ -993,9 +1003,9 @@ class PsxStep {
     st.keys_o = Tensor();
     if (!sx_) WH_HIP_CHECK_HOST(hipEventRecord(st.own_open, S_stream_.stream()));
     st.ev_open = sx_ ? nullptr : st.own_open;
-    // the summary every gevery_ opens: in between, guard_before's estimate
-    // counts every key inserted since the last one (gsince_), an upper bound
-    if (insert && ++gskip_ >= gevery_) guard_after(false);
+    // the summary every gevery_ opens: in between, the guard's estimate
+    // counts every key opened since the last one, an upper bound
+    if (insert && ++gskip_ >= gevery_) summarise();
   }
 
   void c2(PsxSt& st) {
@@ -1179,65 +1189,13 @@ class PsxStep {
     st.gpush = st.slot = st.vpos = st.chain = st.head = Tensor();
   }
 
-  // ------------------------------------------------------------ store guard
-  // kv/__init__.py StoreGuard: before an open, the previous summary (one
-  // open behind: long complete) is checked -- a lost key or row raises --
-  // and the table / V slab grow so the coming open cannot overflow them;
-  // after it a summary is enqueued on a side stream.
-  // (summary slots 2 / 3 of the store: 0 / 1 belong to the Python guard)
-  void guard_read() {
-    if (!gpend_) return;
-    mark("store summary read (host wait)", -1);
-    wait_event(gev_[gk_]);
-    gpend_ = false;
-    auto h = store_->summary_read(2 + gk_);
-    gkeys_ = h[0];
-    gvused_ = h[3];
-    TORCH_CHECK(h[1] == 0 && h[2] == 0, "parameter store shard lost data: ", h[1],
-                " failed inserts, ", h[2], " embedding rows dropped (table ", h[0], "/",
-                store_->cap(), " keys, V slab ", h[3], "/", store_->vcap(), " rows)");
-  }
-  void guard_before(int64_t n) {
-    guard_read();
-    const int64_t need = gkeys_ + gsince_ + n;
-    if ((double)need > max_load_ * (double)store_->cap()) {
-      int64_t cap = store_->cap();
-      while ((double)need > 0.5 * (double)cap) cap *= 2;
-      Tensor remap = store_->grow(cap);
-      ++grows_;
-      std::vector<PsxSt*> live{pull_.get()};
-      for (auto& p : pushes_) live.push_back(p.get());
-      for (PsxSt* st : live)
-        if (st && st->slot.defined() && st->slot.numel()) {
-          auto s64 = st->slot.to(torch::kInt64);
-          st->slot = torch::where(s64 >= 0, remap.index_select(0, s64.clamp_min(0)), st->slot);
-        }
-    }
-    if (vs_ > 0) {
-      const int64_t vneed = gvused_ + gsince_ + n + grecent_[0] + grecent_[1];
-      if (vneed > store_->vcap()) {
-        int64_t vcap = std::max<int64_t>(store_->vcap(), 1);
-        while (vneed > vcap) vcap *= 2;
-        store_->grow_v(vcap);
-        ++vgrows_;
-      }
-    }
-    gsince_ += n;
-    grecent_[0] = grecent_[1];
-    grecent_[1] = n;
-  }
-  void guard_after(bool sync) {
+  // the store guard's summary (StoreGuard::after) on a side stream behind
+  // the open
+  void summarise() {
     gskip_ = 0;
-    gk_ ^= 1;
     wait_on(cs_, S_stream_);
-    {
-      c10::hip::HIPStreamGuard sg(cs_);
-      store_->summary_async(2 + gk_);
-      WH_HIP_CHECK_HOST(hipEventRecord(gev_[gk_], cs_.stream()));
-    }
-    gpend_ = true;
-    gsince_ = 0;
-    if (sync) guard_read();
+    c10::hip::HIPStreamGuard sg(cs_);
+    guard_.after();
   }
 
   static constexpr int kMaxTau = 8;
@@ -1256,7 +1214,6 @@ class PsxStep {
   int64_t seed_, loss_;
   Tensor met_, auc_sum_;
   int64_t tau_;
-  double max_load_;
   int vs_ = 0;
   PsxTx tx_ = kTxIdentity;
   c10::intrusive_ptr<c10d::ProcessGroup> pg_;  // kTxStaged
@@ -1304,10 +1261,7 @@ class PsxStep {
   // a host read less on 3 of 4 steps)
   const int gevery_ = linear_ ? 4 : 1;
   int gskip_ = 0;
-  hipEvent_t gev_[2] = {};
-  int gk_ = 0;
-  bool gpend_ = false;
-  int64_t gkeys_ = 0, gvused_ = 0, gsince_ = 0, grecent_[2] = {0, 0}, grows_ = 0, vgrows_ = 0;
+  StoreGuard guard_;
 };
 
 Tensor c10d_a2a_rows(py::object pg, const Tensor& x, const std::vector<int64_t>& send_rows,

@@ -6,7 +6,8 @@
 // CRB row-block format, the text parsers, InputSplit part alignment (text
 // and RecordIO), the multi-threaded ordered ThreadedReader / MinibatchIter,
 // the conf parser, the WorkloadPool under concurrent workers and the
-// control-plane transport (Van) with live reader threads.
+// control-plane transport (Van) with live reader threads; and the pure
+// arithmetic of the exact AUC and of the store guard's growth plan.
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include "host/io.h"
 #include "host/json.h"
 #include "host/parsers.h"
+#include "host/store_guard_plan.h"
 #include "host/van.h"
 #include "host/workload_pool.h"
 
@@ -300,8 +302,40 @@ static void test_auc() {
   }
 }
 
+// the store guard's plan as the native guard drives it: four opens from a
+// table of 1024 slots and a V slab of 64 rows at max_load 0.7 (expected
+// values from kv/__init__.py StoreGuard.before_open on a stub store)
+static void test_store_guard_plan() {
+  wh::StoreGuardPlan p;
+  int64_t cap = 1024, vcap = 64;
+  auto open = [&](int64_t n) {
+    cap = wh::grown_cap(p.need(n), cap, 0.7);
+    if (p.vneed(n) > vcap) vcap = wh::grown_vcap(p.vneed(n), vcap);
+    p.opened(n);
+  };
+  auto is = [&](int64_t c, int64_t v, int64_t since, int64_t r0, int64_t r1) {
+    return cap == c && vcap == v && p.since == since && p.recent[0] == r0 && p.recent[1] == r1;
+  };
+  open(600);
+  EXPECT(is(1024, 1024, 600, 0, 600));
+  open(300);
+  EXPECT(is(2048, 2048, 900, 600, 300));
+  p.summarised(850, 700);
+  EXPECT(p.keys == 850 && p.vused == 700 && p.since == 0);
+  open(10);
+  EXPECT(is(2048, 2048, 10, 300, 10));
+  EXPECT(p.vneed(1000) == 2020);  // at most 2048: the slab must not grow
+  open(1000);
+  EXPECT(is(4096, 2048, 1010, 10, 1000));
+  // the load bound is compared in floating point: 716 < 0.7 * 1024 = 716.8
+  EXPECT(wh::grown_cap(716, 1024, 0.7) == 1024);
+  EXPECT(wh::grown_cap(717, 1024, 0.7) == 2048);
+  EXPECT(wh::grown_vcap(1, 0) == 1 && wh::grown_vcap(64, 64) == 64 && wh::grown_vcap(65, 64) == 128);
+}
+
 int main() {
   test_auc();
+  test_store_guard_plan();
   test_lz4();
   test_crb();
   test_parsers();
