@@ -4,6 +4,10 @@
 the ranks (row split, histogram allreduce per level over RCCL).
 
     python benchmarks/bench_gbdt.py [--rows 11000000] [--trees 500] [--depth 8]
+
+--num-class K: multi:softprob on K quantile classes of the same synthetic
+score (K trees per round; reports rounds/s and trees/s, and the softmax
+gradient kernel alone against its plain-torch form and the 12 K n byte floor).
 """
 import argparse
 import json
@@ -21,14 +25,37 @@ from wormhole_amd.parallel.comm import env_local_rank  # noqa: E402
 from wormhole_amd.parallel import launch  # noqa: E402
 
 
-def higgs_like(n, f, seed, dev):
+def higgs_like(n, f, seed, dev, num_class=0):
     g = torch.Generator(device=dev).manual_seed(seed)
     X = torch.randn(n, f, device=dev, generator=g)
     X[:, :7] = X[:, :7].abs()  # kinematic-like positive features
     w = torch.randn(f, device=dev, generator=g)
     logit = (X * w).sum(1) * 0.3 + torch.sin(X[:, 0] * X[:, 1]) + 0.5 * (X[:, 2] > 1).float()
     y = (torch.rand(n, device=dev, generator=g) < torch.sigmoid(logit)).float()
+    if num_class > 1:  # K equal-mass classes of the score
+        srt = logit.sort().values
+        edges = srt[[(n * k) // num_class for k in range(1, num_class)]]
+        y = torch.bucketize(logit, edges).float()
     return X, y
+
+
+def time_gpair(obj, margin, label, dev, reps=10):
+    """ms per call of the fused softmax gradient kernel and of its plain-torch
+    form on the same device tensors (events around `reps` calls, after one
+    warm-up call each)."""
+    out = []
+    for fn in (lambda: obj.gpair(margin, label, None),
+               lambda: G.softmax_gpair_torch(margin, label, None)):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / reps)
+    return out
 
 
 def main():
@@ -39,6 +66,8 @@ def main():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--max-bin", type=int, default=256)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--num-class", type=int, default=0,
+                    help="K > 1: multi:softprob, K trees per round (--trees counts trees)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the framework's PyTorch CPU path (anchor numbers)")
     ap.add_argument("--gpus", type=int, default=1,
@@ -58,10 +87,12 @@ def main():
     bsp = BSP(dev)
     launch.verify_world(bsp.comm, a.gpus if launch.launched() else 1)
     n = a.rows // bsp.world
-    X, y = higgs_like(n, a.features, 7 + bsp.rank, dev)
+    K = a.num_class if a.num_class > 1 else 1
+    X, y = higgs_like(n, a.features, 7 + bsp.rank, dev, a.num_class)
     dm = G.DMatrix.from_dense(X, y, dev)
     p = G.GBDTParam()
-    p.objective = "binary:logistic"
+    p.objective = "binary:logistic" if K == 1 else "multi:softprob"
+    p.num_class = a.num_class if K > 1 else 0
     p.max_depth = a.depth
     p.eta = 0.1
     p.max_bin = a.max_bin
@@ -71,20 +102,21 @@ def main():
     B = cuts.bin(dm)
     sync()
     t_prep = time.perf_counter() - t_prep
-    obj = G.Objective(p.objective)
+    obj = G.Objective(p.objective, p.num_class)
     tb = G.TreeBuilder(p, bsp, dm, cuts, B)
-    margin = torch.zeros(n, device=dev)
+    margin = torch.zeros(n, device=dev) if K == 1 else torch.zeros(K, n, device=dev)
+    rounds = max(1, a.trees // K)
     for _ in range(a.warmup):
-        t = tb.build(obj.gpair(margin, dm.label, None), margin)
-        if hasattr(t, "materialize"):
-            t.materialize()
+        for t in G.boost_round(obj, tb, dm, margin):
+            if hasattr(t, "materialize"):
+                t.materialize()
     sync()
     bsp.barrier()
     b0 = tb.hist_bytes()
     t0 = time.perf_counter()
     tree = None
-    for _ in range(a.trees):
-        tree = tb.build(obj.gpair(margin, dm.label, None), margin)
+    for _ in range(rounds):
+        tree = G.boost_round(obj, tb, dm, margin)[-1]
     # a device-grown tree's host lists are built one tree later: the last
     # one's inside the timed region too
     if tree is not None and hasattr(tree, "materialize"):
@@ -95,13 +127,22 @@ def main():
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     bsp.allreduce(t, "max")
     dt = float(t.item())
-    hb = bsp.allreduce_scalar((tb.hist_bytes() - b0) / max(a.trees, 1), "max")
-    err = G.eval_metric("error", torch.sigmoid(margin), dm.label, None, bsp)
+    ntree = rounds * K
+    hb = bsp.allreduce_scalar((tb.hist_bytes() - b0) / max(ntree, 1), "max")
+    err = obj.metrics([obj.default_metric()], margin, dm.label, None, bsp)[0]
+    extra = {}
+    if K > 1:
+        extra = {"num_class": K, "rounds": rounds, "rounds_per_s": rounds / dt}
+        if dev.type == "cuda":
+            ms_k, ms_t = time_gpair(obj, margin, dm.label, dev)
+            extra.update({"gpair_softmax_ms": ms_k, "gpair_torch_ms": ms_t,
+                          "gpair_bytes_floor": 12 * K * n,
+                          "gpair_softmax_GBps": 12e-6 * K * n / ms_k})
     if bsp.rank == 0:
         print(json.dumps({"metric": "GBDT trees/s (hist, depth %d, %dx%d)" % (a.depth, a.rows, a.features),
-                          "value": a.trees / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
-                          "ms_per_tree": 1000 * dt / a.trees,
-                          "trees": a.trees, "sketch_bin_s": t_prep,
+                          "value": ntree / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
+                          "ms_per_tree": 1000 * dt / ntree,
+                          "trees": ntree, **extra, "sketch_bin_s": t_prep,
                           "hist_exchange": ("feature-reduce-scatter" if tb.xchg is not None
                                             else "allreduce") if bsp.world > 1 else None,
                           "hist_bytes_per_rank_per_tree": hb,

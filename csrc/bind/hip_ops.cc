@@ -2185,6 +2185,75 @@ std::vector<Tensor> gbdt_gpair(const Tensor& margin, const Tensor& label,
   return {gp, st};
 }
 
+// ---- multi-class softmax: margin f32 [K, n] class-major, label f32 [n]
+namespace {
+// per device, grown with K; the ticket words at its head stay zeroed
+double* softmax_scratch(const Tensor& like, int64_t K) {
+  static std::vector<Tensor> scratch(64);
+  Tensor& t = scratch[like.device().index()];
+  const int64_t need = wh::gbdt_softmax_scratch((int)K);
+  if (!t.defined() || t.numel() < need)
+    t = torch::zeros({need}, like.options().dtype(torch::kFloat64));
+  return ptr<double>(t);
+}
+
+const float* softmax_args(const char* op, const Tensor& margin, const Tensor* label,
+                          const c10::optional<Tensor>& weight, int64_t* K, int64_t* n) {
+  CHECK_IN(margin, torch::kFloat32);
+  TORCH_CHECK(margin.dim() == 2 && margin.size(0) >= 1 && margin.size(0) < (1 << 23), op,
+              ": margin must be [num_class, n]");
+  *K = margin.size(0);
+  *n = margin.size(1);
+  if (label) {
+    CHECK_IN((*label), torch::kFloat32);
+    TORCH_CHECK(label->numel() == *n, op, ": label size mismatch");
+  }
+  if (weight.has_value() && weight->defined()) {
+    CHECK_IN((*weight), torch::kFloat32);
+    TORCH_CHECK(weight->numel() == *n, op, ": weight size mismatch");
+    return ptr<float>(*weight);
+  }
+  return nullptr;
+}
+}  // namespace
+
+// (gpair f32 [K, n, 2], stats f64 [K, 4] = per class {sum g, sum h, max|g|, max|h|})
+std::vector<Tensor> gbdt_gpair_softmax(const Tensor& margin, const Tensor& label,
+                                       const c10::optional<Tensor>& weight) {
+  int64_t K, n;
+  const float* wp = softmax_args("gbdt_gpair_softmax", margin, &label, weight, &K, &n);
+  c10::DeviceGuard g(margin.device());
+  auto gp = torch::empty({K, n, 2}, margin.options());
+  auto st = torch::zeros({K, 4}, margin.options().dtype(torch::kFloat64));
+  if (n > 0)
+    wh::gbdt_gpair_softmax(n, (int)K, ptr<float>(margin), ptr<float>(label), wp, ptr<float>(gp),
+                           softmax_scratch(margin, K), ptr<double>(st), cur_stream(margin));
+  return {gp, st};
+}
+
+// prob: probabilities f32 [n, K]; else arg-max class ids f32 [n]
+Tensor gbdt_softmax_out(const Tensor& margin, bool prob) {
+  int64_t K, n;
+  softmax_args("gbdt_softmax_out", margin, nullptr, c10::nullopt, &K, &n);
+  c10::DeviceGuard g(margin.device());
+  auto out = prob ? torch::empty({n, K}, margin.options()) : torch::empty({n}, margin.options());
+  wh::gbdt_softmax_out(n, (int)K, ptr<float>(margin), prob, ptr<float>(out), cur_stream(margin));
+  return out;
+}
+
+// f64 [3] = {sum w [arg-max != y], sum w (-log max(p_y, 1e-16)), sum w}
+Tensor gbdt_multi_eval(const Tensor& margin, const Tensor& label,
+                       const c10::optional<Tensor>& weight) {
+  int64_t K, n;
+  const float* wp = softmax_args("gbdt_multi_eval", margin, &label, weight, &K, &n);
+  c10::DeviceGuard g(margin.device());
+  auto out = torch::zeros({3}, margin.options().dtype(torch::kFloat64));
+  if (n > 0)
+    wh::gbdt_multi_eval(n, (int)K, ptr<float>(margin), ptr<float>(label), wp,
+                        softmax_scratch(margin, 1), ptr<double>(out), cur_stream(margin));
+  return out;
+}
+
 // {2^eg, 2^eh[, R]} (f32) from m = {max|g|, max|h|} (f32 [2], on the device)
 Tensor gbdt_qscale(const Tensor& m, double nglobal, int64_t R) {
   CHECK_IN(m, torch::kFloat32);
@@ -3560,6 +3629,9 @@ PYBIND11_MODULE(_hip, m) {
   m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
         py::arg("lds") = true);
   m.def("gbdt_gpair", &gbdt_gpair);
+  m.def("gbdt_gpair_softmax", &gbdt_gpair_softmax);
+  m.def("gbdt_softmax_out", &gbdt_softmax_out);
+  m.def("gbdt_multi_eval", &gbdt_multi_eval);
   m.def("gbdt_qscale", &gbdt_qscale);
   // the ingest ops block on one small device read each: the GIL is released
   // so a producer thread's parsing overlaps the training loop

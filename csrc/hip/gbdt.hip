@@ -904,6 +904,317 @@ void gbdt_gpair(int64_t n, const float* margin, const float* label, const float*
                      logistic ? 1 : 0, reinterpret_cast<float2*>(gpair), scratch, ticket, stats);
 }
 
+namespace {
+// ---- multi-class (multi:softmax / multi:softprob): K margins per row, class-
+// major (margin [K, n], gpair [K, n, 2]) so that margin[k] / gpair[k] are the
+// contiguous per-tree tensors of the single-output grower. A lane owns a row
+// and reads margin[k * n + i] coalesced for every k.
+constexpr int kSmThreads = 256, kSmWaves = kSmThreads / 64, kSmBlocks = 1024;
+constexpr int kSmRegK = 8;    // register path: K <= 8 (and a 4-class build for K <= 4)
+constexpr int kSmLdsK = 256;  // classes per pass of the any-K path (LDS: 128 bytes per class)
+constexpr double kNllMax = 36.841361487904734;  // -log(1e-16)
+
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Running max and sum of exp(m - max) over a row's K margins, one read each
+// (the sum in fp64: its rescales must not cost the emitted p a digit), and
+// the first arg-max.
+struct RowSoftmax {
+  float mx;
+  double s;
+  int arg;
+};
+__device__ __forceinline__ RowSoftmax row_softmax(const float* __restrict__ margin, int64_t n,
+                                                  int64_t i, int K) {
+  RowSoftmax r{margin[i], 1.0, 0};
+  // branch-free, so that the unrolled loads go out together: a new maximum
+  // rescales the sum by e and adds 1, anything else adds e
+#pragma unroll 8
+  for (int k = 1; k < K; ++k) {
+    const float m = margin[(int64_t)k * n + i];
+    const bool up = m > r.mx;
+    const double e = (double)expf(-fabsf(m - r.mx));
+    r.s = up ? r.s * e + 1.0 : r.s + e;
+    r.mx = up ? m : r.mx;
+    r.arg = up ? k : r.arg;
+  }
+  return r;
+}
+
+// class k's pair of a row: g = w (p - [y = k]), h = w max(2 p (1 - p), 1e-16)
+__device__ __forceinline__ float2 softmax_pair(float p, bool hit, float w) {
+  return make_float2((p - (hit ? 1.f : 0.f)) * w, fmaxf(2.f * p * (1.f - p), 1e-16f) * w);
+}
+
+// Softmax gradient pairs of one boosting round (all K trees) in one launch,
+// with every class's root statistics: stats[k] = {sum g, sum h (fp64),
+// max |g|, max |h|} of gpair[k], the four values k_gpair gives one output.
+// Per wave and class the sums live in LDS (acc [waves][kc][4], each wave its
+// own slice, so no atomics and one order); a block adds its waves in wave
+// order and stores the class partials (part [K][blocks][4]); the block that
+// arrives last reduces each class over the blocks in a fixed tree. KR > 0:
+// K <= KR, a row's margins stay in registers (read once) and the class sums
+// too, reduced over the wave once at the end. KR == 0: any K, two reads of
+// the row (running max + sum, then emit; the second hits L2) in passes of
+// <= kSmLdsK classes; a pass past the first repeats the max + sum reads.
+template <int KR>
+__global__ __launch_bounds__(kSmThreads) void k_gpair_softmax(
+    int64_t n, int K, const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, float2* __restrict__ out, double* __restrict__ part,
+    unsigned int* ticket, double* stats) {
+  extern __shared__ __attribute__((aligned(16))) double acc[];
+  __shared__ int last;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int KC = KR > 0 ? K : (K < kSmLdsK ? K : kSmLdsK);
+  double* wacc = acc + (size_t)wid * KC * 4;
+  const int64_t stride = (int64_t)gridDim.x * kSmThreads;
+  for (int c0 = 0; c0 < K; c0 += KC) {
+    const int kc = K - c0 < KC ? K - c0 : KC;
+    if constexpr (KR > 0) {
+      double sg[KR], sh[KR];
+      float mg[KR], mh[KR];
+#pragma unroll
+      for (int k = 0; k < KR; ++k) sg[k] = sh[k] = 0.0, mg[k] = mh[k] = 0.f;
+      for (int64_t i = (int64_t)blockIdx.x * kSmThreads + threadIdx.x; i < n; i += stride) {
+        // no branch around a load (a guarded load waits for the one before
+        // it): classes past K re-read class 0 and count as -inf, exp = 0
+        float m[KR];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const float v = margin[(int64_t)(k < K ? k : 0) * n + i];
+          m[k] = k < K ? v : -INFINITY;
+          mx = fmaxf(mx, m[k]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          m[k] = expf(m[k] - mx);
+          s += m[k];
+        }
+        const float y = label[i], w = weight ? weight[i] : 1.f;
+        const float inv = 1.f / s;  // (one division per row)
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+          const float2 gh = softmax_pair(m[k] * inv, y == (float)k, w);
+          if (k < K) out[(int64_t)k * n + i] = gh;
+          sg[k] += gh.x;
+          sh[k] += gh.y;
+          mg[k] = fmaxf(mg[k], fabsf(gh.x));
+          mh[k] = fmaxf(mh[k], fabsf(gh.y));
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < KR; ++k)
+        if (k < K) {
+          const double a = wave_sum_d(sg[k]), b = wave_sum_d(sh[k]);
+          const double c = wave_max_d((double)mg[k]), d = wave_max_d((double)mh[k]);
+          if (lane == 0) {
+            wacc[k * 4 + 0] = a; wacc[k * 4 + 1] = b; wacc[k * 4 + 2] = c; wacc[k * 4 + 3] = d;
+          }
+        }
+    } else {
+      for (int q = lane; q < kc * 4; q += 64) wacc[q] = 0.0;  // (read back by this wave only)
+      for (int64_t base = (int64_t)blockIdx.x * kSmThreads; base < n; base += stride) {
+        const int64_t i = base + threadIdx.x;
+        const bool act = i < n;
+        const int64_t ii = act ? i : n - 1;  // idle lanes read a valid row and add zeros
+        const RowSoftmax r = row_softmax(margin, n, ii, K);
+        const float inv = (float)(1.0 / r.s);
+        const float y = label[ii], w = weight ? weight[ii] : 1.f;
+        float mk = margin[(int64_t)c0 * n + ii];
+        for (int k = c0; k < c0 + kc; ++k) {
+          const float p = expf(mk - r.mx) * inv;
+          // the next class's margin is on its way during this one's reductions
+          mk = margin[(int64_t)(k + 1 < c0 + kc ? k + 1 : k) * n + ii];
+          float2 gh = softmax_pair(p, y == (float)k, w);
+          if (act) out[(int64_t)k * n + i] = gh;
+          else gh = make_float2(0.f, 0.f);
+          const double a = wave_sum_d((double)gh.x), b = wave_sum_d((double)gh.y);
+          const double c = wave_max_d((double)fabsf(gh.x)), d = wave_max_d((double)fabsf(gh.y));
+          if (lane == 0) {
+            double* t = wacc + (k - c0) * 4;
+            t[0] += a; t[1] += b; t[2] = fmax(t[2], c); t[3] = fmax(t[3], d);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kc; k += kSmThreads) {
+      double v[4] = {0, 0, 0, 0};
+      for (int w = 0; w < kSmWaves; ++w) {
+        const double* t = acc + ((size_t)w * KC + k) * 4;
+        v[0] += t[0]; v[1] += t[1]; v[2] = fmax(v[2], t[2]); v[3] = fmax(v[3], t[3]);
+      }
+      unsigned long long* pp = reinterpret_cast<unsigned long long*>(part) +
+                               ((size_t)(c0 + k) * gridDim.x + blockIdx.x) * 4;
+      for (int q = 0; q < 4; ++q) lb_store(pp + q, (unsigned long long)__double_as_longlong(v[q]));
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) last = arrive_last(ticket, blockIdx.x, gridDim.x);
+  __syncthreads();
+  if (!last) return;
+  // the last block: wave w reduces classes w, w + waves, ...; lane l takes
+  // blocks l, l + 64, ..., then the fixed wave tree -- the same sums every run
+  const unsigned long long* pp = reinterpret_cast<const unsigned long long*>(part);
+  for (int k = wid; k < K; k += kSmWaves) {
+    double v[4] = {0, 0, 0, 0};
+    for (unsigned b = lane; b < gridDim.x; b += 64) {
+      const unsigned long long* t = pp + ((size_t)k * gridDim.x + b) * 4;
+      v[0] += __longlong_as_double((long long)lb_load(t));
+      v[1] += __longlong_as_double((long long)lb_load(t + 1));
+      v[2] = fmax(v[2], __longlong_as_double((long long)lb_load(t + 2)));
+      v[3] = fmax(v[3], __longlong_as_double((long long)lb_load(t + 3)));
+    }
+    v[0] = wave_sum_d(v[0]);
+    v[1] = wave_sum_d(v[1]);
+    v[2] = wave_max_d(v[2]);
+    v[3] = wave_max_d(v[3]);
+    if (lane == 0)
+      for (int q = 0; q < 4; ++q) stats[k * 4 + q] = v[q];
+  }
+}
+
+// Predictions from K margins per row: prob == 0 -> out [n] the arg-max class
+// id (lowest on a tie); else out [n, K] row-major probabilities. A lane owns
+// a row for the max + sum pass; the probabilities of a block's 256 rows are
+// then written in output order (coalesced stores; the margin re-reads hit L2).
+__global__ __launch_bounds__(kSmThreads) void k_softmax_out(int64_t n, int K,
+                                                            const float* __restrict__ margin,
+                                                            int prob, float* __restrict__ out) {
+  __shared__ float smx[kSmThreads], sinv[kSmThreads];
+  for (int64_t base = (int64_t)blockIdx.x * kSmThreads; base < n;
+       base += (int64_t)gridDim.x * kSmThreads) {
+    const int64_t i = base + threadIdx.x;
+    if (i < n) {
+      const RowSoftmax r = row_softmax(margin, n, i, K);
+      if (!prob) out[i] = (float)r.arg;
+      smx[threadIdx.x] = r.mx;  // (read in prob mode only)
+      sinv[threadIdx.x] = (float)(1.0 / r.s);
+    }
+    if (!prob) continue;
+    __syncthreads();
+    const int64_t rows = n - base < kSmThreads ? n - base : kSmThreads;
+    const uint32_t total = (uint32_t)rows * (uint32_t)K;  // (K < 2^23: the binding)
+    for (uint32_t e = threadIdx.x; e < total; e += kSmThreads) {
+      const uint32_t r = e / (uint32_t)K, k = e - r * (uint32_t)K;
+      out[base * K + e] = expf(margin[(int64_t)k * n + base + r] - smx[r]) * sinv[r];
+    }
+    __syncthreads();
+  }
+}
+
+// {sum w [arg-max != y], sum w (-log max(p_y, 1e-16)), sum w} in fp64, by
+// per-block partials + arrival ticket like k_gpair. A label outside [0, K)
+// (or no integer) is never used as an index: it counts as an error with
+// nll = -log(1e-16).
+__global__ __launch_bounds__(kSmThreads) void k_multi_eval(
+    int64_t n, int K, const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, double* __restrict__ part, unsigned int* ticket,
+    double* out) {
+  __shared__ double sh[3][kSmWaves];
+  __shared__ int last;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  double v[3] = {0, 0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * kSmThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kSmThreads) {
+    const RowSoftmax r = row_softmax(margin, n, i, K);
+    const float y = label[i];
+    const double w = weight ? (double)weight[i] : 1.0;
+    int yi = -1;
+    if (y >= 0.f && y < (float)K && (float)(int)y == y) yi = (int)y;
+    double nll = kNllMax, err = 1.0;
+    if (yi >= 0) {
+      const float d = margin[(int64_t)yi * n + i] - r.mx;
+      nll = fmin(log(r.s) - (double)d, kNllMax);
+      err = r.arg != yi ? 1.0 : 0.0;
+    }
+    v[0] += w * err;
+    v[1] += w * nll;
+    v[2] += w;
+  }
+  for (int q = 0; q < 3; ++q) {
+    v[q] = wave_sum_d(v[q]);
+    if (lane == 0) sh[q][wid] = v[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 3; ++q) {
+      double t = 0;
+      for (int w = 0; w < kSmWaves; ++w) t += sh[q][w];
+      lb_store(reinterpret_cast<unsigned long long*>(part) + blockIdx.x * 4 + q,
+               (unsigned long long)__double_as_longlong(t));
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = arrive_last(ticket, blockIdx.x, gridDim.x);
+  }
+  __syncthreads();
+  if (!last) return;
+  const unsigned long long* pp = reinterpret_cast<const unsigned long long*>(part);
+  for (int q = 0; q < 3; ++q) {
+    double t = 0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += kSmThreads)
+      t += __longlong_as_double((long long)lb_load(pp + b * 4 + q));
+    t = wave_sum_d(t);
+    __syncthreads();
+    if (lane == 0) sh[q][wid] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int q = 0; q < 3; ++q) {
+    double t = 0;
+    for (int w = 0; w < kSmWaves; ++w) t += sh[q][w];
+    out[q] = t;
+  }
+}
+}  // namespace
+
+// scratch (doubles): the (zeroed) arrival ticket words first, then the block partials
+constexpr int64_t kSmTicketD = (kArriveWords + 1) / 2 + 4 - ((kArriveWords + 1) / 2) % 4;
+
+int64_t gbdt_softmax_scratch(int K) { return kSmTicketD + 4 * (int64_t)kSmBlocks * K; }
+
+void gbdt_gpair_softmax(int64_t n, int K, const float* margin, const float* label,
+                        const float* weight, float* gpair, double* scratch, double* stats,
+                        hipStream_t s) {
+  if (n <= 0 || K <= 0) return;
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch);
+  double* part = scratch + kSmTicketD;
+  const int nb = grid_for(n, kSmThreads, kSmBlocks);
+  float2* out = reinterpret_cast<float2*>(gpair);
+  if (K <= kSmRegK) {
+    const auto kern = K <= kSmRegK / 2 ? k_gpair_softmax<kSmRegK / 2> : k_gpair_softmax<kSmRegK>;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(kSmThreads), (size_t)kSmWaves * K * 4 * sizeof(double),
+                       s, n, K, margin, label, weight, out, part, ticket, stats);
+  } else {
+    const int kc = std::min(K, kSmLdsK);
+    hipLaunchKernelGGL(k_gpair_softmax<0>, dim3(nb), dim3(kSmThreads),
+                       (size_t)kSmWaves * kc * 4 * sizeof(double), s, n, K, margin, label, weight,
+                       out, part, ticket, stats);
+  }
+}
+
+void gbdt_softmax_out(int64_t n, int K, const float* margin, bool prob, float* out,
+                      hipStream_t s) {
+  if (n <= 0 || K <= 0) return;
+  hipLaunchKernelGGL(k_softmax_out, dim3(grid_for(n, kSmThreads, 8 * kSmBlocks)),
+                     dim3(kSmThreads), 0, s, n, K, margin, prob ? 1 : 0, out);
+}
+
+void gbdt_multi_eval(int64_t n, int K, const float* margin, const float* label,
+                     const float* weight, double* scratch, double* out, hipStream_t s) {
+  if (n <= 0 || K <= 0) return;
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch);
+  hipLaunchKernelGGL(k_multi_eval, dim3(grid_for(n, kSmThreads, kSmBlocks)), dim3(kSmThreads), 0,
+                     s, n, K, margin, label, weight, scratch + kSmTicketD, ticket, out);
+}
+
 void gbdt_leaf_walk(const uint8_t* B, int64_t n, int f, int nn, const int32_t* feat, const int32_t* bin,
                     const uint8_t* defl, const int32_t* left, const int32_t* right,
                     const float* val, float* margin, hipStream_t s, bool lds) {

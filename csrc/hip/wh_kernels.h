@@ -591,6 +591,19 @@ void gbdt_qscale(const float* m, double nglobal, int R, float* out, hipStream_t 
 int64_t gbdt_gpair_scratch();
 void gbdt_gpair(int64_t n, const float* margin, const float* label, const float* weight,
                 bool logistic, float* gpair, double* scratch, double* stats, hipStream_t s);
+// multi-class softmax, class-major margin [K, n] / gpair [K, n, 2]: the pairs
+// of all K trees of a round + stats [K, 4] (per class as gbdt_gpair's) in one
+// launch; predictions (arg-max ids [n], or probabilities [n, K]); evaluation
+// sums out [3] = {sum w err, sum w nll, sum w}. scratch: gbdt_softmax_scratch(K)
+// doubles, zeroed once (the ticket words stay zeroed). Nothing runs for n <= 0.
+int64_t gbdt_softmax_scratch(int K);
+void gbdt_gpair_softmax(int64_t n, int K, const float* margin, const float* label,
+                        const float* weight, float* gpair, double* scratch, double* stats,
+                        hipStream_t s);
+void gbdt_softmax_out(int64_t n, int K, const float* margin, bool prob, float* out,
+                      hipStream_t s);
+void gbdt_multi_eval(int64_t n, int K, const float* margin, const float* label,
+                     const float* weight, double* scratch, double* out, hipStream_t s);
 void gbdt_leaf_walk(const uint8_t* B, int64_t n, int f, int nn, const int32_t* feat, const int32_t* bin,
                     const uint8_t* defl, const int32_t* left, const int32_t* right,
                     const float* val, float* margin, hipStream_t s, bool lds = true);

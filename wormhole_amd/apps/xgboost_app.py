@@ -2,7 +2,12 @@
 xgboost CLI surface the reference drives (learn/xgboost/mushroom.hadoop.conf,
 learn/xgboost/run_yarn.sh; SURVEY §2.2 "xgboost"):
 
-tasks ``train | pred | dump | eval``; parameters booster, objective, eta,
+tasks ``train | pred | dump | eval``; parameters booster, objective
+(binary:logistic, binary:logitraw, reg:logistic, reg:linear,
+reg:squarederror, multi:softmax, multi:softprob), num_class (the multi:
+objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
+belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
+ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
 gamma, min_child_weight, max_depth, lambda, alpha, base_score, max_bin,
 subsample, colsample_bytree, seed, eval_metric, num_round, save_period,
 eval_train, eval[name]=path, data, test:data, model_in, model_out, model_dir,
@@ -152,14 +157,19 @@ def main(argv):
         path = test_data or data
         raw = load(path)
         dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse)
-        pred = b.obj.pred(b.predict_margin(dm))
+        margin = b.predict_margin(dm)
         if task == "eval":
             metrics = param.eval_metric or [b.obj.default_metric()]
-            s = "".join("\ttest-%s:%f" % (m, G.eval_metric(m, pred, dm.label, dm.weight, bsp))
-                        for m in metrics)
+            b.obj.check_metrics(metrics)
+            b.obj.check_labels(dm.label, bsp)
+            vals = b.obj.metrics(metrics, margin, dm.label, dm.weight, bsp)
+            s = "".join("\ttest-%s:%f" % (m, v) for m, v in zip(metrics, vals))
             bsp.tracker_print(s.lstrip("\t"))
         else:
-            parts = bsp.comm.allgather_object(pred.float().cpu().tolist())
+            # one value per line: n class ids (multi:softmax), n x K row-major
+            # probabilities (multi:softprob), else n predictions
+            pred = b.obj.pred(margin)
+            parts = bsp.comm.allgather_object(pred.float().cpu().reshape(-1).tolist())
             if bsp.rank == 0:
                 with open_uri(name_pred, "w") as f:
                     for part in parts:
@@ -180,40 +190,44 @@ def main(argv):
     deval = [(name, G.make_dmatrix(*r, ncol=ncol, device=dev, sparse=dsparse))
              for name, r in eval_raw]
     booster = G.Booster.load(model_in, param) if model_in else G.Booster(param, ncol)
-    start = len(booster.trees)
     version, gstate, _ = bsp.load_checkpoint()
     if version > 0:
         booster = _booster_from_state(G, gstate, param)
-        start = len(booster.trees)
+    obj = booster.obj
+    K = obj.n_group  # trees per round: tree t of the flat list belongs to class t % K
+    start = len(booster.trees) // K
+    if version > 0:
         print("restart from version=%d (round %d)" % (version, start), flush=True)
+    metrics = param.eval_metric or [obj.default_metric()]
+    obj.check_metrics(metrics)
+    for d in [dtrain] + [d for _, d in deval]:
+        obj.check_labels(d.label, bsp)
     margin = booster.predict_margin(dtrain)
-    # hessian-weighted sketch: weights at the starting margin
-    hess = booster.obj.gpair(margin, dtrain.label, None)[:, 1] if dtrain.n else None
+    # hessian-weighted sketch: weights at the starting margin (multi-class:
+    # the row's hessians summed over the classes)
+    hess = None
+    if dtrain.n:
+        hess = obj.gpair(margin, dtrain.label, None)[..., 1]
+        hess = hess.sum(0) if K > 1 else hess
     cuts = G.Cuts.build(dtrain, param.max_bin, bsp, hess=hess)
     B = cuts.bin(dtrain)
     builder = G.make_builder(param, bsp, dtrain, cuts, B)
     emargins = [booster.predict_margin(d) for _, d in deval]
-    metrics = param.eval_metric or [booster.obj.default_metric()]
     gen = torch.Generator().manual_seed(param.seed + 17 * bsp.rank)
     fgen = torch.Generator().manual_seed(param.seed)
     for r in range(start, num_round):
-        gp = booster.obj.gpair(margin, dtrain.label, dtrain.weight)
-        if param.subsample < 1.0:
-            keep = (torch.rand(dtrain.n, generator=gen) < param.subsample).to(dev)
-            gp = gp * keep[:, None].float()
-        builder.sample_features(fgen)
-        tree = builder.build(gp, margin)
-        booster.trees.append(tree)
+        new = G.boost_round(obj, builder, dtrain, margin, gen, fgen)  # K trees
+        booster.trees += new
         msg = "[%d]" % r
         for (name, d), em in zip(deval, emargins):
-            d.predict_tree(tree, em)
-            p = booster.obj.pred(em)
-            for m in metrics:
-                msg += "\t%s-%s:%f" % (name, m, G.eval_metric(m, p, d.label, d.weight, bsp))
+            for k, tree in enumerate(new):
+                d.predict_tree(tree, em[k] if K > 1 else em)
+            for m, v in zip(metrics, obj.metrics(metrics, em, d.label, d.weight, bsp)):
+                msg += "\t%s-%s:%f" % (name, m, v)
         if eval_train:
-            p = booster.obj.pred(margin)
-            for m in metrics:
-                msg += "\ttrain-%s:%f" % (m, G.eval_metric(m, p, dtrain.label, dtrain.weight, bsp))
+            for m, v in zip(metrics, obj.metrics(metrics, margin, dtrain.label, dtrain.weight,
+                                                 bsp)):
+                msg += "\ttrain-%s:%f" % (m, v)
         bsp.tracker_print(msg)
         if save_period and (r + 1) % save_period == 0 and bsp.rank == 0:
             booster.save(os.path.join(model_dir, "%04d.model" % (r + 1)))
@@ -231,10 +245,11 @@ def _booster_state(b):
     for t in b.trees:
         trees.append({k: torch.tensor(getattr(t, k), dtype=torch.float64)
                       for k in ("feat", "cond", "left", "right", "defl", "leaf", "gain", "cover")})
-    return {"num_feature": b.num_feature, "trees": trees}
+    return {"num_feature": b.num_feature, "num_class": b.param.num_class, "trees": trees}
 
 
 def _booster_from_state(G, s, param):
+    param.num_class = int(s.get("num_class", param.num_class))
     b = G.Booster(param, int(s["num_feature"]))
     for d in s["trees"]:
         t = G.RegTree()

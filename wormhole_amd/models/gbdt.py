@@ -59,6 +59,7 @@ class GBDTParam:
         self.subsample = 1.0
         self.colsample_bytree = 1.0
         self.seed = 0
+        self.num_class = 0  # multi:softmax / multi:softprob: classes (trees per round)
         self.eval_metric = []
         self.silent = 0
 
@@ -69,7 +70,7 @@ class GBDTParam:
         elif name in ("eta", "gamma", "min_child_weight", "alpha", "base_score", "subsample",
                       "colsample_bytree"):
             setattr(self, name, float(val))
-        elif name in ("max_depth", "max_bin", "seed", "silent"):
+        elif name in ("max_depth", "max_bin", "seed", "silent", "num_class"):
             setattr(self, name, int(val))
         elif name in ("objective", "booster"):
             setattr(self, name, val)
@@ -110,15 +111,55 @@ def _threshold_l1(G, alpha):
 
 
 # ---------------------------------------------------------------- objective
+MULTI_METRICS = ("merror", "mlogloss")
+SINGLE_METRICS = ("error", "logloss", "rmse", "auc")
+NLL_MAX = -math.log(1e-16)
+
+
 class Objective:
-    def __init__(self, name):
+    """Single-output objectives keep one margin per row; multi:softmax and
+    multi:softprob keep ``num_class`` margins per row, class-major
+    (margin [K, n], gpair [K, n, 2]), so ``margin[k]`` / ``gpair[k]`` are the
+    contiguous tensors a tree builder takes: one round grows K trees, tree t
+    of the flat list belongs to class t % K."""
+
+    def __init__(self, name, num_class=0):
         if name not in ("binary:logistic", "reg:logistic", "reg:linear", "reg:squarederror",
-                        "binary:logitraw"):
+                        "binary:logitraw", "multi:softmax", "multi:softprob"):
             raise ValueError("unknown objective " + name)
         self.name = name
         self.logistic = name in ("binary:logistic", "reg:logistic", "binary:logitraw")
+        self.multi = name.startswith("multi:")
+        if self.multi and int(num_class) < 2:
+            raise ValueError("objective %s needs num_class >= 2 (got %d)" % (name, num_class))
+        self.num_class = int(num_class) if self.multi else 0
+
+    @property
+    def n_group(self):
+        """Margins per row = trees per boosting round."""
+        return self.num_class if self.multi else 1
+
+    def check_labels(self, label, bsp):
+        """Multi-class labels must be integers in [0, num_class): decided on
+        every rank together (the flag is allreduced before anyone raises, so
+        no rank is left waiting in a collective)."""
+        if not self.multi:
+            return
+        bad = bool(((label < 0) | (label >= self.num_class) | (label != label.floor())).any()) \
+            if label.numel() else False
+        if bsp.allreduce_scalar(1.0 if bad else 0.0, "max") > 0:
+            raise ValueError("label must be in [0, num_class)")
+
+    def check_metrics(self, names):
+        for m in names:
+            if m not in MULTI_METRICS + SINGLE_METRICS:
+                raise ValueError("unknown eval_metric " + m)
+            if (m in MULTI_METRICS) != self.multi:
+                raise ValueError("eval_metric %s does not fit objective %s" % (m, self.name))
 
     def prob_to_margin(self, base):
+        if self.multi:
+            return base  # the same for every class: cancels in the softmax
         if self.logistic:
             if not 0.0 < base < 1.0:
                 raise ValueError("base_score must be in (0,1) for logistic loss")
@@ -126,6 +167,8 @@ class Objective:
         return base
 
     def gpair(self, margin, label, weight):
+        if self.multi:
+            return self._gpair_softmax(margin, label, weight)
         if margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32:
             # one launch; the root statistics ride along (gpair_stats)
             gp, st = _native.hip().gbdt_gpair(margin.contiguous(), label.contiguous(),
@@ -144,13 +187,109 @@ class Objective:
             g, h = g * weight, h * weight
         return torch.stack([g, h], 1).float().contiguous()
 
+    def _gpair_softmax(self, margin, label, weight):
+        """margin [K, n] -> gpair [K, n, 2]: p = softmax over the classes,
+        g = w (p_k - [y = k]), h = w max(2 p_k (1 - p_k), 1e-16). On the GPU
+        one launch, with every class's root statistics (:func:`class_gpair`);
+        the torch form below is its reference and the CPU path."""
+        K = self.num_class
+        if margin.dim() != 2 or margin.shape[0] != K:
+            raise ValueError("multi-class margins must be [num_class, n]")
+        if (margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32
+                and (weight is None or weight.dtype == torch.float32)):
+            gp, st = _native.hip().gbdt_gpair_softmax(
+                margin.contiguous(), label.contiguous(),
+                weight.contiguous() if weight is not None else None)
+            gp._wh_stats = st
+            return gp
+        return softmax_gpair_torch(margin, label, weight)
+
     def pred(self, margin):
+        if self.multi:
+            if margin.is_cuda and margin.dtype == torch.float32:
+                return _native.hip().gbdt_softmax_out(margin.contiguous(),
+                                                      self.name == "multi:softprob")
+            if self.name == "multi:softmax":
+                return first_argmax(margin).to(margin.dtype)
+            return torch.softmax(margin, 0).t().contiguous()
         if self.name in ("binary:logistic", "reg:logistic"):
             return torch.sigmoid(margin)
         return margin
 
     def default_metric(self):
+        if self.multi:
+            return "merror"
         return "error" if self.name == "binary:logistic" else "rmse"
+
+    def metrics(self, names, margin, label, weight, bsp):
+        """Globally reduced metrics of a set from its margins. Multi-class:
+        merror = sum w [arg-max != y] / sum w and mlogloss = sum w (-log
+        max(p_y, 1e-16)) / sum w from ONE reduction {sum w err, sum w nll,
+        sum w} (on the GPU one launch, ``gbdt_multi_eval``) and one allreduce
+        of the three doubles. A label outside [0, K) counts as an error with
+        nll = -log(1e-16)."""
+        self.check_metrics(names)
+        if not self.multi:
+            p = self.pred(margin)
+            return [eval_metric(m, p, label, weight, bsp) for m in names]
+        v = multi_eval_sums(margin, label, weight)
+        bsp.allreduce(v)
+        v = v.tolist()
+        den = v[2] if v[2] > 0 else 1.0
+        return [v[0] / den if m == "merror" else v[1] / den for m in names]
+
+
+def first_argmax(margin):
+    """Arg-max over the classes of margin [K, n]; on an exact tie the lowest
+    class wins."""
+    K = margin.shape[0]
+    ids = torch.arange(K, device=margin.device)[:, None]
+    mx = margin.max(0, keepdim=True).values
+    return torch.where(margin == mx, ids, torch.full_like(ids, K)).min(0).values
+
+
+def softmax_gpair_torch(margin, label, weight):
+    """The softmax gradient pairs [K, n, 2] of margin [K, n] in plain torch,
+    in the margins' precision: the reference of ``gbdt_gpair_softmax``."""
+    K = margin.shape[0]
+    p = torch.softmax(margin, 0)
+    hit = label[None, :] == torch.arange(K, device=margin.device, dtype=label.dtype)[:, None]
+    g = p - hit.to(p.dtype)
+    h = torch.clamp(2.0 * p * (1.0 - p), min=1e-16)
+    if weight is not None:
+        g, h = g * weight[None, :], h * weight[None, :]
+    return torch.stack([g, h], 2).float().contiguous()
+
+
+def multi_eval_sums(margin, label, weight):
+    """{sum w err, sum w nll, sum w} (fp64 [3]) of this rank's rows."""
+    K = margin.shape[0]
+    if (margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32
+            and (weight is None or weight.dtype == torch.float32)):
+        return _native.hip().gbdt_multi_eval(margin.contiguous(), label.contiguous(),
+                                             weight.contiguous() if weight is not None else None)
+    w = (weight if weight is not None else torch.ones_like(label)).double()
+    if label.numel() == 0:
+        return torch.zeros(3, dtype=torch.float64, device=margin.device)
+    ok = (label >= 0) & (label < K) & (label == label.floor())
+    yi = torch.where(ok, label, torch.zeros_like(label)).long()
+    m = margin.double()
+    lse = torch.logsumexp(m, 0)
+    nll = (lse - m.gather(0, yi[None, :])[0]).clamp(max=NLL_MAX)
+    nll = torch.where(ok, nll, torch.full_like(nll, NLL_MAX))
+    err = torch.where(ok, (first_argmax(m) != yi).double(), torch.ones_like(nll))
+    return torch.stack([(w * err).sum(), (w * nll).sum(), w.sum()])
+
+
+def class_gpair(gpair, k):
+    """Class k's [n, 2] slice of a multi-class gradient tensor, carrying its
+    own row of the fused kernel's root statistics (else every tree pays a
+    fresh reduction and a host wait in :func:`gpair_stats`)."""
+    gk = gpair[k]
+    st = getattr(gpair, "_wh_stats", None)
+    if st is not None:
+        gk._wh_stats = st[k]
+    return gk
 
 
 def gpair_stats(gpair):
@@ -192,6 +331,8 @@ def eval_metric(name, pred, label, weight, bsp):
         p = torch.cat([a for a, _ in parts])
         lab = torch.cat([b for _, b in parts])
         return float(ops.ref.auc(p, lab))
+    if name in MULTI_METRICS:
+        raise ValueError("eval_metric %s needs a multi-class objective (Objective.metrics)" % name)
     raise ValueError("unknown eval_metric " + name)
 
 
@@ -1343,6 +1484,27 @@ def make_builder(param, bsp, dm, cuts, B):
     return TreeBuilder(param, bsp, dm, cuts, B)
 
 
+def boost_round(obj, builder, dm, margin, gen=None, fgen=None):
+    """One boosting round on the training margins (updated in place): one
+    gradient call, then one tree per class on its own slice of the pairs and
+    margins (a single tree for a single-output objective). ``subsample``
+    (rows, from ``gen``) and ``colsample_bytree`` (features, from ``fgen``)
+    are drawn per tree. Returns the new trees in class order."""
+    p = builder.p
+    K = obj.n_group
+    gp = obj.gpair(margin, dm.label, dm.weight)
+    new = []
+    for k in range(K):
+        gk, mk = (class_gpair(gp, k), margin[k]) if K > 1 else (gp, margin)
+        if p.subsample < 1.0:
+            keep = (torch.rand(dm.n, generator=gen) < p.subsample).to(dm.device)
+            gk = gk * keep[:, None].float()
+        if p.colsample_bytree < 1.0:  # (else the builder's mask stays all-features)
+            builder.sample_features(fgen)
+        new.append(builder.build(gk, mk))
+    return new
+
+
 # ---------------------------------------------------------------- booster
 class Booster:
     MAGIC = b"WHGB"
@@ -1351,22 +1513,27 @@ class Booster:
         self.param = param
         self.num_feature = int(num_feature)
         self.trees = []
-        self.obj = Objective(param.objective)
+        self.obj = Objective(param.objective, param.num_class)
         self.base_margin = self.obj.prob_to_margin(param.base_score)
 
     def predict_margin(self, dm, ntree_limit=0):
-        margin = torch.full((dm.n,), self.base_margin, dtype=torch.float32, device=dm.device)
+        """[n] margins, or [K, n] for K classes (tree t adds to row t % K)."""
+        K = self.obj.n_group
+        margin = torch.full((dm.n,) if K == 1 else (K, dm.n), self.base_margin,
+                            dtype=torch.float32, device=dm.device)
         trees = self.trees[:ntree_limit] if ntree_limit else self.trees
-        for t in trees:
-            dm.predict_tree(t, margin)
+        for i, t in enumerate(trees):
+            dm.predict_tree(t, margin if K == 1 else margin[i % K])
         return margin
 
     def save(self, path):
         p = self.param
         with open_uri(path, "wb") as f:
             f.write(self.MAGIC)
-            hdr = ("%s|%g|%d|%d" % (p.objective, p.base_score, self.num_feature,
-                                     len(self.trees))).encode()
+            hdr = "%s|%g|%d|%d" % (p.objective, p.base_score, self.num_feature, len(self.trees))
+            if self.obj.n_group > 1:  # (single-output files keep their four fields)
+                hdr += "|%d" % self.obj.n_group
+            hdr = hdr.encode()
             f.write(struct.pack("<I", len(hdr)) + hdr)
             for t in self.trees:
                 n = len(t.feat)
@@ -1384,9 +1551,13 @@ class Booster:
             if f.read(4) != Booster.MAGIC:
                 raise ValueError("invalid model file " + path)
             (ln,) = struct.unpack("<I", f.read(4))
-            objective, base, nf, ntree = f.read(ln).decode().split("|")
+            fields = f.read(ln).decode().split("|")
+            if len(fields) not in (4, 5):
+                raise ValueError("invalid model header in " + path)
+            objective, base, nf, ntree = fields[:4]
             param.objective = objective
             param.base_score = float(base)
+            param.num_class = int(fields[4]) if len(fields) == 5 else 0
             b = Booster(param, int(nf))
             for _ in range(int(ntree)):
                 (n,) = struct.unpack("<I", f.read(4))
