@@ -14,6 +14,29 @@
 // allocations, for a GPU step of a few tens of microseconds. Here the same
 // kernels are enqueued from C++ with one Python crossing per minibatch.
 //
+// Launch sequence of a training minibatch on S: open / pull -> forward ->
+// (V-chunk bucketing) -> backward (scalar chunks, V chunks) -> push; the AUC
+// chain starts behind the backward on its side stream.
+//
+// The backward's chunk plan comes from the open: the backward's outputs and
+// scratch are allocated first (fm_bwd_alloc; after the guard, which may grow
+// the slab that gvc mirrors in direct mode), the open -- which decides each
+// key's embedding row, has the planner's 1024-key tiles and runs a look-back
+// scan already -- counts and emits the chunks with the planner's own emit_key
+// (wh_chunk_plan.h), and fm_backward runs with FmBwdPhase::kBucketRun. The
+// open's fallbacks (more keys than the look-back has tiles, where it also
+// takes the compact pull; evaluation passes have no backward) leave planning
+// to fm_backward (kAll), as before.
+//
+// Fused V update (fused_v, the default in direct mode): most embedded keys
+// occur at most kChunkV = 64 times in a minibatch, so one backward wave holds
+// the key's finished gradient row and its V row in registers. That wave applies
+// the AdaGrad step in place (fm.hip k_bwd_v<G, true>) instead of writing the
+// row to gvc for the push to read back beside a second read of V; the push
+// then skips those keys' row work (FTRL on w and fresh rows are unchanged).
+// Direct mode has no clipping / dropout / normalisation, the only readers of
+// the compact gradient rows between the backward and the push.
+//
 // Streams: the compute stream S (the caller's) and the localize stream ls,
 // where the NEXT minibatch's localize runs while this one trains
 // (LocalizeAhead, as in LinearStep::step_localize); the AUC runs on the
@@ -22,9 +45,11 @@ class DifactoStep {
  public:
   // hp: the learner's 8 DiFacto hyper-parameters; post = (grad_clipping,
   // dropout, grad_normalization, dim); direct: the FM kernels read the V
-  // rows in place in the store's slab (no post-processing)
+  // rows in place in the store's slab (no post-processing); fused_v: in
+  // direct mode, single-chunk keys get their V update in the backward
   DifactoStep(KVStore* store, std::vector<double> hp, int64_t threshold, bool l1_shrk,
-              int64_t seed, int64_t loss, std::vector<double> post, double max_load, bool direct)
+              int64_t seed, int64_t loss, std::vector<double> post, double max_load, bool direct,
+              bool fused_v)
       : store_(store), hp_(std::move(hp)), threshold_(threshold), l1_shrk_(l1_shrk), seed_(seed),
         loss_(loss), guard_(store, max_load), ahead_(store->slots_.device()) {
     TORCH_CHECK(hp_.size() == 8 && post.size() == 4, "DifactoStep: hp[8], post[4]");
@@ -36,6 +61,7 @@ class DifactoStep {
     dim_ = (int64_t)post[3];
     post_on_ = clip_ > 0 || dropout_ > 0 || gnorm_;
     direct_ = direct && !post_on_;
+    fused_v_ = fused_v && direct_;
   }
   DifactoStep(const DifactoStep&) = delete;
   DifactoStep& operator=(const DifactoStep&) = delete;
@@ -70,9 +96,20 @@ class DifactoStep {
     // feature counts pushed on data pass 0
     const bool push_cnt = train && data_pass == 0;
     if (train) guard_.before(U);  // (no slot is held across steps: nothing to remap)
+    // training: the backward's outputs and scratch exist before the open,
+    // which writes the chunk plan into them (after the guard: gvc mirrors
+    // the V slab in direct mode)
+    std::vector<Tensor> bwd;
+    wh::FmBwdPlanDst dst;
+    bool planned = false;
+    if (train && U > 0) {
+      bwd = fm_bwd_alloc(csc_off, csc_row.numel(), direct_ ? store_->V_.size(0) : U, vs_, true);
+      dst = fm_bwd_plan_dst(bwd, csc_off, csc_row.numel(), label.numel(), vs_);
+    }
     auto o = store_->difacto_open_pull(uniq, train,
                                        push_cnt ? c10::optional<Tensor>(ucnt) : c10::nullopt, hp_,
-                                       threshold_, l1_shrk_, seed_, direct_);
+                                       threshold_, l1_shrk_, seed_, direct_,
+                                       train && U > 0 ? &dst : nullptr, &planned);
     if (train) guard_.after();  // on S: one wave that reads counters only
     const Tensor &slot = o[0], &hdr = o[1], &vc = o[2], &vpos = o[3];
     ht.mark(2);
@@ -88,7 +125,13 @@ class DifactoStep {
     if (train && U > 0) {
       const c10::optional<Tensor> cv =
           csc_val.defined() && csc_val.numel() ? c10::optional<Tensor>(csc_val) : c10::nullopt;
-      auto bw = fm_backward(csc_off, csc_row, cv, fw[1], fw[2], hdr, vc, vs_);
+      // (the slabs' addresses are this step's: the guard grows them before the open)
+      const FmFuse fuse = {ptr<float>(store_->V_), ptr<float>(store_->VG_),
+                           KVStore::dhp(hp_, threshold_, l1_shrk_, seed_)};
+      // (the open's compact-pull fallback hands out a copy of the rows: unfused)
+      const bool fuse_now = fused_v_ && vc.data_ptr() == store_->V_.data_ptr();
+      auto bw = fm_backward_impl(csc_off, csc_row, cv, fw[1], fw[2], hdr, vc, vs_,
+                                 fuse_now ? &fuse : nullptr, planned ? &bwd : nullptr);
       if (post_on_)
         fm_grad_post(bw[1], m, dim_, clip_, dropout_, seed_ + 7919 * step + 1, gnorm_);
       ht.mark(4);
@@ -96,7 +139,8 @@ class DifactoStep {
       // the push and the next open rather than the backward planning)
       auc_acc_side(fw[0], label, auc_sum);
       ht.mark(6);
-      store_->difacto_push(slot, hdr, bw[0], bw[1], hp_, threshold_, l1_shrk_, seed_);
+      store_->difacto_push_after(slot, hdr, bw[0], bw[1], hp_, threshold_, l1_shrk_, seed_,
+                                 fuse_now ? c10::optional<Tensor>(ucnt) : c10::nullopt);
       ht.mark(5);
     } else if (train) {
       auc_acc_side(fw[0], label, auc_sum);
@@ -107,6 +151,7 @@ class DifactoStep {
   // drop a begun localize (end of a pass, or before a Python-path call)
   void reset() { ahead_.reset(); }
   bool direct() const { return direct_; }
+  bool fused_v() const { return fused_v_; }
   int64_t grows() const { return guard_.grows(); }
   int64_t vgrows() const { return guard_.vgrows(); }
   // the guard's last summary {keys, failed inserts, V overflows, V rows}
@@ -123,7 +168,7 @@ class DifactoStep {
   int64_t seed_, loss_;
   int vs_ = 0;
   double clip_ = 0, dropout_ = 0;
-  bool gnorm_ = false, post_on_ = false, direct_ = false;
+  bool gnorm_ = false, post_on_ = false, direct_ = false, fused_v_ = false;
   int64_t dim_ = 0;
   StoreGuard guard_;
   LocalizeAhead ahead_;

@@ -821,6 +821,23 @@ class KVStore {
                                         const c10::optional<Tensor>& cnt,
                                         const std::vector<double>& h, int64_t threshold,
                                         bool l1_shrk, int64_t seed, bool direct) {
+    return difacto_open_pull(keys, insert, cnt, h, threshold, l1_shrk, seed, direct, nullptr,
+                             nullptr);
+  }
+
+  // The open that also emits the FM backward's chunk plan (DifactoStep): keys
+  // are a localize's unique keys, plan names that localize's csc_off and the
+  // backward's pre-allocated outputs and scratch (wh::fm_bwd_plan_dst over
+  // fm_bwd_alloc's buffers, made on this stream before the call: the emitter
+  // zeroes the gw / gvc rows of multi-chunk keys). *planned: the plan was
+  // written; false on the fallbacks (more keys than the look-back has tiles,
+  // no keys), after which the backward plans for itself (FmBwdPhase::kAll).
+  std::vector<Tensor> difacto_open_pull(const Tensor& keys, bool insert,
+                                        const c10::optional<Tensor>& cnt,
+                                        const std::vector<double>& h, int64_t threshold,
+                                        bool l1_shrk, int64_t seed, bool direct,
+                                        const wh::FmBwdPlanDst* plan, bool* planned) {
+    if (planned) *planned = false;
     CHECK_IN(keys, torch::kInt64);
     const int32_t* cp = nullptr;
     if (cnt.has_value() && cnt->defined()) {
@@ -847,13 +864,14 @@ class KVStore {
     if (!wh::difacto_open_pull(table(), reinterpret_cast<const uint64_t*>(keys.data_ptr()), n,
                                cp, dhp(h, threshold, l1_shrk, seed), insert ? 1 : 0,
                                lookback(keys.device()), ptr<int32_t>(slot), ptr<float>(hdr),
-                               ptr<int64_t>(vpos), direct ? nullptr : ptr<float>(vc), s)) {
+                               ptr<int64_t>(vpos), direct ? nullptr : ptr<float>(vc), s, plan)) {
       // (too many keys for the one-launch path: the compact pull below)
       slot = find(keys, insert);
       if (cp) difacto_push_cnt(slot, *cnt, h, threshold, l1_shrk, seed);
       auto r = difacto_pull(slot, l1_shrk);
       return {slot, r[0], r[1], r[2]};
     }
+    if (planned) *planned = plan != nullptr;
     return {slot, hdr, vc, vpos};
   }
 
@@ -861,6 +879,15 @@ class KVStore {
   void difacto_push(const Tensor& slot, const Tensor& hdr, const Tensor& gw, const Tensor& gvc,
                     const std::vector<double>& h, int64_t threshold, bool l1_shrk,
                     int64_t seed) {
+    difacto_push_after(slot, hdr, gw, gvc, h, threshold, l1_shrk, seed, c10::nullopt);
+  }
+
+  // The push behind a fused backward (DifactoStep, wh::FmBwdProblem::fuse_v):
+  // with ucnt, the minibatch's occurrence counts, the keys of one V chunk have
+  // had their AdaGrad step and get only the FTRL step on w here.
+  void difacto_push_after(const Tensor& slot, const Tensor& hdr, const Tensor& gw,
+                          const Tensor& gvc, const std::vector<double>& h, int64_t threshold,
+                          bool l1_shrk, int64_t seed, const c10::optional<Tensor>& ucnt) {
     CHECK_IN(slot, torch::kInt32);
     CHECK_IN(hdr, torch::kFloat32);
     CHECK_IN(gw, torch::kFloat32);
@@ -869,10 +896,16 @@ class KVStore {
     TORCH_CHECK(hdr.numel() == 2 * n && gw.numel() == n, "push: hdr/gw size mismatch");
     TORCH_CHECK(vstride_ == 0 || (gvc.dim() == 2 && gvc.size(1) == vstride_),
                 "push: gvc must be [m, vstride]");
+    const int32_t* uc = nullptr;
+    if (ucnt.has_value()) {
+      CHECK_IN((*ucnt), torch::kInt32);
+      TORCH_CHECK(ucnt->numel() >= n, "push: count size mismatch");
+      uc = ptr<int32_t>(*ucnt);
+    }
     c10::DeviceGuard g(slot.device());
     wh::difacto_push(table(), ptr<int32_t>(slot), ptr<float>(hdr), ptr<float>(gw),
                      gvc.numel() ? ptr<float>(gvc) : nullptr, n, dhp(h, threshold, l1_shrk, seed),
-                     cur_stream(slot));
+                     cur_stream(slot), uc);
   }
 
   // ---------------------------------------------------- multi-shard (psx.hip)
@@ -1202,12 +1235,20 @@ static std::vector<Tensor> fm_bwd_alloc(const Tensor& csc_off, int64_t nnz, int6
           vstride > 0 ? torch::empty({vc_rows, vstride}, f32) : torch::empty({0}, f32), scratch};
 }
 
+// The fused update of a backward (wh::FmBwdProblem::fuse_v): the table's V
+// and VG slabs and the store's hyper-parameters.
+struct FmFuse {
+  float *v, *vg;
+  wh::DifactoHP hp;
+};
+
 // two_pass: plan without the look-back scan (count -> scan -> fill), the
 // path of more keys than the scan has tiles
 static void fm_bwd_launch(const std::vector<Tensor>& pl, const Tensor& csc_off,
                           const Tensor& csc_row, const float* csc_val, const float* dual,
                           const float* xv, const float* hdr, const float* vc, int64_t vstride,
-                          int64_t nrows, wh::FmBwdPhase phase, bool two_pass = false) {
+                          int64_t nrows, wh::FmBwdPhase phase, bool two_pass = false,
+                          const FmFuse* fuse = nullptr) {
   wh::FmBwdProblem p;
   p.nuniq = csc_off.numel() - 1;
   p.nnz = csc_row.numel();
@@ -1223,6 +1264,11 @@ static void fm_bwd_launch(const std::vector<Tensor>& pl, const Tensor& csc_off,
   p.gw = ptr<float>(pl[0]);
   p.gvc = pl[1].numel() ? ptr<float>(pl[1]) : nullptr;
   p.deterministic = deterministic();
+  if (fuse) {
+    p.fuse_v = fuse->v;
+    p.fuse_vg = fuse->vg;
+    p.fuse_hp = fuse->hp;
+  }
   const wh::Lookback lb = lookback(csc_off.device());
   wh::fm_backward(p, pl[2].data_ptr(), two_pass ? nullptr : &lb, cur_stream(csc_off), phase);
 }
@@ -1249,20 +1295,56 @@ static int64_t fm_bwd_check_run(const Tensor& dual, const c10::optional<Tensor>&
   return vc->numel() ? vc->size(0) : 0;
 }
 
-// returns (gw [U], gvc [like vc]) (linear: gvc is empty)
-std::vector<Tensor> fm_backward(const Tensor& csc_off, const Tensor& csc_row,
-                                const c10::optional<Tensor>& csc_val, const Tensor& dual,
-                                const c10::optional<Tensor>& xv, const Tensor& w_or_hdr,
-                                const c10::optional<Tensor>& vc, int64_t vstride) {
+// Where a kernel outside fm.hip (the single-shard open) writes the chunk plan
+// of a backward whose buffers `pl` (fm_bwd_alloc) exist already.
+static wh::FmBwdPlanDst fm_bwd_plan_dst(const std::vector<Tensor>& pl, const Tensor& csc_off,
+                                        int64_t nnz, int64_t nrows, int64_t vstride) {
+  wh::FmBwdProblem p = {};
+  p.nuniq = csc_off.numel() - 1;
+  p.nnz = nnz;
+  p.nrows = nrows;
+  p.csc_off = ptr<int64_t>(csc_off);
+  p.vstride = (int)vstride;
+  p.gw = ptr<float>(pl[0]);
+  p.gvc = pl[1].numel() ? ptr<float>(pl[1]) : nullptr;
+  p.deterministic = deterministic();
+  return wh::fm_bwd_plan_dst(p, pl[2].data_ptr());
+}
+
+// returns (gw [U], gvc [like vc]) (linear: gvc is empty); fuse (the native
+// step only): single-chunk keys' gvc rows are not written, see FmBwdProblem;
+// planned (the native step only): fm_bwd_alloc's buffers of this call, into
+// which the open has written the chunk plan
+static std::vector<Tensor> fm_backward_impl(const Tensor& csc_off, const Tensor& csc_row,
+                                            const c10::optional<Tensor>& csc_val,
+                                            const Tensor& dual, const c10::optional<Tensor>& xv,
+                                            const Tensor& w_or_hdr,
+                                            const c10::optional<Tensor>& vc, int64_t vstride,
+                                            const FmFuse* fuse,
+                                            const std::vector<Tensor>* planned = nullptr) {
   fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
   const int64_t vrows = fm_bwd_check_run(dual, xv, vc, vstride);
   c10::DeviceGuard g(csc_off.device());
+  if (planned) {
+    TORCH_CHECK((*planned)[1].numel() == vrows * vstride, "backward: gvc rows differ from vc's");
+    fm_bwd_launch(*planned, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
+                  optptr<float>(xv), ptr<float>(w_or_hdr), optptr<float>(vc), vstride,
+                  dual.numel(), wh::FmBwdPhase::kBucketRun, false, fuse);
+    return {(*planned)[0], (*planned)[1]};
+  }
   auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vrows, vstride, true);
   fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
                 vstride > 0 ? optptr<float>(xv) : nullptr, ptr<float>(w_or_hdr),
                 vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
-                wh::FmBwdPhase::kAll);
+                wh::FmBwdPhase::kAll, false, fuse);
   return {pl[0], pl[1]};
+}
+
+std::vector<Tensor> fm_backward(const Tensor& csc_off, const Tensor& csc_row,
+                                const c10::optional<Tensor>& csc_val, const Tensor& dual,
+                                const c10::optional<Tensor>& xv, const Tensor& w_or_hdr,
+                                const c10::optional<Tensor>& vc, int64_t vstride) {
+  return fm_backward_impl(csc_off, csc_row, csc_val, dual, xv, w_or_hdr, vc, vstride, nullptr);
 }
 
 // Phase 1 of the backward on the CURRENT stream (the planning that needs no
@@ -1316,6 +1398,45 @@ std::vector<Tensor> fm_backward_run(const std::vector<Tensor>& plan, const Tenso
                 vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
                 wh::FmBwdPhase::kRun);
   return {gw, gvc};
+}
+
+// (tests) KVStore::difacto_open_pull with the backward's chunk plan emitted by
+// the open, then the V-chunk bucketing: returns (slot, hdr, vc, vpos, plan),
+// plan as fm_backward_plan returns it, for fm_backward_run. The plan is
+// empty where the open fell back (DifactoStep then plans in the backward).
+py::tuple difacto_open_pull_plan(KVStore& store, const Tensor& keys, bool insert,
+                                 const c10::optional<Tensor>& cnt, const std::vector<double>& h,
+                                 int64_t threshold, bool l1_shrk, int64_t seed, bool direct,
+                                 const Tensor& csc_off, const Tensor& csc_row, int64_t nrows) {
+  CHECK_IN(csc_off, torch::kInt64);
+  CHECK_IN(csc_row, torch::kInt32);
+  TORCH_CHECK(csc_off.numel() == keys.numel() + 1, "open_pull_plan: csc_off must have U + 1");
+  c10::DeviceGuard g(keys.device());
+  const int64_t vstride = store.vstride();
+  check_vstride(vstride);
+  TORCH_CHECK(vstride > 0, "open_pull_plan: an embedding store");
+  const int64_t vrows = direct ? store.V_.size(0) : keys.numel();
+  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vrows, vstride, false);
+  const wh::FmBwdPlanDst dst = fm_bwd_plan_dst(pl, csc_off, csc_row.numel(), nrows, vstride);
+  bool planned = false;
+  auto o = store.difacto_open_pull(keys, insert, cnt, h, threshold, l1_shrk, seed, direct, &dst,
+                                   &planned);
+  if (!planned) return py::make_tuple(o[0], o[1], o[2], o[3], std::vector<Tensor>());
+  fm_bwd_launch(pl, csc_off, csc_row, nullptr, nullptr, nullptr, ptr<float>(o[1]), nullptr,
+                vstride, nrows, wh::FmBwdPhase::kBucket);
+  return py::make_tuple(o[0], o[1], o[2], o[3], pl);
+}
+
+// (tests) the chunk totals {scalar, V} of a backward plan, a device int64 [2]
+Tensor fm_backward_plan_totals(const std::vector<Tensor>& plan, const Tensor& csc_off,
+                               int64_t nnz, int64_t vstride) {
+  TORCH_CHECK(plan.size() == 3, "not a backward plan");
+  const wh::FmBwdPlanDst d = fm_bwd_plan_dst(plan, csc_off, nnz, 0, vstride);
+  const int64_t base = reinterpret_cast<int64_t>(plan[2].data_ptr());
+  const int64_t a = reinterpret_cast<int64_t>(d.tot_s) - base;
+  const int64_t b = reinterpret_cast<int64_t>(d.tot_v) - base;
+  auto i64 = plan[2].view(torch::kInt64);
+  return torch::stack({i64[a / 8], i64[b / 8]});
 }
 
 // gvc [mcap, vstride]; m: device int64 tensor holding the live row count
@@ -3517,10 +3638,10 @@ PYBIND11_MODULE(_hip, m) {
         "one rank's per-peer all-to-all-v plan: (esz, (own_src, own_dst, own_bytes), sends, recvs)");
   py::class_<DifactoStep>(m, "DifactoStep")
       .def(py::init<KVStore*, std::vector<double>, int64_t, bool, int64_t, int64_t,
-                    std::vector<double>, double, bool>(),
+                    std::vector<double>, double, bool, bool>(),
            py::arg("store"), py::arg("hp"), py::arg("threshold"), py::arg("l1_shrk"),
            py::arg("seed"), py::arg("loss"), py::arg("post"), py::arg("max_load"),
-           py::arg("direct"), py::keep_alive<1, 2>())
+           py::arg("direct"), py::arg("fused_v") = true, py::keep_alive<1, 2>())
       .def("step", &DifactoStep::step, py::arg("keys"), py::arg("offset"), py::arg("val"),
            py::arg("label"), py::arg("train"), py::arg("data_pass"), py::arg("met"),
            py::arg("auc_sum"), py::arg("step"), py::arg("next_keys") = py::none(),
@@ -3529,6 +3650,7 @@ PYBIND11_MODULE(_hip, m) {
       .def("reset", &DifactoStep::reset)
       .def("guard_sync", &DifactoStep::guard_sync)
       .def_property_readonly("direct", &DifactoStep::direct)
+      .def_property_readonly("fused_v", &DifactoStep::fused_v)
       .def_property_readonly("grows", &DifactoStep::grows)
       .def_property_readonly("vgrows", &DifactoStep::vgrows);
   m.def("c10d_a2a_rows", &c10d_a2a_rows, py::arg("pg"), py::arg("x"), py::arg("send_rows"),
@@ -3544,6 +3666,14 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("hdr"), py::arg("vc_rows"), py::arg("nrows"), py::arg("vstride"),
         py::arg("two_pass") = false);
   m.def("fm_backward_run", &fm_backward_run);
+  m.def("difacto_open_pull_plan", &difacto_open_pull_plan, py::arg("store"), py::arg("keys"),
+        py::arg("insert"), py::arg("cnt"), py::arg("h"), py::arg("threshold"),
+        py::arg("l1_shrk"), py::arg("seed"), py::arg("direct"), py::arg("csc_off"),
+        py::arg("csc_row"), py::arg("nrows"),
+        "(tests) the open with the backward's chunk plan: (slot, hdr, vc, vpos, plan)");
+  m.def("fm_backward_plan_totals", &fm_backward_plan_totals, py::arg("plan"),
+        py::arg("csc_off"), py::arg("nnz"), py::arg("vstride"),
+        "(tests) a backward plan's chunk totals {scalar, V}");
   m.def("fm_grad_post", &fm_grad_post);
   m.def("vidx_renumber", &vidx_renumber);
   m.def("ps_unpack", &ps_unpack);
@@ -3656,7 +3786,11 @@ PYBIND11_MODULE(_hip, m) {
       .def("linear_push", &KVStore::linear_push)
       .def("difacto_push_cnt", &KVStore::difacto_push_cnt)
       .def("difacto_pull", &KVStore::difacto_pull)
-      .def("difacto_open_pull", &KVStore::difacto_open_pull, py::arg("keys"), py::arg("insert"),
+      .def("difacto_open_pull",
+           py::overload_cast<const Tensor&, bool, const c10::optional<Tensor>&,
+                             const std::vector<double>&, int64_t, bool, int64_t, bool>(
+               &KVStore::difacto_open_pull),
+           py::arg("keys"), py::arg("insert"),
            py::arg("cnt"), py::arg("h"), py::arg("threshold"), py::arg("l1_shrk"), py::arg("seed"),
            py::arg("direct") = false)
       .def("difacto_push", &KVStore::difacto_push)

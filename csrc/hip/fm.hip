@@ -23,6 +23,8 @@
 // m keys with an embedding move 256 bytes; the rest move 8 (pull) / 4 (push).
 #include "wh_common.h"
 #include <string>
+#include "kv_device.h"
+#include "wh_chunk_plan.h"
 #include "wh_kernels.h"
 #include "wh_lookback.h"
 #include "wh_loss.h"
@@ -35,7 +37,6 @@ namespace wh {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kChunk = 32;  // occurrences per backward work item
 constexpr int kFwdBlocks = 2048;  // persistent forward grid: 8192 waves = 32 per CU
 
 // Memory-level parallelism decides both FM kernels: every V / xv row is a
@@ -267,80 +268,12 @@ __global__ __launch_bounds__(kThreads) void k_lin_fwd(int64_t nrows, const int64
 }
 
 // ---------------------------------------------------------------- backward
-// Two work lists over the CSC: keys WITHOUT an embedding are split into
-// "scalar" chunks of <= kChunkS occurrences summed by one lane each (gw
-// only); keys WITH an embedding into "V" chunks of <= kChunkV = 64
-// occurrences, one WAVE each (gw, xxp and the 64-float gV row). A key with
-// more than one chunk accumulates its chunks with float atomics.
-constexpr int kChunkV = 64;
-
-// chunks of a key with cnt occurrences
-__device__ __forceinline__ int64_t key_chunks(int64_t cnt, bool isv) {
-  return isv ? (cnt + kChunkV - 1) / kChunkV : (cnt + kChunk - 1) / kChunk;
-}
+// The two work lists (scalar chunks, V chunks) and their one emitter:
+// wh_chunk_plan.h, shared with the open that can emit the plan itself.
 
 // embedding row of key k, -1 without one (hdr == nullptr: the linear model)
 __device__ __forceinline__ int32_t key_vidx(const float2* __restrict__ hdr, int64_t k) {
   return hdr ? __float_as_int(hdr[k].y) : -1;
-}
-
-// What the chunk planners write: the scalar chunk list {key, CSC begin}, the
-// V chunk list, one packed int4 {key, CSC begin, n | multi << 8, vidx} each
-// (so the backward wave fetches a chunk's description in one load), and the
-// zeroed gradients of multi-chunk keys.
-struct ChunkOut {
-  int32_t* key_s;
-  int32_t* beg_s;
-  int4* meta_v;
-  float* gw;
-  float* gvc;
-  int vstride;
-};
-
-// The chunks [c0, c0 + nc) of key k (CSC begin b0, cnt occurrences, embedding
-// row vid when isv). Called by all 64 lanes, each with its own key (nc == 0:
-// none): a single-chunk key is written by its lane; a multi-chunk (hot) key
-// is expanded by the whole wave, 64 chunks per round, so the hottest key does
-// not serialise.
-__device__ __forceinline__ void emit_key(const ChunkOut& o, int32_t k, int64_t c0, int32_t nc,
-                                         int32_t b0, int32_t cnt, int32_t vid, int isv) {
-  const int lane = threadIdx.x & 63;
-  if (nc == 1) {
-    if (isv) {
-      o.meta_v[c0] = make_int4(k, b0, cnt, vid);
-    } else {
-      o.key_s[c0] = k;
-      o.beg_s[c0] = b0;
-    }
-  }
-  uint64_t m = __ballot(nc > 1);
-  while (m) {
-    const int src = __ffsll((unsigned long long)m) - 1;
-    m &= m - 1;
-    const int32_t jk = __shfl(k, src, 64);
-    const int64_t jc0 = __shfl(c0, src, 64);
-    const int32_t jnc = __shfl(nc, src, 64);
-    const int32_t jb0 = __shfl(b0, src, 64);
-    const int32_t jcnt = __shfl(cnt, src, 64);
-    const int32_t jvid = __shfl(vid, src, 64);
-    const int jv = __shfl(isv, src, 64);
-    for (int32_t q = lane; q < jnc; q += 64) {
-      if (jv) {
-        const int32_t cb = q * kChunkV;
-        const int32_t n = jcnt - cb < kChunkV ? jcnt - cb : kChunkV;
-        o.meta_v[jc0 + q] = make_int4(jk, jb0 + cb, n | (1 << 8), jvid);
-      } else {
-        o.key_s[jc0 + q] = jk;
-        o.beg_s[jc0 + q] = jb0 + q * kChunk;
-      }
-    }
-    if (lane == 0) o.gw[jk] = 0.f;
-    if (jv) {
-      for (int d = lane * 4; d < o.vstride; d += 256)
-        *reinterpret_cast<float4*>(o.gvc + (int64_t)jvid * o.vstride + d) =
-            make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
 }
 
 // Two-pass plan, for more keys than the look-back scan has tiles:
@@ -542,7 +475,7 @@ __global__ __launch_bounds__(kThreads) void k_vchunk_scatter(const int64_t* __re
   }
 }
 
-// scalar chunks: one lane sums dual_i * x_ik over <= kChunk occurrences
+// scalar chunks: one lane sums dual_i * x_ik over <= kChunkS occurrences
 __global__ __launch_bounds__(kThreads) void k_bwd_scalar(const int64_t* __restrict__ nchunk_p,
                                                          const int32_t* __restrict__ chunk_key,
                                                          const int32_t* __restrict__ chunk_beg,
@@ -557,7 +490,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scalar(const int64_t* __restri
   const int k = chunk_key[c];
   const int kb = (int)csc_off[k], ke = (int)csc_off[k + 1];
   const int b = chunk_beg[c];
-  const int e = b + kChunk < ke ? b + kChunk : ke;
+  const int e = b + kChunkS < ke ? b + kChunkS : ke;
   float gw = 0.f;
   int p = b;
   for (; p + 3 < e; p += 4) {  // 4 independent row->dual chains in flight
@@ -572,7 +505,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scalar(const int64_t* __restri
     for (int u = 0; u < 4; ++u) gw += dual[i[u]] * x[u];
   }
   for (; p < e; ++p) gw += dual[csc_row[p]] * (csc_val ? csc_val[p] : 1.f);
-  if (ke - kb <= kChunk) gw_out[k] = gw;
+  if (ke - kb <= kChunkS) gw_out[k] = gw;
   else if (part_gw) part_gw[c] = gw;  // deterministic: summed in chunk order later
   else atomicAdd(gw_out + k, gw);
 }
@@ -581,7 +514,21 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scalar(const int64_t* __restri
 // software-pipelined like the forward: while chunk i's xv rows are gathered,
 // the duals of chunk i+1, the CSC rows of chunk i+2 and the description of
 // chunk i+3 are in flight.
-template <int G>
+// FUSED (FmBwdProblem::fuse_v): the V rows are read from fv, the table's slab
+// (vc is null), and a single-chunk key's wave, which holds the key's finished
+// gradient row and its V row, applies the AdaGrad step itself (VG row loaded
+// beside the V row, behind the gathers) and stores V / VG instead of the gvc
+// row. In place is safe: in the backward a V row is read only by its own
+// key's chunks, and a single-chunk key has one wave. fv / fvg alias nothing
+// declared __restrict__ here. Multi-chunk keys are the same in both variants.
+// After the butterfly every one of the 64 / G sub-groups holds the whole row,
+// so with 4 or more of them (G <= 16) sub-group s updates component s of each
+// float4 -- one element per lane, a quarter of the correctly rounded sqrt /
+// divide sequences (~30 VALU instructions per element) that a float4 per
+// lane of one sub-group issues. With the float4 form the fused step measured
+// level with the unfused one on the headline, with this one 12-20 us per
+// step faster (profiles/difacto_open_plan_fused_v.txt).
+template <int G, bool FUSED>
 __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ nchunk_p,
                                                     const int4* __restrict__ meta,
                                                     const int32_t* __restrict__ csc_row,
@@ -592,8 +539,11 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
                                                     float* __restrict__ gw_out,
                                                     float* __restrict__ gvc,
                                                     float* __restrict__ part_gw,
-                                                    float* __restrict__ part_gv) {
+                                                    float* __restrict__ part_gv, float* fv,
+                                                    float* fvg, DifactoHP hp) {
   using S = Shape<G>;
+  constexpr bool kSplit = 64 / G >= 4;  // fused update: one element per lane
+  const float* vrows = FUSED ? fv : vc;
   __shared__ int2 stage[kThreads / 64][64];
   int2* st = stage[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63, gl = lane & (G - 1), sub = lane / G;
@@ -622,6 +572,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
     const bool multi = (mc.z >> 8) != 0;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 vg = make_float4(0.f, 0.f, 0.f, 0.f);
     stage_pairs<G>(st, lane, rc, dc);
     // one gather batch of TB instructions starting at instruction t0
     auto batch = [&](auto tb, int t0) {
@@ -636,7 +587,11 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
         a[t] = reinterpret_cast<const float4*>(src)[gl];
       }
       if (t0 == 0) {
-        v = reinterpret_cast<const float4*>(vc + (uint32_t)mc.w * (uint32_t)S::VS)[gl];
+        v = reinterpret_cast<const float4*>(vrows + (uint32_t)mc.w * (uint32_t)S::VS)[gl];
+        if (FUSED && !multi) {
+          if (kSplit) vg.x = fvg[(uint32_t)mc.w * (uint32_t)S::VS + gl * 4 + (sub & 3)];
+          else vg = reinterpret_cast<const float4*>(fvg + (uint32_t)mc.w * (uint32_t)S::VS)[gl];
+        }
         // prefetch the next stages behind the gathers
         dn = rn >= 0 ? dual[rn] * xn : 0.f;
         load_rows(m2, r2, x2);
@@ -677,7 +632,25 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
       else atomicAdd(gw_out + mc.x, gw);
     }
     acc.x -= xxp * v.x; acc.y -= xxp * v.y; acc.z -= xxp * v.z; acc.w -= xxp * v.w;
-    if (!multi || part_gv) {
+    if (FUSED && !multi) {
+      if (kSplit) {
+        const int comp = sub & 3;
+        const float a = comp == 0 ? acc.x : comp == 1 ? acc.y : comp == 2 ? acc.z : acc.w;
+        float v1 = comp == 0 ? v.x : comp == 1 ? v.y : comp == 2 ? v.z : v.w;
+        kvd::adagrad1(v1, vg.x, a, hp);
+        if (sub < 4) {
+          const uint32_t at = (uint32_t)mc.w * (uint32_t)S::VS + gl * 4 + comp;
+          fv[at] = v1;
+          fvg[at] = vg.x;
+        }
+      } else {
+        kvd::adagrad4(v, vg, acc, hp);
+        if (sub == 0) {
+          reinterpret_cast<float4*>(fv + (uint32_t)mc.w * (uint32_t)S::VS)[gl] = v;
+          reinterpret_cast<float4*>(fvg + (uint32_t)mc.w * (uint32_t)S::VS)[gl] = vg;
+        }
+      }
+    } else if (!multi || part_gv) {
       // single chunk: the row itself; deterministic mode: this chunk's
       // partial row (the list is key-major, unbucketed), summed in order later
       float* dst = multi ? part_gv + c * (int64_t)vstride : gvc + (int64_t)mc.w * vstride;
@@ -718,8 +691,8 @@ __global__ __launch_bounds__(kThreads) void k_bwd_reduce_s(const int64_t* __rest
   if (c >= *nchunk_p) return;
   const int k = chunk_key[c];
   const int64_t kb = csc_off[k], cnt = csc_off[k + 1] - kb;
-  if (cnt <= kChunk || chunk_beg[c] != kb) return;
-  const int64_t n = (cnt + kChunk - 1) / kChunk;
+  if (cnt <= kChunkS || chunk_beg[c] != kb) return;
+  const int64_t n = (cnt + kChunkS - 1) / kChunkS;
   float s = 0.f;
   for (int64_t q = 0; q < n; ++q) s += part_gw[c + q];
   gw_out[k] = s;
@@ -879,7 +852,7 @@ void lin_forward_strided(int64_t nrows, const int64_t* offset, const int32_t* li
                      wstride, label, loss, py, dual, part, met, ticket, acc5);
 }
 
-static int64_t scalar_cap(int64_t nuniq, int64_t nnz) { return nuniq + nnz / kChunk + 1; }
+static int64_t scalar_cap(int64_t nuniq, int64_t nnz) { return nuniq + nnz / kChunkS + 1; }
 static int64_t v_cap(int64_t nuniq, int64_t nnz) { return nuniq + nnz / kChunkV + 1; }
 
 static int bucket_shift(int64_t nrows) {
@@ -912,6 +885,16 @@ int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministi
   return at;
 }
 
+FmBwdPlanDst fm_bwd_plan_dst(const FmBwdProblem& p, void* scratch) {
+  FmBwdLayout l;
+  fm_bwd_layout(p.nuniq, p.nnz, p.vstride, p.deterministic, &l);
+  char* base = static_cast<char*>(scratch);
+  int64_t* off_s = reinterpret_cast<int64_t*>(base + l.off);
+  return {p.csc_off, reinterpret_cast<int32_t*>(base + l.key_s),
+          reinterpret_cast<int32_t*>(base + l.beg_s), base + l.meta_v, p.gw, p.gvc, p.vstride,
+          off_s + p.nuniq, off_s + p.nuniq + 1 + p.nuniq};
+}
+
 void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipStream_t s,
                  FmBwdPhase phase) {
   const int64_t nuniq = p.nuniq;
@@ -935,7 +918,7 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
   const bool bucket =
       hdr && !p.deterministic && p.nrows * (int64_t)vstride * 4 > ((int64_t)2 << 20);
   int4* meta_sorted = bucket ? meta_v + cap_v : meta_v;
-  if (phase != FmBwdPhase::kRun) {
+  if (phase == FmBwdPhase::kAll || phase == FmBwdPhase::kPlan) {
     const ChunkOut out = {key_s, beg_s, meta_v, p.gw, p.gvc, vstride};
     const int64_t ntiles = (nuniq + kPlanTile - 1) / kPlanTile;
     if (lb && ntiles <= kLbMaxTiles) {  // one launch
@@ -953,17 +936,17 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
       hipLaunchKernelGGL(k_chunk_fill, grid, dim3(kThreads), 0, s, nuniq, p.csc_off, off_s, off_v,
                          hdr, out);
     }
-    if (bucket) {
-      int32_t* hist = reinterpret_cast<int32_t*>(base + l.hist);
-      const int shift = bucket_shift(std::max<int64_t>(p.nrows, 1));
-      hipLaunchKernelGGL(k_vchunk_hist, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
-                         meta_v, p.csc_row, shift, hist);
-      hipLaunchKernelGGL(k_vchunk_scan, dim3(1), dim3(kBuckets * kScanParts), 0, s, hist);
-      hipLaunchKernelGGL(k_vchunk_scatter, dim3(kBucketBlocks), dim3(kThreads), 0, s,
-                         off_v + nuniq, meta_v, p.csc_row, shift, hist, meta_sorted);
-    }
   }
-  if (phase == FmBwdPhase::kPlan) return;
+  if (phase != FmBwdPhase::kRun && bucket) {
+    int32_t* hist = reinterpret_cast<int32_t*>(base + l.hist);
+    const int shift = bucket_shift(std::max<int64_t>(p.nrows, 1));
+    hipLaunchKernelGGL(k_vchunk_hist, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
+                       meta_v, p.csc_row, shift, hist);
+    hipLaunchKernelGGL(k_vchunk_scan, dim3(1), dim3(kBuckets * kScanParts), 0, s, hist);
+    hipLaunchKernelGGL(k_vchunk_scatter, dim3(kBucketBlocks), dim3(kThreads), 0, s,
+                       off_v + nuniq, meta_v, p.csc_row, shift, hist, meta_sorted);
+  }
+  if (phase == FmBwdPhase::kPlan || phase == FmBwdPhase::kBucket) return;
   // chunk counts are device values (off[nuniq]); the scalar kernel launches
   // over the host-side bound and surplus lanes exit; the V kernel is
   // persistent. No host synchronisation in the step.
@@ -984,11 +967,18 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
   // concurrent localize; measured round 4, removed)
   dispatch_g(vstride / 4, [&](auto g) {
     constexpr int G = decltype(g)::value;
-    const int64_t vblk =
-        std::min<int64_t>((cap_v + 3) / 4, resident_blocks(k_bwd_v<G>, 2048));
-    hipLaunchKernelGGL(k_bwd_v<G>, dim3((unsigned)vblk), dim3(kThreads), 0, s, off_v + nuniq,
-                       meta_sorted, p.csc_row, p.csc_val, p.dual, p.xv, p.vc, vstride, p.gw,
-                       p.gvc, pgv_w, pgv);
+    auto run = [&](auto kernel, const float* vc) {
+      const int64_t vblk = std::min<int64_t>((cap_v + 3) / 4, resident_blocks(kernel, 2048));
+      hipLaunchKernelGGL(kernel, dim3((unsigned)vblk), dim3(kThreads), 0, s, off_v + nuniq,
+                         meta_sorted, p.csc_row, p.csc_val, p.dual, p.xv, vc, vstride, p.gw,
+                         p.gvc, pgv_w, pgv, p.fuse_v, p.fuse_vg, p.fuse_hp);
+    };
+    if (p.fuse_v && p.fuse_v != p.vc) {
+      fprintf(stderr, "fm.hip: the fused update needs vc to be the V slab itself\n");
+      abort();
+    }
+    if (p.fuse_v) run(k_bwd_v<G, true>, nullptr);
+    else run(k_bwd_v<G, false>, p.vc);
   });
   if (det)
     hipLaunchKernelGGL(k_bwd_reduce_v, dim3(grid_for(cap_v * 64, kThreads)), dim3(kThreads), 0, s,

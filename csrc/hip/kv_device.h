@@ -106,18 +106,25 @@ __device__ __forceinline__ float difacto_ftrl(float w, float gw, float& sq, floa
   return (z > 0 ? z - hp.l1 : z + hp.l1) / eta;
 }
 
-// AdaGrad on 4 embedding elements (reference UpdateV, async_sgd.h:289-296)
+// AdaGrad on 4 embedding elements (reference UpdateV, async_sgd.h:289-296):
+//   gg = g + v_l2 v;  cg = sqrt(cg^2 + gg^2);  v -= v_alpha / (cg + v_beta) gg
+// The one copy of the update: the store's push, the multi-shard push and the
+// fused FM backward (fm.hip k_bwd_v) call it, and every rounding is spelled
+// out (the contraction the compiler chose for the push before the roundings
+// were fixed), so all callers give the same bits whatever surrounds the call.
+__device__ __forceinline__ void adagrad1(float& v, float& cg, float g, const DifactoHP& hp) {
+  const float gg = __fmaf_rn(hp.v_l2, v, g);
+  cg = sqrtf(__fadd_rn(__fmul_rn(cg, cg), __fmul_rn(gg, gg)));
+  const float eta = __fdiv_rn(hp.v_alpha, __fadd_rn(cg, hp.v_beta));
+  v = __fmaf_rn(-eta, gg, v);
+}
+
 __device__ __forceinline__ void adagrad4(float4& v, float4& cg, const float4& g,
                                          const DifactoHP& hp) {
-  float* pv = &v.x;
-  float* pc = &cg.x;
-  const float* pg = &g.x;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float gg = pg[e] + hp.v_l2 * pv[e];
-    pc[e] = sqrtf(pc[e] * pc[e] + gg * gg);
-    pv[e] -= hp.v_alpha / (pc[e] + hp.v_beta) * gg;
-  }
+  adagrad1(v.x, cg.x, g.x, hp);
+  adagrad1(v.y, cg.y, g.y, hp);
+  adagrad1(v.z, cg.z, g.z, hp);
+  adagrad1(v.w, cg.w, g.w, hp);
 }
 
 __device__ __forceinline__ float l1l2_solve(float z, float eta, float l1, float l2) {

@@ -14,6 +14,7 @@
 #include "wh_kernels.h"
 #include "wh_lookback.h"
 #include "kv_device.h"
+#include "wh_chunk_plan.h"
 
 namespace wh {
 namespace {
@@ -245,7 +246,7 @@ template <int G>
 __global__ __launch_bounds__(kThreads) void k_difacto_open_pull(
     KVTable t, const uint64_t* __restrict__ keys, int64_t n, const int32_t* __restrict__ cnt,
     DifactoHP hp, int insert, Lookback lb, int ntiles, int32_t* __restrict__ slot_out,
-    float2* hdr, int64_t* vpos, float* vc) {
+    float2* hdr, int64_t* vpos, float* vc, ChunkPlanArg plan) {
   __shared__ uint32_t shs[16];
   __shared__ int sht;
   const int tile = lb_tile(lb, ntiles, &sht);
@@ -257,6 +258,11 @@ __global__ __launch_bounds__(kThreads) void k_difacto_open_pull(
   uint64_t h[kPullPer], prev[kPullPer];
 #pragma unroll
   for (int r = 0; r < kPullPer; ++r) k[r] = i0 + r < n ? keys[i0 + r] : kEmptyKey;
+  // (plan) the keys' CSC extents, in flight beside the probes
+  int64_t co[kPullPer + 1];
+#pragma unroll
+  for (int r = 0; r <= kPullPer; ++r)
+    co[r] = plan.csc_off && i0 + r <= n ? plan.csc_off[i0 + r] : 0;
 #pragma unroll
   for (int r = 0; r < kPullPer; ++r) {  // all home-slot probes in flight together
     h[r] = mix64(k[r]) & mask;
@@ -305,16 +311,31 @@ __global__ __launch_bounds__(kThreads) void k_difacto_open_pull(
       }
     }
   }
-  uint32_t f[1] = {0u}, ex[1], tot[1];
+  // scanned: the V flags and, with a plan, the keys' scalar / V chunk counts
+  // (the per-key V decision is final here: row[r] >= 0)
+  uint32_t f[3] = {0u, 0u, 0u}, ex[3], tot[3];
+  uint32_t nc[kPullPer];
 #pragma unroll
   for (int r = 0; r < kPullPer; ++r) {
     if (hp.l1_shrk && w[r] == 0.f) row[r] = -1;  // (a fresh row has w != 0)
     f[0] += row[r] >= 0 ? 1u : 0u;
+    nc[r] = plan.csc_off && i0 + r < n ? (uint32_t)key_chunks(co[r + 1] - co[r], row[r] >= 0)
+                                       : 0u;
+    if (row[r] >= 0) f[2] += nc[r];
+    else f[1] += nc[r];
   }
   // direct (vc == null): the header points at the table's own V rows; only
   // the count of pulled rows is scanned (vpos[n])
   const bool direct = vc == nullptr;
-  lb_block_scan<1>(lb, tile, f, ex, tot, shs);
+  if (plan.csc_off) {
+    lb_block_scan<3>(lb, tile, f, ex, tot, shs);
+  } else {
+    const uint32_t f1[1] = {f[0]};
+    uint32_t ex1[1], tot1[1];
+    lb_block_scan<1>(lb, tile, f1, ex1, tot1, shs);
+    ex[0] = ex1[0];
+    tot[0] = tot1[0];
+  }
   int32_t vp[kPullPer];
   uint32_t run = ex[0];
 #pragma unroll
@@ -327,6 +348,20 @@ __global__ __launch_bounds__(kThreads) void k_difacto_open_pull(
     run += row[r] >= 0 ? 1u : 0u;
   }
   if (tile == ntiles - 1 && threadIdx.x == 0) vpos[n] = tot[0];
+  if (plan.csc_off) {  // the backward's chunk lists, with the vidx the header got
+    if (tile == ntiles - 1 && threadIdx.x == 0) {
+      *plan.tot_s = tot[1];
+      *plan.tot_v = tot[2];
+    }
+#pragma unroll
+    for (int r = 0; r < kPullPer; ++r) {
+      const int isv = row[r] >= 0;
+      emit_key(plan.out, (int32_t)(i0 + r), isv ? ex[2] : ex[1], (int32_t)nc[r], (int32_t)co[r],
+               (int32_t)(co[r + 1] - co[r]), direct ? row[r] : vp[r], isv);
+      if (isv) ex[2] += nc[r];
+      else ex[1] += nc[r];
+    }
+  }
   // event counters: inserts / failed inserts / new embedding weights
   const long long ci = wave_sum_ll(created), cf = wave_sum_ll(failed), cv = wave_sum_ll(newv);
   if (lane == 0) {
@@ -446,7 +481,8 @@ __global__ __launch_bounds__(kThreads) void k_difacto_push(KVTable t, const int3
                                                            const float2* __restrict__ hdr,
                                                            const float* __restrict__ gw,
                                                            const float* __restrict__ gvc,
-                                                           int64_t n, DifactoHP hp) {
+                                                           int64_t n, DifactoHP hp,
+                                                           const int32_t* __restrict__ ucnt) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   float oldw = 0.f, neww = 0.f;
@@ -489,7 +525,8 @@ __global__ __launch_bounds__(kThreads) void k_difacto_push(KVTable t, const int3
     t.sl[s].vrow = nrow;
     row = nrow;
     kind = 1;
-  } else if (gvid >= 0 && row >= 0) {
+  } else if (gvid >= 0 && row >= 0 && !(ucnt && ucnt[i] <= kChunkV)) {
+    // (ucnt: a single-chunk key's step was applied by the fused backward)
     kind = 2;
   }
   long long newv = kind == 1 ? t.dim : 0;
@@ -535,16 +572,7 @@ __global__ __launch_bounds__(kThreads) void k_difacto_push(KVTable t, const int3
           *reinterpret_cast<float4*>(VG) = make_float4(0.f, 0.f, 0.f, 0.f);
           continue;
         }
-        // AdaGrad on V (reference UpdateV, learn/difacto/async_sgd.h:289-296)
-        float* pv = &v[b].x;
-        float* pc = &cg[b].x;
-        const float* pg = &g[b].x;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float gg = pg[e] + hp.v_l2 * pv[e];
-          pc[e] = sqrtf(pc[e] * pc[e] + gg * gg);
-          pv[e] -= hp.v_alpha / (pc[e] + hp.v_beta) * gg;
-        }
+        adagrad4(v[b], cg[b], g[b], hp);
         *reinterpret_cast<float4*>(V) = v[b];
         *reinterpret_cast<float4*>(VG) = cg[b];
       }
@@ -569,16 +597,7 @@ __global__ __launch_bounds__(kThreads) void k_difacto_push(KVTable t, const int3
     for (int c = gl * 4; c < t.vstride; c += 4 * G) {
       float4 v = *reinterpret_cast<float4*>(V + c);
       float4 cg = *reinterpret_cast<float4*>(VG + c);
-      const float4 g = *reinterpret_cast<const float4*>(gv + c);
-      float* pv = &v.x;
-      float* pc = &cg.x;
-      const float* pg = &g.x;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float gg = pg[e] + hp.v_l2 * pv[e];
-        pc[e] = sqrtf(pc[e] * pc[e] + gg * gg);
-        pv[e] -= hp.v_alpha / (pc[e] + hp.v_beta) * gg;
-      }
+      adagrad4(v, cg, *reinterpret_cast<const float4*>(gv + c), hp);
       *reinterpret_cast<float4*>(V + c) = v;
       *reinterpret_cast<float4*>(VG + c) = cg;
     }
@@ -656,12 +675,12 @@ void difacto_pull_rows(const KVTable& t, const int32_t* slot, int64_t n, const i
 }
 
 void difacto_push(const KVTable& t, const int32_t* slot, const float* hdr, const float* gw,
-                  const float* gvc, int64_t n, DifactoHP hp, hipStream_t s) {
+                  const float* gvc, int64_t n, DifactoHP hp, hipStream_t s, const int32_t* ucnt) {
   if (n <= 0) return;
   const int G = lanes_per_key(t.vstride);
   const dim3 grid(grid_for(n, kThreads)), block(kThreads);  // lane per key
   WH_DISPATCH_G(G, k_difacto_push, grid, block, 0, s, t, slot,
-                reinterpret_cast<const float2*>(hdr), gw, gvc, n, hp);
+                reinterpret_cast<const float2*>(hdr), gw, gvc, n, hp, ucnt);
 }
 
 void vidx_renumber(float* hdr, int64_t n, int32_t* flag_tmp, int64_t* pos_tmp, int64_t* scan_tmp,
@@ -713,13 +732,13 @@ namespace wh {
 
 bool difacto_open_pull(const KVTable& t, const uint64_t* keys, int64_t n, const int32_t* cnt,
                        DifactoHP hp, int insert, const Lookback& lb, int32_t* slot, float* hdr,
-                       int64_t* vpos, float* vc, hipStream_t s) {
+                       int64_t* vpos, float* vc, hipStream_t s, const FmBwdPlanDst* plan) {
   const int64_t ntiles = (n + kPullTile - 1) / kPullTile;
   if (n <= 0 || ntiles > kLbMaxTiles) return false;
   const int G = lanes_per_key(t.vstride);
   const dim3 grid((unsigned)ntiles), block(kThreads);
   WH_DISPATCH_G(G, k_difacto_open_pull, grid, block, 0, s, t, keys, n, cnt, hp, insert, lb,
-                (int)ntiles, slot, reinterpret_cast<float2*>(hdr), vpos, vc);
+                (int)ntiles, slot, reinterpret_cast<float2*>(hdr), vpos, vc, chunk_plan_arg(plan));
   return true;
 }
 

@@ -18,7 +18,7 @@ void scan_i32(const int32_t* in, int64_t* out, int64_t n, int64_t* tmp, hipStrea
 void scan_i64(const int64_t* in, int64_t* out, int64_t n, int64_t* tmp, hipStream_t s);
 // Decoupled look-back state (device side in wh_lookback.h).
 constexpr int kLbMaxTiles = 1 << 16;
-constexpr int kLbChannels = 2;
+constexpr int kLbChannels = 3;
 struct Lookback {
   unsigned long long* gran;  // [kLbChannels][kLbMaxTiles] {tag, value} granules
   unsigned int* ticket;      // [1], zero between launches
@@ -210,9 +210,12 @@ void difacto_pull_hdr(const KVTable& t, const int32_t* slot, int64_t n, int l1_s
 void difacto_pull_rows(const KVTable& t, const int32_t* slot, int64_t n, const int32_t* vflag,
                        const int64_t* vpos, float* hdr, float* vc, hipStream_t s);
 // push: gw[i] for every key (FTRL on w), gvc[vidx_i] for keys whose pull
-// header (owner numbering) carried a V row (AdaGrad on V)
+// header (owner numbering) carried a V row (AdaGrad on V). ucnt (optional):
+// the keys' occurrence counts in the minibatch; keys with ucnt <= kChunkV
+// skip the AdaGrad step (the fused backward has applied it, FmBwdProblem).
 void difacto_push(const KVTable& t, const int32_t* slot, const float* hdr, const float* gw,
-                  const float* gvc, int64_t n, DifactoHP hp, hipStream_t s);
+                  const float* gvc, int64_t n, DifactoHP hp, hipStream_t s,
+                  const int32_t* ucnt = nullptr);
 // worker side of a multi-shard pull: renumber hdr[i].y into the local
 // compact order (exclusive scan of hdr[i].y >= 0); tmp = n int32 +
 // scan_tmp_elems(n) int64; count[0] = m
@@ -225,10 +228,15 @@ void vidx_renumber(float* hdr, int64_t n, int32_t* flag_tmp, int64_t* pos_tmp, i
 bool difacto_pull_fused(const KVTable& t, const int32_t* slot, int64_t n, int l1_shrk,
                         const Lookback& lb, float* hdr, int64_t* vpos, float* vc, hipStream_t s);
 // single-shard minibatch open: find-or-insert the (distinct) keys -> slot,
-// add cnt (int32, may be null) with lazy V allocation, then the fused pull
+// add cnt (int32, may be null) with lazy V allocation, then the fused pull.
+// plan (optional; keys in the order of the localize whose csc_off it names):
+// the FM backward's chunk plan is emitted too, with the vidx the header gets
+// (fm_backward then runs with FmBwdPhase::kBucketRun).
+struct FmBwdPlanDst;
 bool difacto_open_pull(const KVTable& t, const uint64_t* keys, int64_t n, const int32_t* cnt,
                        DifactoHP hp, int insert, const Lookback& lb, int32_t* slot, float* hdr,
-                       int64_t* vpos, float* vc, hipStream_t s);
+                       int64_t* vpos, float* vc, hipStream_t s,
+                       const FmBwdPlanDst* plan = nullptr);
 bool vidx_renumber_fused(float* hdr, int64_t n, const Lookback& lb, int64_t* count,
                          hipStream_t s);
 
@@ -337,12 +345,25 @@ struct FmBwdProblem {
   // (WH_DETERMINISTIC=1) hot keys' chunk partials are summed in occurrence
   // order by a second pass instead of float atomics
   bool deterministic;
+  // Fused update (the single-shard native step in direct mode, where vc IS
+  // the table's V slab): a key whose occurrences fit one V chunk gets its
+  // AdaGrad step from the backward wave that holds its finished gradient row,
+  // which writes V / VG instead of the gvc row; difacto_push (skip_single)
+  // then leaves those keys' rows alone. Null: every gradient row goes to gvc.
+  float* fuse_v = nullptr;
+  float* fuse_vg = nullptr;
+  DifactoHP fuse_hp = {};
 };
+// occurrences per V chunk of the backward (one wave each); a key with at most
+// this many has one chunk
+constexpr int kChunkV = 64;
 // kPlan: only the planning that needs no dual (chunk lists + V-chunk
 // bucketing: CSC offsets and the pull header), so it can run on a side stream
 // concurrently with the forward; kRun: the rest (dual / xv dependent), after
-// kPlan with the same problem sizes and scratch; kAll: both.
-enum class FmBwdPhase { kAll, kPlan, kRun };
+// kPlan with the same problem sizes and scratch; kAll: both. After a chunk
+// plan that another kernel emitted (the single-shard open, FmBwdPlanDst):
+// kBucket, the V-chunk bucketing alone, then kRun; kBucketRun: both.
+enum class FmBwdPhase { kAll, kPlan, kRun, kBucket, kBucketRun };
 // The backward's scratch is ONE buffer of fm_bwd_layout(...) bytes (16-byte
 // aligned base); the regions' byte offsets, for the record:
 struct FmBwdLayout {
@@ -355,6 +376,19 @@ struct FmBwdLayout {
 };
 int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministic,
                       FmBwdLayout* out = nullptr);
+// Where the chunk plan of problem p lives in `scratch`, for a kernel outside
+// fm.hip that emits it (p: sizes, csc_off, vstride, gw, gvc, deterministic):
+// the lists, the gradients whose multi-chunk rows the emitter zeroes, and the
+// total words off_s[nuniq] / off_v[nuniq]. meta_v is an int4 array.
+struct FmBwdPlanDst {
+  const int64_t* csc_off;
+  int32_t *key_s, *beg_s;
+  void* meta_v;
+  float *gw, *gvc;
+  int vstride;
+  int64_t *tot_s, *tot_v;
+};
+FmBwdPlanDst fm_bwd_plan_dst(const FmBwdProblem& p, void* scratch);
 // lb == nullptr (or more keys than the look-back scan has tiles): the
 // two-pass plan (count -> scan -> fill) instead of the single-launch one
 void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipStream_t s,

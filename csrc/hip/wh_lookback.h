@@ -146,7 +146,11 @@ __device__ __forceinline__ uint32_t lb_exclusive(const Lookback& lb, int ch, int
 // Block-wide exclusive scan of one uint32 per thread for NV channels.
 // Returns each thread's exclusive prefix WITHIN the whole scan (block
 // prefix from the look-back included) and writes the grand totals (valid
-// only in the last tile) to total[]. `sh` needs 16 + 2*NV uint32 of LDS.
+// only in the last tile) to total[]. `sh` needs 5 * NV uint32 of LDS (blocks
+// of at most 4 waves): the waves' partials at [c * 4 + wave], then the block
+// prefixes at [4 * NV + c]. The channels' look-backs run side by side, wave c
+// on channel c (each is a chain of memory round trips), where the block has
+// that many waves.
 template <int NV>
 __device__ __forceinline__ void lb_block_scan(const Lookback& lb, int tile, const uint32_t (&v)[NV],
                                               uint32_t (&excl)[NV], uint32_t (&total)[NV],
@@ -177,17 +181,19 @@ __device__ __forceinline__ void lb_block_scan(const Lookback& lb, int tile, cons
       btot[c] += s;
     }
   }
-  if (wid == 0) {
+  const bool split = nw >= NV;
+  if (split ? wid < NV : wid == 0) {
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
+      if (split && wid != c) continue;
       const uint32_t p = lb_exclusive(lb, c, tile, btot[c]);
-      if (lane == 0) sh[8 + c] = p;
+      if (lane == 0) sh[4 * NV + c] = p;
     }
   }
   __syncthreads();
 #pragma unroll
   for (int c = 0; c < NV; ++c) {
-    const uint32_t p = sh[8 + c];
+    const uint32_t p = sh[4 * NV + c];
     excl[c] = p + wbase[c] + inc[c] - v[c];
     total[c] = p + btot[c];
   }

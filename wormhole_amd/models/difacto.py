@@ -73,7 +73,10 @@ class DifactoLearner:
         # One shard on the GPU: the FM kernels read the V rows in place in the
         # table's slab instead of a pulled copy (kv.difacto_open_pull direct)
         # -- unless the embedding gradients are post-processed (clipping /
-        # dropout / normalisation walk the compact gradient rows).
+        # dropout / normalisation walk the compact gradient rows). In that
+        # mode the native step also applies the V update of keys with at most
+        # 64 occurrences inside the backward (WH_DIFACTO_FUSED_V=0: all in the
+        # push, as the op-by-op step does).
         post = emb is not None and (emb.grad_clipping > 0 or emb.dropout > 0
                                     or bool(emb.grad_normalization))
         self.direct_pull = (self.device.type == "cuda" and comm.size == 1 and self.vstride > 0
@@ -95,7 +98,8 @@ class DifactoLearner:
                 l1_shrk=self.l1_shrk, seed=int(seed), loss=int(self.loss),
                 post=[float(e.grad_clipping), float(e.dropout),
                       1.0 if e.grad_normalization else 0.0, float(self.dim)],
-                max_load=float(self.kv.guard.max_load), direct=self.direct_pull)
+                max_load=float(self.kv.guard.max_load), direct=self.direct_pull,
+                fused_v=os.environ.get("WH_DIFACTO_FUSED_V", "1") != "0")
 
     def psx_linear_hp(self):
         """Embedding-free model on the multi-shard step's linear wire format:
