@@ -1,18 +1,18 @@
 // torch / pybind11 binding layer for the gfx950 HIP kernels (module
-// wormhole_amd._hip). Host-only translation unit: validates tensors, sizes
+// wormhole_amd._hip): the module itself and everything that shares the
+// parameter-server state -- localize, KVStore, FM, the native steps, RCCL,
+// the AUC chain, quantisation. The stateless BSP families have translation
+// units of their own (gbdt_ops.cc, kmeans_ops.cc, bsp_ops.cc, ingest_ops.cc;
+// registered from PYBIND11_MODULE below). Host-only: validates tensors, sizes
 // outputs and launches on the current PyTorch HIP stream.
-#include <torch/extension.h>
-#include <pybind11/stl.h>
-#include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
+#include "bind_common.h"
+
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPCachingAllocator.h>
-#include <hip/hip_runtime.h>
 #include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
 #include <torch/csrc/distributed/c10d/Work.hpp>
 
 #include <algorithm>
-#include <map>
 #include <array>
 #include <cstdio>
 #include <cstdlib>
@@ -31,35 +31,12 @@
 #include <string>
 #include <vector>
 
-#include "hip/wh_kernels.h"
 #include "host/auc_host.h"
 #include "host/store_guard_plan.h"
 
+using namespace wh_bind;
+
 namespace {
-
-using torch::Tensor;
-
-inline hipStream_t cur_stream(const Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
-
-#define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be a GPU tensor")
-#define CHECK_CONT(t) TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
-#define CHECK_DT(t, dt) TORCH_CHECK((t).scalar_type() == (dt), #t " has wrong dtype ", (t).scalar_type())
-#define CHECK_IN(t, dt) \
-  CHECK_DEV(t);         \
-  CHECK_CONT(t);        \
-  CHECK_DT(t, dt)
-
-template <typename T>
-T* ptr(const Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
-
-#define WH_HIP_CHECK_HOST(expr)                                                   \
-  do {                                                                          \
-    hipError_t _e = (expr);                                                     \
-    TORCH_CHECK(_e == hipSuccess, "HIP error ", hipGetErrorString(_e), " at ",  \
-                __FILE__, ":", __LINE__);                                       \
-  } while (0)
 
 // The host's wait for a step's one device read (the localize counts, the
 // store guard's summary): polled for up to 2 ms before a blocking wait. The
@@ -78,18 +55,6 @@ inline void wait_event(hipEvent_t e) {
   }
 #endif
   WH_HIP_CHECK_HOST(hipEventSynchronize(e));
-}
-
-template <typename T>
-const T* optptr(const c10::optional<Tensor>& t) {
-  return (t.has_value() && t->defined() && t->numel() > 0) ? reinterpret_cast<const T*>(t->data_ptr())
-                                                           : nullptr;
-}
-
-inline int64_t next_pow2(int64_t x) {
-  int64_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
 }
 
 // Per-device persistent workspaces (allocated once, zero-initialised; the
@@ -2052,550 +2017,6 @@ Tensor gather_rows(const Tensor& in, const Tensor& idx) {
 
 int64_t vstride_for(int64_t dim) { return dim == 0 ? 0 : 4 * next_pow2((dim + 3) / 4); }
 
-// ------------------------------------------------------------------ gbdt
-Tensor gbdt_bin(const Tensor& X, const Tensor& cuts, const Tensor& cut_off) {
-  CHECK_IN(X, torch::kFloat32);
-  CHECK_IN(cuts, torch::kFloat32);
-  CHECK_IN(cut_off, torch::kInt32);
-  TORCH_CHECK(X.dim() == 2 && cut_off.numel() == X.size(1) + 1);
-  c10::DeviceGuard g(X.device());
-  auto B = torch::empty({X.size(0), X.size(1)}, X.options().dtype(torch::kUInt8));
-  wh::gbdt_bin(ptr<float>(X), X.size(0), (int)X.size(1), ptr<float>(cuts), ptr<int32_t>(cut_off),
-               ptr<uint8_t>(B), cur_stream(X));
-  return B;
-}
-
-// tasks [T, 5] (slot, fbeg, fcnt, rbeg, rend); red [R, 6] (slot, fbeg, fcnt,
-// t0, nt, tstride) sums the fp32 partials of tasks t0 + k * tstride into hist
-// qscale [2] float32 = {2^eg, 2^eh}: fixed-point scales of g and h (see gbdt.hip);
-// [3] = {2^eg, 2^eh, R}: int32 LDS sums over <= R rows (k_hist W32)
-void gbdt_hist(const Tensor& B, int64_t nbin, const Tensor& ridx, const Tensor& gpair,
-               const Tensor& qscale, const Tensor& tasks, const Tensor& red, int64_t max_fcnt,
-               const Tensor& hist) {
-  CHECK_IN(B, torch::kUInt8);
-  CHECK_IN(ridx, torch::kInt32);
-  CHECK_IN(gpair, torch::kFloat32);
-  CHECK_IN(tasks, torch::kInt32);
-  CHECK_IN(red, torch::kInt32);
-  CHECK_IN(hist, torch::kFloat64);
-  TORCH_CHECK(nbin >= 1 && nbin <= 255, "nbin must be in [1, 255]");
-  CHECK_IN(qscale, torch::kFloat32);
-  TORCH_CHECK(qscale.numel() == 2 || qscale.numel() == 3,
-              "qscale must hold {scale_g, scale_h} or {scale_g, scale_h, int32 rows}");
-  TORCH_CHECK(wh::gbdt_hist_lds((int)max_fcnt, (int)nbin) <= 160 * 1024, "feature group too wide");
-  TORCH_CHECK(tasks.dim() == 2 && tasks.size(1) == 5);
-  TORCH_CHECK(red.dim() == 2 && red.size(1) == 6);
-  const int f = (int)B.size(1);
-  TORCH_CHECK(hist.numel() % ((int64_t)f * nbin * 2) == 0, "hist must be [S, F, nbin, 2]");
-  // dword row loads need every group 4-aligned; the caller guarantees equal
-  // multiple-of-4 groups when f % 4 == 0 (checked again here on the host copy)
-  bool dw = f % 4 == 0 && max_fcnt % 4 == 0;
-  c10::DeviceGuard g(B.device());
-  auto part = torch::empty({tasks.size(0) * wh::gbdt_hist_pstride((int)max_fcnt, (int)nbin)},
-                           gpair.options().dtype(torch::kInt64));
-  wh::gbdt_hist(ptr<uint8_t>(B), f, (int)nbin, ptr<int32_t>(ridx), ptr<float>(gpair),
-                ptr<float>(qscale), ptr<int32_t>(tasks), (int)tasks.size(0), ptr<int32_t>(red),
-                (int)red.size(0), (int)max_fcnt, dw, ptr<int64_t>(part), ptr<double>(hist),
-                cur_stream(B), nullptr, 0, nullptr, qscale.numel() == 3);
-}
-
-// ------------------------------------------------------------------ lbfgs
-Tensor owlqn_dir(const Tensor& g, const Tensor& w, double l1, const c10::optional<Tensor>& out) {
-  CHECK_IN(g, torch::kFloat32);
-  CHECK_IN(w, torch::kFloat32);
-  TORCH_CHECK(g.numel() == w.numel());
-  c10::DeviceGuard dg(g.device());
-  Tensor d = out.has_value() ? *out : torch::empty_like(g);
-  if (out.has_value()) {
-    CHECK_IN(d, torch::kFloat32);
-    TORCH_CHECK(d.numel() == g.numel(), "owlqn_dir: out size");
-  }
-  wh::owlqn_dir(ptr<float>(g), ptr<float>(w), g.numel(), (float)l1, ptr<float>(d), cur_stream(g));
-  return d;
-}
-
-Tensor owlqn_fix_dot(const Tensor& d, const Tensor& steep, bool fix) {
-  CHECK_IN(d, torch::kFloat32);
-  CHECK_IN(steep, torch::kFloat32);
-  TORCH_CHECK(d.numel() == steep.numel());
-  c10::DeviceGuard dg(d.device());
-  auto part = torch::empty({wh::owlqn_part_doubles()}, d.options().dtype(torch::kFloat64));
-  auto v = torch::empty({1}, d.options().dtype(torch::kFloat64));
-  wh::owlqn_fix_dot(ptr<float>(d), ptr<float>(steep), d.numel(), fix ? 1 : 0, ptr<double>(part),
-                    ptr<double>(v), cur_stream(d));
-  return v;
-}
-
-std::vector<Tensor> owlqn_step(const Tensor& w, const Tensor& d, double alpha, bool fix) {
-  CHECK_IN(w, torch::kFloat32);
-  CHECK_IN(d, torch::kFloat32);
-  TORCH_CHECK(w.numel() == d.numel());
-  c10::DeviceGuard dg(w.device());
-  auto nw = torch::empty_like(w);
-  auto part = torch::empty({wh::owlqn_part_doubles()}, w.options().dtype(torch::kFloat64));
-  auto l1 = torch::empty({1}, w.options().dtype(torch::kFloat64));
-  wh::owlqn_step(ptr<float>(w), ptr<float>(d), w.numel(), (float)alpha, fix ? 1 : 0,
-                 ptr<float>(nw), ptr<double>(part), ptr<double>(l1), cur_stream(w));
-  return {nw, l1};
-}
-
-// <H[r], H[probe k]> for every row r of the history [R, n]: [R, K] fp64
-Tensor hist_dots(const Tensor& H, const std::vector<int64_t>& probes) {
-  CHECK_IN(H, torch::kFloat32);
-  TORCH_CHECK(H.dim() == 2, "hist_dots: H must be [R, n]");
-  const int R = (int)H.size(0), K = (int)probes.size();
-  std::vector<int32_t> pr(K);
-  for (int k = 0; k < K; ++k) {
-    TORCH_CHECK(probes[k] >= 0 && probes[k] < R, "hist_dots: probe row out of range");
-    pr[k] = (int32_t)probes[k];
-  }
-  c10::DeviceGuard dg(H.device());
-  auto part = torch::empty({wh::owlqn_part_doubles() * 4}, H.options().dtype(torch::kFloat64));
-  auto out = torch::empty({R, K}, H.options().dtype(torch::kFloat64));
-  TORCH_CHECK(wh::hist_dots(ptr<float>(H), R, H.size(1), H.size(1), pr.data(), K,
-                            ptr<double>(part), ptr<double>(out), cur_stream(H)),
-              "hist_dots: 1..4 probes, row length a multiple of 4");
-  return out;
-}
-
-// the direction slice d = sum coef[r] H[rows[r]] (fp32, list order), sign
-// fixed against H[steep_row]; returns (d, sum d * steep as fp64 [1])
-std::vector<Tensor> dir_fix_dot(const Tensor& H, const std::vector<int64_t>& rows,
-                                const std::vector<double>& coef, int64_t steep_row, bool fix,
-                                int64_t n) {
-  CHECK_IN(H, torch::kFloat32);
-  TORCH_CHECK(H.dim() == 2 && rows.size() == coef.size() && rows.size() <= 64,
-              "dir_fix_dot: <= 64 rows of H [R, n]");
-  const int R = (int)H.size(0);
-  std::vector<int32_t> r32(rows.size());
-  std::vector<float> c32(rows.size());
-  for (size_t i = 0; i < rows.size(); ++i) {
-    TORCH_CHECK(rows[i] >= 0 && rows[i] < R, "dir_fix_dot: row out of range");
-    r32[i] = (int32_t)rows[i];
-    c32[i] = (float)coef[i];
-  }
-  TORCH_CHECK(steep_row >= 0 && steep_row < R, "dir_fix_dot: steep row out of range");
-  if (n < 0) n = H.size(1);
-  TORCH_CHECK(n <= H.size(1), "dir_fix_dot: n exceeds the row length");
-  c10::DeviceGuard dg(H.device());
-  auto d = torch::empty({n}, H.options());
-  auto part = torch::empty({wh::owlqn_part_doubles()}, H.options().dtype(torch::kFloat64));
-  auto v = torch::empty({1}, H.options().dtype(torch::kFloat64));
-  wh::dir_fix_dot(ptr<float>(H), n, H.size(1), r32.data(), c32.data(), (int)rows.size(),
-                  (int)steep_row, fix ? 1 : 0, ptr<float>(d), ptr<double>(part), ptr<double>(v),
-                  cur_stream(H));
-  return {d, v};
-}
-
-Tensor multi_dot(const Tensor& H, const Tensor& ia, const Tensor& ib) {
-  CHECK_IN(H, torch::kFloat32);
-  CHECK_IN(ia, torch::kInt32);
-  CHECK_IN(ib, torch::kInt32);
-  TORCH_CHECK(H.dim() == 2 && ia.numel() == ib.numel());
-  c10::DeviceGuard dg(H.device());
-  const int R = (int)H.size(0), np = (int)ia.numel();
-  auto out = torch::zeros({np}, H.options().dtype(torch::kFloat64));
-  TORCH_CHECK(wh::multi_dot(ptr<float>(H), R, H.size(1), ptr<int32_t>(ia), ptr<int32_t>(ib), np,
-                            ptr<double>(out), cur_stream(H)),
-              "multi_dot: at most 64 rows and 64 pairs");
-  return out;
-}
-
-Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid, double alpha,
-                  double lambda, double min_child_weight) {
-  CHECK_IN(hist, torch::kFloat64);
-  CHECK_IN(totals, torch::kFloat64);
-  CHECK_IN(valid, torch::kBool);
-  c10::DeviceGuard g(hist.device());
-  TORCH_CHECK(hist.dim() == 4 && hist.size(3) == 2, "hist must be [S, F, nbin, 2]");
-  const int S = (int)hist.size(0), F = (int)hist.size(1), nbin = (int)hist.size(2);
-  TORCH_CHECK(totals.numel() == 2 * (int64_t)S, "totals must be [S, 2]");
-  TORCH_CHECK(valid.numel() == (int64_t)F * nbin, "valid must be [F, nbin]");
-  auto out = torch::empty({S, 6}, hist.options());
-  auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 4, 1)}, hist.options());
-  TORCH_CHECK(wh::gbdt_split(ptr<double>(hist), ptr<double>(totals),
-                             reinterpret_cast<const uint8_t*>(valid.data_ptr()), S, F, nbin,
-                             alpha, lambda, min_child_weight, ptr<double>(cand), ptr<double>(out),
-                             cur_stream(hist)),
-              "gbdt_split: nbin > 1024 or empty input");
-  return out;
-}
-
-Tensor gbdt_seg_fill(const Tensor& beg, const Tensor& node, int64_t n) {
-  CHECK_IN(beg, torch::kInt32);
-  CHECK_IN(node, torch::kInt32);
-  TORCH_CHECK(beg.numel() == node.numel() && beg.numel() > 0, "segment arrays mismatch");
-  c10::DeviceGuard g(beg.device());
-  auto out = torch::empty({n}, beg.options());
-  wh::gbdt_seg_fill(ptr<int32_t>(beg), ptr<int32_t>(node), (int)beg.numel(), n, ptr<int32_t>(out),
-                    cur_stream(beg));
-  return out;
-}
-
-// partition the positions of the split nodes; returns the new ridx
-Tensor gbdt_partition(const Tensor& B, const Tensor& ridx, const Tensor& pos_node,
-                      const Tensor& node_feat, const Tensor& node_bin, const Tensor& node_defl,
-                      const Tensor& seg_beg, const Tensor& seg_end, Tensor nleft_out,
-                      const c10::optional<Tensor>& Bc) {
-  CHECK_IN(B, torch::kUInt8);
-  const uint8_t* bc = nullptr;
-  if (Bc.has_value() && Bc->defined()) {
-    CHECK_IN((*Bc), torch::kUInt8);
-    TORCH_CHECK(Bc->dim() == 2 && Bc->size(0) == B.size(1) && Bc->size(1) == B.size(0),
-                "Bc must be B transposed ([f, nrows])");
-    bc = ptr<uint8_t>(*Bc);
-  }
-  CHECK_IN(ridx, torch::kInt32);
-  CHECK_IN(pos_node, torch::kInt32);
-  c10::DeviceGuard g(B.device());
-  auto s = cur_stream(B);
-  const int64_t n = ridx.numel();
-  auto left = torch::empty({n}, ridx.options());
-  wh::gbdt_goleft(ptr<uint8_t>(B), bc, B.size(0), (int)B.size(1), ptr<int32_t>(ridx), n,
-                  ptr<int32_t>(pos_node), ptr<int32_t>(node_feat), ptr<int32_t>(node_bin),
-                  ptr<uint8_t>(node_defl), ptr<int32_t>(left), s);
-  auto lscan = torch::empty({n + 1}, ridx.options().dtype(torch::kInt64));
-  auto tmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-  wh::scan_i32(ptr<int32_t>(left), ptr<int64_t>(lscan), n, ptr<int64_t>(tmp), s);
-  // nleft[node] = lscan[end] - lscan[beg]
-  auto nl = (lscan.index_select(0, seg_end.to(torch::kInt64)) -
-             lscan.index_select(0, seg_beg.to(torch::kInt64))).to(torch::kInt32);
-  nleft_out.copy_(nl);
-  auto out = torch::empty_like(ridx);
-  wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), ptr<int32_t>(node_feat),
-                   ptr<int32_t>(seg_beg), ptr<int32_t>(nleft_out), ptr<int32_t>(left),
-                   ptr<int64_t>(lscan), ptr<int32_t>(out), s);
-  return out;
-}
-
-void gbdt_leaf_add(const Tensor& ridx, const Tensor& pos_node, const Tensor& leaf,
-                   const Tensor& margin) {
-  CHECK_IN(ridx, torch::kInt32);
-  CHECK_IN(leaf, torch::kFloat32);
-  CHECK_IN(margin, torch::kFloat32);
-  c10::DeviceGuard g(ridx.device());
-  wh::gbdt_leaf_add(ptr<int32_t>(ridx), ridx.numel(), ptr<int32_t>(pos_node), ptr<float>(leaf),
-                    ptr<float>(margin), cur_stream(ridx));
-}
-
-// tree arrays: int32 feat / bin / left / right, uint8 defl, float val [nodes]
-// (gpair f32 [n, 2], stats f64 [4] = {sum g, sum h, max|g|, max|h|})
-std::vector<Tensor> gbdt_gpair(const Tensor& margin, const Tensor& label,
-                               const c10::optional<Tensor>& weight, bool logistic) {
-  CHECK_IN(margin, torch::kFloat32);
-  CHECK_IN(label, torch::kFloat32);
-  const int64_t n = margin.numel();
-  TORCH_CHECK(label.numel() == n, "gbdt_gpair: label size mismatch");
-  const float* wp = nullptr;
-  if (weight.has_value() && weight->defined()) {
-    CHECK_IN((*weight), torch::kFloat32);
-    TORCH_CHECK(weight->numel() == n, "gbdt_gpair: weight size mismatch");
-    wp = ptr<float>(*weight);
-  }
-  c10::DeviceGuard g(margin.device());
-  static std::vector<Tensor> scratch(64);  // per device, the ticket tail stays zeroed
-  const int dev = margin.device().index();
-  if (!scratch[dev].defined())
-    scratch[dev] = torch::zeros({wh::gbdt_gpair_scratch()}, margin.options().dtype(torch::kFloat64));
-  auto gp = torch::empty({n, 2}, margin.options());
-  auto st = n > 0 ? torch::empty({4}, margin.options().dtype(torch::kFloat64))  // k_gpair writes all 4
-                  : torch::zeros({4}, margin.options().dtype(torch::kFloat64));
-  if (n > 0)
-    wh::gbdt_gpair(n, ptr<float>(margin), ptr<float>(label), wp, logistic, ptr<float>(gp),
-                   ptr<double>(scratch[dev]), ptr<double>(st), cur_stream(margin));
-  return {gp, st};
-}
-
-// ---- multi-class softmax: margin f32 [K, n] class-major, label f32 [n]
-namespace {
-// per device, grown with K; the ticket words at its head stay zeroed
-double* softmax_scratch(const Tensor& like, int64_t K) {
-  static std::vector<Tensor> scratch(64);
-  Tensor& t = scratch[like.device().index()];
-  const int64_t need = wh::gbdt_softmax_scratch((int)K);
-  if (!t.defined() || t.numel() < need)
-    t = torch::zeros({need}, like.options().dtype(torch::kFloat64));
-  return ptr<double>(t);
-}
-
-const float* softmax_args(const char* op, const Tensor& margin, const Tensor* label,
-                          const c10::optional<Tensor>& weight, int64_t* K, int64_t* n) {
-  CHECK_IN(margin, torch::kFloat32);
-  TORCH_CHECK(margin.dim() == 2 && margin.size(0) >= 1 && margin.size(0) < (1 << 23), op,
-              ": margin must be [num_class, n]");
-  *K = margin.size(0);
-  *n = margin.size(1);
-  if (label) {
-    CHECK_IN((*label), torch::kFloat32);
-    TORCH_CHECK(label->numel() == *n, op, ": label size mismatch");
-  }
-  if (weight.has_value() && weight->defined()) {
-    CHECK_IN((*weight), torch::kFloat32);
-    TORCH_CHECK(weight->numel() == *n, op, ": weight size mismatch");
-    return ptr<float>(*weight);
-  }
-  return nullptr;
-}
-}  // namespace
-
-// (gpair f32 [K, n, 2], stats f64 [K, 4] = per class {sum g, sum h, max|g|, max|h|})
-std::vector<Tensor> gbdt_gpair_softmax(const Tensor& margin, const Tensor& label,
-                                       const c10::optional<Tensor>& weight) {
-  int64_t K, n;
-  const float* wp = softmax_args("gbdt_gpair_softmax", margin, &label, weight, &K, &n);
-  c10::DeviceGuard g(margin.device());
-  auto gp = torch::empty({K, n, 2}, margin.options());
-  auto st = torch::zeros({K, 4}, margin.options().dtype(torch::kFloat64));
-  if (n > 0)
-    wh::gbdt_gpair_softmax(n, (int)K, ptr<float>(margin), ptr<float>(label), wp, ptr<float>(gp),
-                           softmax_scratch(margin, K), ptr<double>(st), cur_stream(margin));
-  return {gp, st};
-}
-
-// prob: probabilities f32 [n, K]; else arg-max class ids f32 [n]
-Tensor gbdt_softmax_out(const Tensor& margin, bool prob) {
-  int64_t K, n;
-  softmax_args("gbdt_softmax_out", margin, nullptr, c10::nullopt, &K, &n);
-  c10::DeviceGuard g(margin.device());
-  auto out = prob ? torch::empty({n, K}, margin.options()) : torch::empty({n}, margin.options());
-  wh::gbdt_softmax_out(n, (int)K, ptr<float>(margin), prob, ptr<float>(out), cur_stream(margin));
-  return out;
-}
-
-// f64 [3] = {sum w [arg-max != y], sum w (-log max(p_y, 1e-16)), sum w}
-Tensor gbdt_multi_eval(const Tensor& margin, const Tensor& label,
-                       const c10::optional<Tensor>& weight) {
-  int64_t K, n;
-  const float* wp = softmax_args("gbdt_multi_eval", margin, &label, weight, &K, &n);
-  c10::DeviceGuard g(margin.device());
-  auto out = torch::zeros({3}, margin.options().dtype(torch::kFloat64));
-  if (n > 0)
-    wh::gbdt_multi_eval(n, (int)K, ptr<float>(margin), ptr<float>(label), wp,
-                        softmax_scratch(margin, 1), ptr<double>(out), cur_stream(margin));
-  return out;
-}
-
-// {2^eg, 2^eh[, R]} (f32) from m = {max|g|, max|h|} (f32 [2], on the device)
-Tensor gbdt_qscale(const Tensor& m, double nglobal, int64_t R) {
-  CHECK_IN(m, torch::kFloat32);
-  TORCH_CHECK(m.numel() == 2 && nglobal >= 1 && R >= 0, "gbdt_qscale: bad arguments");
-  c10::DeviceGuard g(m.device());
-  auto out = torch::empty({R > 0 ? 3 : 2}, m.options());
-  wh::gbdt_qscale(ptr<float>(m), nglobal, (int)R, ptr<float>(out), cur_stream(m));
-  return out;
-}
-
-void gbdt_leaf_walk(const Tensor& B, const Tensor& feat, const Tensor& bin, const Tensor& defl,
-                    const Tensor& left, const Tensor& right, const Tensor& val,
-                    const Tensor& margin, bool lds) {
-  CHECK_IN(B, torch::kUInt8);
-  CHECK_IN(feat, torch::kInt32);
-  CHECK_IN(bin, torch::kInt32);
-  CHECK_IN(defl, torch::kUInt8);
-  CHECK_IN(left, torch::kInt32);
-  CHECK_IN(right, torch::kInt32);
-  CHECK_IN(val, torch::kFloat32);
-  CHECK_IN(margin, torch::kFloat32);
-  TORCH_CHECK(B.dim() == 2 && margin.numel() == B.size(0), "leaf_walk: B must be [n, f]");
-  const int64_t nn = feat.numel();
-  TORCH_CHECK(bin.numel() == nn && defl.numel() == nn && left.numel() == nn &&
-                  right.numel() == nn && val.numel() == nn && nn > 0,
-              "leaf_walk: tree array sizes differ");
-  c10::DeviceGuard g(B.device());
-  TORCH_CHECK(nn <= INT32_MAX, "leaf_walk: too many nodes");
-  wh::gbdt_leaf_walk(ptr<uint8_t>(B), B.size(0), (int)B.size(1), (int)nn, ptr<int32_t>(feat),
-                     ptr<int32_t>(bin), ptr<uint8_t>(defl), ptr<int32_t>(left),
-                     ptr<int32_t>(right), ptr<float>(val), ptr<float>(margin), cur_stream(B), lds);
-}
-
-void gbdt_predict(const Tensor& X, const Tensor& feat, const Tensor& thr, const Tensor& left,
-                  const Tensor& right, const Tensor& defl, const Tensor& leaf, const Tensor& margin) {
-  CHECK_IN(X, torch::kFloat32);
-  CHECK_IN(margin, torch::kFloat32);
-  c10::DeviceGuard g(X.device());
-  wh::gbdt_predict(ptr<float>(X), X.size(0), (int)X.size(1), ptr<int32_t>(feat), ptr<float>(thr),
-                   ptr<int32_t>(left), ptr<int32_t>(right), ptr<uint8_t>(defl), ptr<float>(leaf),
-                   ptr<float>(margin), cur_stream(X));
-}
-
-// ---------------------------------------------------------------- kmeans
-Tensor kmeans_pack_x(const Tensor& X) {
-  CHECK_IN(X, torch::kFloat32);
-  TORCH_CHECK(X.dim() == 2, "X must be [n, f]");
-  c10::DeviceGuard g(X.device());
-  const int64_t n = X.size(0);
-  const int f = (int)X.size(1);
-  const int ks = wh::kmeans_ks(f);
-  auto Xp = torch::empty({(n + 31) / 32 * ks * 64}, X.options());
-  wh::kmeans_pack_x(ptr<float>(X), n, f, ptr<float>(Xp), cur_stream(X));
-  return Xp;
-}
-
-Tensor kmeans_pack_c(const Tensor& C) {
-  CHECK_IN(C, torch::kFloat32);
-  TORCH_CHECK(C.dim() == 2, "C must be [k, f]");
-  c10::DeviceGuard g(C.device());
-  const int k = (int)C.size(0), f = (int)C.size(1);
-  auto Cp = torch::empty({wh::kmeans_cp_elems(k, f)}, C.options());
-  wh::kmeans_pack_c(ptr<float>(C), k, f, ptr<float>(Cp), cur_stream(C));
-  return Cp;
-}
-
-std::vector<Tensor> kmeans_assign(const Tensor& Xp, int64_t n, int64_t f, const Tensor& Cp,
-                                  int64_t k) {
-  CHECK_IN(Xp, torch::kFloat32);
-  CHECK_IN(Cp, torch::kFloat32);
-  const int ks = wh::kmeans_ks((int)f);
-  TORCH_CHECK(Xp.numel() == (n + 31) / 32 * ks * 64, "packed X size mismatch");
-  TORCH_CHECK(Cp.numel() == wh::kmeans_cp_elems((int)k, (int)f), "packed C size mismatch");
-  c10::DeviceGuard g(Xp.device());
-  auto assign = torch::empty({n}, Xp.options().dtype(torch::kInt32));
-  auto score = torch::empty({n}, Xp.options());
-  wh::kmeans_assign(ptr<float>(Xp), n, (int)f, ptr<float>(Cp), (int)k, ptr<int32_t>(assign),
-                    ptr<float>(score), cur_stream(Xp));
-  return {assign, score};
-}
-
-// split precision: X [n, f] -> (packed bf16 hi/lo fragments (uint8), row norms)
-std::vector<Tensor> kmeans_pack_x3(const Tensor& X) {
-  CHECK_IN(X, torch::kFloat32);
-  TORCH_CHECK(X.dim() == 2, "X must be [n, f]");
-  c10::DeviceGuard g(X.device());
-  const int64_t n = X.size(0);
-  const int f = (int)X.size(1);
-  TORCH_CHECK(wh::kmeans_x3_supported(f), "split-precision assign needs 1 <= f <= 128");
-  auto Xp = torch::empty({wh::kmeans_x3_xp_bytes(n, f)}, X.options().dtype(torch::kUInt8));
-  wh::kmeans_pack_x3(ptr<float>(X), n, f, Xp.data_ptr(), cur_stream(X));
-  auto xn = X.norm(2, {1}).contiguous();
-  return {Xp, xn};
-}
-
-Tensor kmeans_pack_c3(const Tensor& C) {
-  CHECK_IN(C, torch::kFloat32);
-  c10::DeviceGuard g(C.device());
-  const int k = (int)C.size(0), f = (int)C.size(1);
-  TORCH_CHECK(wh::kmeans_x3_supported(f), "split-precision assign needs 1 <= f <= 128");
-  auto Cp = torch::empty({wh::kmeans_x3_cp_bytes(k, f)}, C.options().dtype(torch::kUInt8));
-  wh::kmeans_pack_c3(ptr<float>(C), k, f, Cp.data_ptr(), cur_stream(C));
-  return Cp;
-}
-
-// returns (assign i32 [n], score f32 [n], near-tie count (device i32 [1]))
-std::vector<Tensor> kmeans_assign_x3(const Tensor& Xp, const Tensor& xnorm, const Tensor& X,
-                                     const Tensor& Cp, const Tensor& C) {
-  CHECK_IN(X, torch::kFloat32);
-  CHECK_IN(C, torch::kFloat32);
-  CHECK_IN(xnorm, torch::kFloat32);
-  CHECK_DEV(Xp);
-  CHECK_DEV(Cp);
-  c10::DeviceGuard g(X.device());
-  const int64_t n = X.size(0);
-  const int f = (int)X.size(1), k = (int)C.size(0);
-  TORCH_CHECK(C.size(1) == f && xnorm.numel() == n, "shape mismatch");
-  TORCH_CHECK(Xp.numel() == wh::kmeans_x3_xp_bytes(n, f), "packed X size mismatch");
-  TORCH_CHECK(Cp.numel() == wh::kmeans_x3_cp_bytes(k, f), "packed C size mismatch");
-  auto assign = torch::empty({n}, X.options().dtype(torch::kInt32));
-  auto score = torch::empty({n}, X.options());
-  auto amb = torch::empty({n + 1}, X.options().dtype(torch::kInt32));
-  auto ct = torch::empty({(int64_t)k * f}, X.options());
-  wh::kmeans_assign_x3(Xp.data_ptr(), ptr<float>(xnorm), ptr<float>(X), n, f, Cp.data_ptr(),
-                       ptr<float>(C), k, ptr<int32_t>(assign), ptr<float>(score),
-                       ptr<int32_t>(amb), ptr<float>(ct), cur_stream(X));
-  return {assign, score, amb.narrow(0, 0, 1)};
-}
-
-Tensor kmeans_accum(const Tensor& X, const Tensor& assign, int64_t k) {
-  CHECK_IN(X, torch::kFloat32);
-  CHECK_IN(assign, torch::kInt32);
-  c10::DeviceGuard g(X.device());
-  const int64_t n = X.size(0);
-  const int f = (int)X.size(1);
-  TORCH_CHECK(assign.numel() == n);
-  auto sums = torch::zeros({k, f + 1}, X.options());
-  // counting-sort path unless k / f are too large for it (then atomics)
-  if (n > 0) {
-    auto scratch = torch::empty({wh::kmeans_accum_scratch(n, (int)k)},
-                                X.options().dtype(torch::kUInt8));
-    if (wh::kmeans_accum_sorted(ptr<float>(X), n, f, (int)k, ptr<int32_t>(assign),
-                                ptr<float>(sums), scratch.data_ptr(), cur_stream(X)))
-      return sums;
-  }
-  wh::kmeans_accum(ptr<float>(X), n, f, ptr<int32_t>(assign), ptr<float>(sums), cur_stream(X));
-  return sums;
-}
-
-// sparse k-means (CSR rows): offset int64 [n + 1] (offset[0] == 0), col int32
-// [nnz] (all < F = Ct.size(0), checked by the caller once per dataset), val
-// float [nnz] or None (all ones), Ct [F, Kp] float (transposed centroids)
-Tensor kmeans_assign_csr(const Tensor& offset, const Tensor& col, const c10::optional<Tensor>& val,
-                         const Tensor& Ct, int64_t K) {
-  CHECK_IN(offset, torch::kInt64);
-  CHECK_IN(col, torch::kInt32);
-  CHECK_IN(Ct, torch::kFloat32);
-  const int64_t n = offset.numel() - 1;
-  TORCH_CHECK(n >= 0 && Ct.dim() == 2 && K >= 1 && Ct.size(1) >= K && Ct.size(1) % 4 == 0,
-              "kmeans_assign_csr: Ct must be [F, Kp >= K], Kp % 4 == 0");
-  const float* vp = nullptr;
-  if (val.has_value() && val->defined()) {
-    CHECK_IN((*val), torch::kFloat32);
-    TORCH_CHECK(val->numel() == col.numel(), "kmeans_assign_csr: val / col size");
-    vp = ptr<float>(*val);
-  }
-  c10::DeviceGuard g(Ct.device());
-  auto assign = torch::empty({std::max<int64_t>(n, 0)}, Ct.options().dtype(torch::kInt32));
-  wh::kmeans_assign_csr(ptr<int64_t>(offset), ptr<int32_t>(col), vp, n, ptr<float>(Ct), (int)K,
-                        (int)Ct.size(1), ptr<int32_t>(assign), cur_stream(Ct));
-  return assign;
-}
-
-Tensor kmeans_accum_csr(const Tensor& offset, const Tensor& col, const c10::optional<Tensor>& val,
-                        const Tensor& assign, int64_t K, int64_t F) {
-  CHECK_IN(offset, torch::kInt64);
-  CHECK_IN(col, torch::kInt32);
-  CHECK_IN(assign, torch::kInt32);
-  const int64_t n = offset.numel() - 1;
-  TORCH_CHECK(assign.numel() == n && K >= 1 && F >= 1, "kmeans_accum_csr: sizes");
-  const float* vp = nullptr;
-  if (val.has_value() && val->defined()) {
-    CHECK_IN((*val), torch::kFloat32);
-    vp = ptr<float>(*val);
-  }
-  c10::DeviceGuard g(col.device());
-  auto sums = torch::zeros({K, F + 1}, col.options().dtype(torch::kFloat32));
-  wh::kmeans_accum_csr(ptr<int64_t>(offset), ptr<int32_t>(col), vp, n, ptr<int32_t>(assign),
-                       (int)F, ptr<float>(sums), cur_stream(col));
-  return sums;
-}
-
-// (new C [k, f], empty-cluster count int64 [1]) from sums [k, f + 1] and C
-std::vector<Tensor> kmeans_update(const Tensor& sums, const Tensor& C) {
-  CHECK_IN(sums, torch::kFloat32);
-  CHECK_IN(C, torch::kFloat32);
-  TORCH_CHECK(C.dim() == 2 && sums.dim() == 2 && sums.size(0) == C.size(0) &&
-                  sums.size(1) == C.size(1) + 1,
-              "kmeans_update: sums must be [k, f + 1] for C [k, f]");
-  c10::DeviceGuard g(C.device());
-  auto out = torch::empty_like(C);
-  auto nempty = torch::zeros({1}, C.options().dtype(torch::kInt64));
-  wh::kmeans_update(ptr<float>(sums), ptr<float>(C), (int)C.size(0), (int)C.size(1),
-                    ptr<float>(out), reinterpret_cast<unsigned long long*>(nempty.data_ptr()),
-                    cur_stream(C));
-  return {out, nempty};
-}
-
-Tensor spmv(const Tensor& offset, const Tensor& col, const c10::optional<Tensor>& val,
-            const Tensor& x) {
-  CHECK_IN(offset, torch::kInt64);
-  CHECK_IN(col, torch::kInt32);
-  CHECK_IN(x, torch::kFloat32);
-  c10::DeviceGuard g(offset.device());
-  const int64_t nrows = offset.numel() - 1;
-  auto y = torch::empty({nrows}, x.options());
-  wh::spmv(nrows, ptr<int64_t>(offset), ptr<int32_t>(col), optptr<float>(val), ptr<float>(x),
-           ptr<float>(y), cur_stream(x));
-  return y;
-}
-
 Tensor spmv_t(const Tensor& csc_off, const Tensor& csc_row, const c10::optional<Tensor>& csc_val,
               const Tensor& p) {
   CHECK_IN(csc_off, torch::kInt64);
@@ -2612,945 +2033,6 @@ Tensor spmv_t(const Tensor& csc_off, const Tensor& csc_row, const c10::optional<
   fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(p), nullptr, nullptr,
                 nullptr, 0, p.numel(), wh::FmBwdPhase::kAll);
   return pl[0];
-}
-
-
-// ------------------------------------------------------------------ glm
-// column-start bits of a CSC with nnz entries (glm.hip), as int64 words
-Tensor glm_heads(const Tensor& csc_off, int64_t nnz) {
-  CHECK_IN(csc_off, torch::kInt64);
-  c10::DeviceGuard g(csc_off.device());
-  const int64_t words = wh::glm_heads_words(nnz);
-  auto hb = torch::empty({words}, csc_off.options());
-  wh::glm_heads(ptr<int64_t>(csc_off), csc_off.numel() - 1,
-                reinterpret_cast<uint64_t*>(hb.data_ptr<int64_t>()), words, cur_stream(csc_off));
-  return hb;
-}
-
-// rows of a linear model: mode 0 -> (None, [loss, 0]); 1 -> (pred - label,
-// [loss, sum]); 2 -> (margin, None). bias: index of the bias weight in w (or -1)
-std::vector<c10::optional<Tensor>> glm_fwd(int64_t mode, const Tensor& offset, const Tensor& gcol,
-                                           const c10::optional<Tensor>& val, const Tensor& w,
-                                           int64_t bias, double base,
-                                           const c10::optional<Tensor>& label, int64_t loss) {
-  CHECK_IN(offset, torch::kInt64);
-  CHECK_IN(gcol, torch::kInt32);
-  CHECK_IN(w, torch::kFloat32);
-  TORCH_CHECK(mode >= 0 && mode <= 3, "glm_fwd: mode 0 / 1 / 2 / 3");
-  TORCH_CHECK(bias < w.numel(), "glm_fwd: bias index out of range");
-  const int64_t nrows = offset.numel() - 1;
-  if (mode != 2) {
-    TORCH_CHECK(label.has_value() && label->defined() && label->numel() == nrows,
-                "glm_fwd: label [nrows] needed");
-    CHECK_IN((*label), torch::kFloat32);
-  }
-  if (val.has_value() && val->defined() && val->numel())
-    TORCH_CHECK(val->numel() == gcol.numel(), "glm_fwd: val must match gcol");
-  c10::DeviceGuard g(w.device());
-  c10::optional<Tensor> out, sums;
-  if (mode != 0) out = torch::empty({nrows}, w.options());
-  Tensor part;
-  if (mode != 2) {
-    sums = torch::empty({2}, w.options().dtype(torch::kFloat64));
-    part = torch::empty({std::max<int64_t>(2 * wh::glm_fwd_blocks(nrows), 2)},
-                        w.options().dtype(torch::kFloat64));
-  }
-  const float* vp = (val.has_value() && val->defined() && val->numel()) ? ptr<float>(*val) : nullptr;
-  wh::glm_fwd((int)mode, nrows, ptr<int64_t>(offset), ptr<int32_t>(gcol), vp, ptr<float>(w),
-              bias >= 0 ? ptr<float>(w) + bias : nullptr, (float)base,
-              mode != 2 ? ptr<float>(*label) : nullptr, (int)loss,
-              out.has_value() ? ptr<float>(*out) : nullptr,
-              mode != 2 ? ptr<double>(part) : nullptr,
-              sums.has_value() ? ptr<double>(*sums) : nullptr, cur_stream(w));
-  return {out, sums};
-}
-
-// (pred - label, [loss, sum]) from the margins glm_fwd mode 3 stored
-std::vector<Tensor> glm_grad_from_margin(const Tensor& margin, const Tensor& label, int64_t loss) {
-  CHECK_IN(margin, torch::kFloat32);
-  CHECK_IN(label, torch::kFloat32);
-  TORCH_CHECK(margin.numel() == label.numel(), "glm_grad_from_margin: sizes differ");
-  c10::DeviceGuard g(margin.device());
-  const int64_t n = margin.numel();
-  auto out = torch::empty({n}, margin.options());
-  auto sums = torch::empty({2}, margin.options().dtype(torch::kFloat64));
-  auto part = torch::empty({std::max<int64_t>(2 * wh::glm_fwd_blocks(n), 2)},
-                           margin.options().dtype(torch::kFloat64));
-  wh::glm_grad_from_margin(n, ptr<float>(margin), ptr<float>(label), (int)loss, ptr<float>(out),
-                           ptr<double>(part), ptr<double>(sums), cur_stream(margin));
-  return {out, sums};
-}
-
-// grad[ucol[c]] (+)= sum over column c's CSC entries of g[row] (* val);
-// grad must be zero where the columns land
-// ucol: the runs' output indices, or an EMPTY tensor for the run index itself
-void glm_xtg(const Tensor& crow, const c10::optional<Tensor>& cval, const Tensor& hb,
-             const Tensor& col0, const Tensor& ucol, const Tensor& g, Tensor& grad,
-             bool all_atomic) {
-  CHECK_IN(crow, torch::kInt32);
-  CHECK_IN(hb, torch::kInt64);
-  CHECK_IN(col0, torch::kInt32);
-  const bool has_u = ucol.numel() > 0;
-  if (has_u) CHECK_IN(ucol, torch::kInt32);
-  CHECK_IN(g, torch::kFloat32);
-  CHECK_IN(grad, torch::kFloat32);
-  const int64_t nnz = crow.numel();
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(crow.data_ptr()) & 15) == 0,
-              "glm_xtg: CSC rows must be 16-byte aligned");
-  TORCH_CHECK(hb.numel() >= wh::glm_heads_words(nnz), "glm_xtg: short column-start bits");
-  TORCH_CHECK(col0.numel() >= wh::glm_xtg_waves(nnz), "glm_xtg: short per-wave columns");
-  const float* vp = (cval.has_value() && cval->defined() && cval->numel()) ? ptr<float>(*cval) : nullptr;
-  if (vp) TORCH_CHECK(cval->numel() == nnz, "glm_xtg: val must match rows");
-  c10::DeviceGuard dg(g.device());
-  wh::glm_xtg(nnz, ptr<int32_t>(crow), vp, reinterpret_cast<const uint64_t*>(ptr<int64_t>(hb)),
-              ptr<int32_t>(col0), has_u ? ptr<int32_t>(ucol) : nullptr, ptr<float>(g),
-              ptr<float>(grad), all_atomic ? 1 : 0, cur_stream(g));
-}
-
-void glm_runs_reduce(const Tensor& coff, const Tensor& rlist, const Tensor& S, const Tensor& cgid,
-                     Tensor& grad) {
-  CHECK_IN(coff, torch::kInt64);
-  CHECK_IN(rlist, torch::kInt32);
-  CHECK_IN(S, torch::kFloat32);
-  CHECK_IN(cgid, torch::kInt32);
-  CHECK_IN(grad, torch::kFloat32);
-  TORCH_CHECK(cgid.numel() == coff.numel() - 1, "glm_runs_reduce: cgid / coff sizes");
-  c10::DeviceGuard dg(S.device());
-  wh::glm_runs_reduce(cgid.numel(), ptr<int64_t>(coff), ptr<int32_t>(rlist), ptr<float>(S),
-                      ptr<int32_t>(cgid), ptr<float>(grad), cur_stream(S));
-}
-
-// ------------------------------------------------------------- gbdt (CSR)
-Tensor gbdt_bin_csr(const Tensor& fid, const c10::optional<Tensor>& val, int64_t ncol,
-                    const Tensor& cuts, const Tensor& cut_off) {
-  CHECK_IN(fid, torch::kInt32);
-  CHECK_IN(cuts, torch::kFloat32);
-  CHECK_IN(cut_off, torch::kInt32);
-  TORCH_CHECK(cut_off.numel() == ncol + 1, "cut_off must be [ncol + 1]");
-  c10::DeviceGuard g(fid.device());
-  auto gbin = torch::empty_like(fid);
-  wh::gbdt_bin_csr(ptr<int32_t>(fid), optptr<float>(val), fid.numel(), (int)ncol, ptr<float>(cuts),
-                   ptr<int32_t>(cut_off), ptr<int32_t>(gbin), cur_stream(fid));
-  return gbin;
-}
-
-// tasks [T, 3] {slot, rbeg, rend} (device int32) -> hist double [nslot, tb, 2]
-Tensor gbdt_hist_csr(const Tensor& row_off, const Tensor& gbin, const Tensor& ridx,
-                     const Tensor& gpair, const Tensor& qscale, const Tensor& tasks,
-                     int64_t max_rows, int64_t tb, int64_t nslot) {
-  CHECK_IN(row_off, torch::kInt64);
-  CHECK_IN(gbin, torch::kInt32);
-  CHECK_IN(ridx, torch::kInt32);
-  CHECK_IN(gpair, torch::kFloat32);
-  CHECK_IN(qscale, torch::kFloat32);
-  CHECK_IN(tasks, torch::kInt32);
-  c10::DeviceGuard g(gbin.device());
-  auto hist = torch::empty({nslot, tb, 2}, gpair.options().dtype(torch::kFloat64));
-  auto hq = torch::empty({std::max<int64_t>(nslot * tb * 2, 1)}, gpair.options().dtype(torch::kInt64));
-  wh::gbdt_hist_csr(ptr<int64_t>(row_off), ptr<int32_t>(gbin), ptr<int32_t>(ridx),
-                    ptr<float>(gpair), ptr<float>(qscale), ptr<int32_t>(tasks),
-                    (int)(tasks.numel() / 3), (int)max_rows, tb, (int)nslot, ptr<int64_t>(hq),
-                    ptr<double>(hist), cur_stream(gbin));
-  return hist;
-}
-
-Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cut_off,
-                      const c10::optional<Tensor>& fvalid, double alpha, double lambda, double mcw) {
-  CHECK_IN(hist, torch::kFloat64);
-  CHECK_IN(totals, torch::kFloat64);
-  CHECK_IN(cut_off, torch::kInt32);
-  c10::DeviceGuard g(hist.device());
-  const int S = (int)hist.size(0);
-  const int F = (int)cut_off.numel() - 1;
-  auto out = torch::empty({S, 6}, hist.options());
-  auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 5, 1)}, hist.options());
-  wh::gbdt_split_csr(ptr<double>(hist), hist.size(1), ptr<double>(totals), ptr<int32_t>(cut_off),
-                     optptr<uint8_t>(fvalid), S, F, alpha, lambda, mcw, ptr<double>(cand),
-                     ptr<double>(out), cur_stream(hist));
-  return out;
-}
-
-Tensor gbdt_partition_csr(const Tensor& row_off, const Tensor& fid, const Tensor& gbin,
-                          const Tensor& cut_off, const Tensor& ridx, const Tensor& pos_node,
-                          const Tensor& node_feat, const Tensor& node_bin, const Tensor& node_defl,
-                          const Tensor& seg_beg, const Tensor& seg_end, Tensor nleft_out) {
-  CHECK_IN(row_off, torch::kInt64);
-  CHECK_IN(fid, torch::kInt32);
-  CHECK_IN(gbin, torch::kInt32);
-  CHECK_IN(ridx, torch::kInt32);
-  CHECK_IN(pos_node, torch::kInt32);
-  c10::DeviceGuard g(ridx.device());
-  auto s = cur_stream(ridx);
-  const int64_t n = ridx.numel();
-  auto left = torch::empty({n}, ridx.options());
-  wh::gbdt_goleft_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), ptr<int32_t>(gbin),
-                      ptr<int32_t>(cut_off), ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node),
-                      ptr<int32_t>(node_feat), ptr<int32_t>(node_bin), ptr<uint8_t>(node_defl),
-                      ptr<int32_t>(left), s);
-  auto lscan = torch::empty({n + 1}, ridx.options().dtype(torch::kInt64));
-  auto tmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-  wh::scan_i32(ptr<int32_t>(left), ptr<int64_t>(lscan), n, ptr<int64_t>(tmp), s);
-  auto nl = (lscan.index_select(0, seg_end.to(torch::kInt64)) -
-             lscan.index_select(0, seg_beg.to(torch::kInt64))).to(torch::kInt32);
-  nleft_out.copy_(nl);
-  auto out = torch::empty_like(ridx);
-  wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), ptr<int32_t>(node_feat),
-                   ptr<int32_t>(seg_beg), ptr<int32_t>(nleft_out), ptr<int32_t>(left),
-                   ptr<int64_t>(lscan), ptr<int32_t>(out), s);
-  return out;
-}
-
-void gbdt_predict_csr(const Tensor& row_off, const Tensor& fid, const c10::optional<Tensor>& val,
-                      const Tensor& feat, const Tensor& thr, const Tensor& left,
-                      const Tensor& right, const Tensor& defl, const Tensor& leaf,
-                      const Tensor& margin) {
-  CHECK_IN(row_off, torch::kInt64);
-  CHECK_IN(fid, torch::kInt32);
-  CHECK_IN(margin, torch::kFloat32);
-  c10::DeviceGuard g(fid.device());
-  wh::gbdt_predict_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val),
-                       row_off.numel() - 1, ptr<int32_t>(feat), ptr<float>(thr),
-                       ptr<int32_t>(left), ptr<int32_t>(right), ptr<uint8_t>(defl),
-                       ptr<float>(leaf), ptr<float>(margin), cur_stream(fid));
-}
-
-// ------------------------------------------------------------ text ingest
-// text: uint8 [nbytes] of nlines whole lines (device) -> (keys i64 [nnz],
-// label f32 [nlines], offset i64 [nlines + 1]); one host read (the key
-// count) sizes the compacted keys
-std::vector<Tensor> parse_criteo(const Tensor& text, int64_t nlines, bool train) {
-  CHECK_IN(text, torch::kUInt8);
-  c10::DeviceGuard g(text.device());
-  auto s = cur_stream(text);
-  auto o = text.options();
-  const int64_t nb = text.numel();
-  const int64_t nt = wh::text_tiles(nb);
-  auto tile_cnt = torch::empty({std::max<int64_t>(nt, 1)}, o.dtype(torch::kInt32));
-  auto tile_off = torch::empty({nt + 1}, o.dtype(torch::kInt64));
-  auto stmp = torch::empty({wh::scan_tmp_elems(std::max<int64_t>(nt, 1))}, o.dtype(torch::kInt64));
-  auto start = torch::empty({nlines + 1}, o.dtype(torch::kInt64));
-  wh::text_lines(ptr<uint8_t>(text), nb, ptr<int32_t>(tile_cnt), ptr<int64_t>(tile_off),
-                   ptr<int64_t>(stmp), ptr<int64_t>(start), s);
-  auto padded = torch::empty({std::max<int64_t>(nlines * 39, 1)}, o.dtype(torch::kInt64));
-  auto cnt = torch::empty({std::max<int64_t>(nlines, 1)}, o.dtype(torch::kInt32));
-  auto label = torch::empty({nlines}, o.dtype(torch::kFloat32));
-  wh::criteo_fields(ptr<uint8_t>(text), nb, ptr<int64_t>(start), nlines, train,
-                    reinterpret_cast<uint64_t*>(padded.data_ptr()), ptr<int32_t>(cnt),
-                    ptr<float>(label), s);
-  auto off = torch::empty({nlines + 1}, o.dtype(torch::kInt64));
-  auto stmp2 = torch::empty({wh::scan_tmp_elems(std::max<int64_t>(nlines, 1))}, o.dtype(torch::kInt64));
-  if (nlines > 0) wh::scan_i32(ptr<int32_t>(cnt), ptr<int64_t>(off), nlines, ptr<int64_t>(stmp2), s);
-  else off.zero_();
-  const int64_t nnz = off[nlines].item<int64_t>();
-  auto keys = torch::empty({nnz}, o.dtype(torch::kInt64));
-  wh::criteo_compact(reinterpret_cast<const uint64_t*>(padded.data_ptr()), ptr<int64_t>(off),
-                     nlines, reinterpret_cast<uint64_t*>(keys.data_ptr()), s);
-  return {keys, label, off};
-}
-
-// text: uint8 [nbytes] of nlines whole libsvm lines (device) -> (keys i64,
-// label f32, offset i64, value f32 or None when every value is 1, weight f32
-// or None when no line has one), as the host parser returns them
-std::vector<Tensor> parse_libsvm(const Tensor& text, int64_t nlines) {
-  CHECK_IN(text, torch::kUInt8);
-  c10::DeviceGuard g(text.device());
-  auto s = cur_stream(text);
-  auto o = text.options();
-  const int64_t nb = text.numel();
-  const int64_t nt = wh::text_tiles(nb);
-  auto tile_cnt = torch::empty({std::max<int64_t>(nt, 1)}, o.dtype(torch::kInt32));
-  auto tile_off = torch::empty({nt + 1}, o.dtype(torch::kInt64));
-  auto stmp = torch::empty({wh::scan_tmp_elems(std::max<int64_t>(std::max(nt, nlines), 1))},
-                           o.dtype(torch::kInt64));
-  auto start = torch::empty({nlines + 1}, o.dtype(torch::kInt64));
-  wh::text_lines(ptr<uint8_t>(text), nb, ptr<int32_t>(tile_cnt), ptr<int64_t>(tile_off),
-                 ptr<int64_t>(stmp), ptr<int64_t>(start), s);
-  auto cnt = torch::empty({std::max<int64_t>(nlines, 1)}, o.dtype(torch::kInt32));
-  auto off = torch::zeros({nlines + 1}, o.dtype(torch::kInt64));
-  wh::libsvm_count(ptr<uint8_t>(text), nb, ptr<int64_t>(start), nlines, ptr<int32_t>(cnt), s);
-  if (nlines > 0) wh::scan_i32(ptr<int32_t>(cnt), ptr<int64_t>(off), nlines, ptr<int64_t>(stmp), s);
-  const int64_t nnz = off[nlines].item<int64_t>();
-  auto keys = torch::empty({nnz}, o.dtype(torch::kInt64));
-  auto val = torch::empty({nnz}, o.dtype(torch::kFloat32));
-  auto label = torch::empty({nlines}, o.dtype(torch::kFloat32));
-  auto weight = torch::empty({nlines}, o.dtype(torch::kFloat32));
-  auto flags = torch::zeros({2}, o.dtype(torch::kInt32));
-  wh::libsvm_fill(ptr<uint8_t>(text), nb, ptr<int64_t>(start), nlines, ptr<int64_t>(off),
-                  reinterpret_cast<uint64_t*>(keys.data_ptr()), ptr<float>(val), ptr<float>(label),
-                  ptr<float>(weight), ptr<int32_t>(flags), s);
-  auto f = flags.cpu();
-  const int32_t* fp = f.data_ptr<int32_t>();
-  // (an undefined tensor reaches Python as None)
-  return {keys, label, off, fp[0] ? val : Tensor(), fp[1] ? weight : Tensor()};
-}
-
-// rows `sel` of a CSR block (keys, off, val?, label) -> (keys, val?, label)
-// of the gathered block whose offsets `noff` [nsel + 1] hold nnz at the end
-std::vector<Tensor> csr_gather(const Tensor& keys, const Tensor& off, const c10::optional<Tensor>& val,
-                     const Tensor& label, const Tensor& sel, const Tensor& noff, int64_t nnz) {
-  CHECK_IN(keys, torch::kInt64);
-  CHECK_IN(off, torch::kInt64);
-  CHECK_IN(label, torch::kFloat32);
-  CHECK_IN(sel, torch::kInt64);
-  CHECK_IN(noff, torch::kInt64);
-  TORCH_CHECK(noff.numel() == sel.numel() + 1 && label.numel() + 1 == off.numel());
-  if (val) {
-    CHECK_IN((*val), torch::kFloat32);
-    TORCH_CHECK(val->numel() == keys.numel());
-  }
-  c10::DeviceGuard g(keys.device());
-  auto s = cur_stream(keys);
-  auto okeys = torch::empty({nnz}, keys.options());
-  auto olabel = torch::empty({sel.numel()}, label.options());
-  Tensor oval;
-  if (val) oval = torch::empty({nnz}, val->options());
-  wh::csr_gather(ptr<int64_t>(off), reinterpret_cast<const uint64_t*>(keys.data_ptr()),
-                 val ? ptr<float>(*val) : nullptr, ptr<float>(label), ptr<int64_t>(sel),
-                 sel.numel(), ptr<int64_t>(noff), reinterpret_cast<uint64_t*>(okeys.data_ptr()),
-                 val ? ptr<float>(oval) : nullptr, ptr<float>(olabel), s);
-  return {okeys, val ? oval : Tensor(), olabel};
-}
-
-// ------------------------------------------------------------ gbdt grower
-// Depth-wise histogram tree growth with the level loop in C++ (reference:
-// xgboost hist updater driven by bin/xgboost.dmlc). Per level
-// ONE host synchronisation: the split results of this level and the
-// partition counts of the previous one come back in a single pinned copy;
-// the child row segments the histograms need are derived on the device
-// (k_child_segs), histogram tasks address them by chunk index, and the
-// sibling histograms are parent - built child in one kernel. Host tables go
-// down as one pinned upload per level. (The Python level loop it replaces
-// left the GPU idle ~60% of each tree on per-node Python work and two syncs
-// per level.)
-struct GrowParams {
-  double eta, alpha, lambda, mcw, rt_eps;
-  int max_depth;
-};
-
-class PinnedBuf {
- public:
-  template <typename T>
-  T* get(int64_t n) {
-    const int64_t bytes = std::max<int64_t>(n * (int64_t)sizeof(T), 8);
-    if (!t_.defined() || t_.numel() < bytes)
-      t_ = torch::empty({bytes * 2}, torch::TensorOptions().dtype(torch::kUInt8).pinned_memory(true));
-    return reinterpret_cast<T*>(t_.data_ptr());
-  }
-  Tensor tensor() const { return t_; }
-
- private:
-  Tensor t_;
-};
-
-// A ring of pinned staging buffers for stream-ordered uploads: a slot is
-// rewritten only after the copy that last read it has run (its event), so
-// the host never has to drain the stream to reuse staging memory.
-class PinnedRing {
- public:
-  static constexpr int N = 4;
-  ~PinnedRing() {
-    for (auto& e : ev_)
-      if (e) (void)hipEventDestroy(e);
-  }
-  template <typename T>
-  T* get(int64_t n) {
-    cur_ = (cur_ + 1) % N;
-    if (ev_[cur_]) WH_HIP_CHECK_HOST(hipEventSynchronize(ev_[cur_]));
-    return buf_[cur_].get<T>(n);
-  }
-  Tensor tensor() const { return buf_[cur_].tensor(); }
-  // after enqueuing the copy that reads the current slot
-  void mark(hipStream_t s) {
-    if (!ev_[cur_]) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&ev_[cur_], hipEventDisableTiming));
-    WH_HIP_CHECK_HOST(hipEventRecord(ev_[cur_], s));
-  }
-
- private:
-  PinnedBuf buf_[N];
-  hipEvent_t ev_[N] = {nullptr, nullptr, nullptr, nullptr};
-  int cur_ = N - 1;
-};
-
-static double l1_threshold(double g, double alpha) {
-  if (alpha <= 0) return g;
-  return g > alpha ? g - alpha : (g < -alpha ? g + alpha : 0.0);
-}
-
-py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, const Tensor& gpair,
-                    const Tensor& qscale, const Tensor& valid, int64_t nbin,
-                    std::vector<std::pair<int64_t, int64_t>> fgroups, int64_t max_fcnt,
-                    std::vector<double> root_tot, std::vector<float> cut_vals,
-                    std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
-                    double mcw, int64_t max_depth, double rt_eps, py::object allreduce) {
-  CHECK_IN(B, torch::kUInt8);
-  CHECK_IN(Bc, torch::kUInt8);
-  CHECK_IN(ridx0, torch::kInt32);
-  CHECK_IN(gpair, torch::kFloat32);
-  CHECK_IN(qscale, torch::kFloat32);
-  CHECK_DEV(valid);
-  c10::DeviceGuard g(B.device());
-  auto s = cur_stream(B);
-  const int64_t n = ridx0.numel();
-  const int F = (int)B.size(1);
-  TORCH_CHECK(n < (int64_t)INT32_MAX, "rows must fit int32");
-  const int G = (int)fgroups.size();
-  const bool dw = F % 4 == 0 && max_fcnt % 4 == 0;
-  const int64_t per = (int64_t)F * nbin * 2;
-  auto f64 = B.options().dtype(torch::kFloat64);
-  auto i32 = B.options().dtype(torch::kInt32);
-  const int chunk = (int)std::max<int64_t>(8192, (n + 1023) / 1024);
-  const bool reduce = !allreduce.is_none();
-  // host tree
-  std::vector<int> feat, bin, defl, left, right, parent;
-  std::vector<double> gain, cover, bw, leaf;
-  std::vector<std::array<double, 2>> tot;
-  auto add = [&](int par) {
-    feat.push_back(-1), bin.push_back(0), defl.push_back(0), left.push_back(-1),
-        right.push_back(-1), parent.push_back(par), gain.push_back(0), cover.push_back(0),
-        bw.push_back(0), leaf.push_back(0), tot.push_back({0, 0});
-    return (int)feat.size() - 1;
-  };
-  auto weight = [&](double G_, double H_) {
-    if (H_ < mcw) return 0.0;
-    return -l1_threshold(G_, alpha) / (H_ + lambda);
-  };
-  const int root = add(-1);
-  tot[root] = {root_tot[0], root_tot[1]};
-  std::map<int, std::pair<int, int>> seg;  // live frontier segments (node -> [b, e))
-  seg[root] = {0, (int)n};
-  std::vector<std::array<int, 3>> done;    // finished leaves: node, b, e
-  // staging rings for the uploads (node tables, task lists), a plain buffer
-  // for the one download per level (read right after its synchronisation)
-  PinnedRing up, up_tasks;
-  PinnedBuf down;
-  Tensor ridx = ridx0;
-  // histogram of the given (slot -> [b, e) device segments); tasks by chunk
-  // histogram of the given (slot -> [b, e) device segments); tasks by chunk.
-  // Prepared (task lists built and uploaded, outputs allocated) before the
-  // level's partition is enqueued, so the histogram launch follows the
-  // child segments without host work in between.
-  struct HistPlan {
-    Tensor d, hist, part;
-    int64_t nt = 0, nr = 0;
-  };
-  auto plan_hist = [&](const std::vector<int64_t>& seglen) -> HistPlan {
-    const int S = (int)seglen.size();
-    std::vector<int32_t> tasks, red;
-    for (int k = 0; k < S; ++k) {
-      const int64_t nch = std::max<int64_t>(1, (seglen[k] + chunk - 1) / chunk);
-      const int t0 = (int)(tasks.size() / 5);
-      for (int64_t c = 0; c < nch; ++c)
-        for (auto& fg : fgroups) {
-          tasks.insert(tasks.end(), {k, (int)fg.first, (int)fg.second, (int)c, chunk});
-        }
-      for (int gi = 0; gi < G; ++gi)
-        red.insert(red.end(), {k, (int)fgroups[gi].first, (int)fgroups[gi].second, t0 + gi,
-                               (int)nch, G});
-    }
-    HistPlan hp;
-    hp.nt = (int64_t)tasks.size() / 5;
-    hp.nr = (int64_t)red.size() / 6;
-    int32_t* h = up_tasks.get<int32_t>(tasks.size() + red.size());
-    std::memcpy(h, tasks.data(), tasks.size() * 4);
-    std::memcpy(h + tasks.size(), red.data(), red.size() * 4);
-    hp.d = up_tasks.tensor().narrow(0, 0, (int64_t)(tasks.size() + red.size()) * 4)
-               .to(B.device(), /*non_blocking=*/true).view(torch::kInt32);
-    up_tasks.mark(s);
-    hp.hist = torch::empty({S, F, nbin, 2}, f64);
-    hp.part = torch::empty({hp.nt * wh::gbdt_hist_pstride((int)max_fcnt, (int)nbin)},
-                           gpair.options().dtype(torch::kInt64));
-    return hp;
-  };
-  auto run_hist = [&](const HistPlan& hp, const Tensor& dseg) -> Tensor {
-    wh::gbdt_hist(ptr<uint8_t>(B), F, (int)nbin, ptr<int32_t>(ridx), ptr<float>(gpair),
-                  ptr<float>(qscale), ptr<int32_t>(hp.d), (int)hp.nt,
-                  ptr<int32_t>(hp.d) + hp.nt * 5, (int)hp.nr, (int)max_fcnt, dw,
-                  ptr<int64_t>(hp.part), ptr<double>(hp.hist), s, ptr<int32_t>(dseg), chunk,
-                  nullptr, qscale.numel() == 3);
-    // (no drain here: the staging ring waits for this copy only when its slot
-    // comes round again; the histogram allreduce is stream-ordered)
-    if (reduce) allreduce(hp.hist);
-    return hp.hist;
-  };
-  Tensor dseg_root = torch::tensor({0, (int)n}, torch::TensorOptions().dtype(torch::kInt32))
-                         .to(B.device());
-  Tensor H_front = run_hist(plan_hist({n}), dseg_root);
-  std::vector<int> frontier{root};
-  // splits whose children's segments wait for the partition counts
-  std::vector<std::array<int, 5>> pending;  // nd, l, r, b, e
-  Tensor nleft_dev;
-  for (int depth = 0; depth <= max_depth && !frontier.empty(); ++depth) {
-    const int S = (int)frontier.size();
-    const bool last = depth == max_depth;
-    Tensor split_out;
-    if (!last) {
-      double* th = up.get<double>(2 * S);
-      for (int k = 0; k < S; ++k) th[2 * k] = tot[frontier[k]][0], th[2 * k + 1] = tot[frontier[k]][1];
-      auto T = up.tensor().narrow(0, 0, 16 * S).to(B.device(), true).view(torch::kFloat64);
-      up.mark(s);
-      split_out = torch::empty({S, 6}, f64);
-      auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 4, 1)}, f64);
-      TORCH_CHECK(wh::gbdt_split(ptr<double>(H_front), ptr<double>(T),
-                                 reinterpret_cast<const uint8_t*>(valid.data_ptr()), S, F,
-                                 (int)nbin, alpha, lambda, mcw, ptr<double>(cand),
-                                 ptr<double>(split_out), s),
-                  "gbdt_split failed");
-    }
-    // the level's one synchronisation: split results + previous partition counts
-    const int64_t nl_n = nleft_dev.defined() ? nleft_dev.numel() : 0;
-    double* hdown = down.get<double>(6 * (last ? 0 : S) + nl_n / 2 + 2);
-    if (!last)
-      WH_HIP_CHECK_HOST(hipMemcpyAsync(hdown, split_out.data_ptr(), 48 * S, hipMemcpyDeviceToHost, s));
-    int32_t* nl_h = reinterpret_cast<int32_t*>(hdown + 6 * (last ? 0 : S));
-    if (nl_n)
-      WH_HIP_CHECK_HOST(hipMemcpyAsync(nl_h, nleft_dev.data_ptr(), 4 * nl_n, hipMemcpyDeviceToHost, s));
-    WH_HIP_CHECK_HOST(hipStreamSynchronize(s));
-    for (auto& pd : pending) {
-      const int m = pd[3] + nl_h[pd[0]];
-      seg[pd[1]] = {pd[3], m};
-      seg[pd[2]] = {m, pd[4]};
-    }
-    pending.clear();
-    for (int nd : frontier) {
-      cover[nd] = tot[nd][1];
-      bw[nd] = weight(tot[nd][0], tot[nd][1]);
-      leaf[nd] = eta * bw[nd];
-    }
-    if (last) break;
-    std::vector<int> split_k;
-    for (int k = 0; k < S; ++k) {
-      const double* o = hdown + 6 * k;
-      if (!(o[0] > rt_eps)) continue;
-      const int nd = frontier[k];
-      const int f = (int)o[1], b = (int)o[2];
-      feat[nd] = f, bin[nd] = b, defl[nd] = (int)o[3], gain[nd] = o[0];
-      const int l = add(nd), r = add(nd);
-      left[nd] = l, right[nd] = r;
-      tot[l] = {o[4], o[5]};
-      tot[r] = {tot[nd][0] - o[4], tot[nd][1] - o[5]};
-      split_k.push_back(k);
-    }
-    if (split_k.empty()) break;
-    const int nnode = (int)feat.size();
-    const int nsplit = (int)split_k.size();
-    // segment tiling of [0, n) for the position -> node map (gaps: -1)
-    std::vector<std::pair<int, int>> tiles;  // (begin, node)
-    {
-      std::vector<std::array<int, 3>> all;
-      for (auto& kv : seg) all.push_back({kv.second.first, kv.second.second, kv.first});
-      std::sort(all.begin(), all.end());
-      int cur = 0;
-      for (auto& a : all) {
-        if (a[0] > cur) tiles.push_back({cur, -1});
-        tiles.push_back({a[0], a[2]});
-        cur = a[1];
-      }
-      if (cur < n) tiles.push_back({cur, -1});
-    }
-    const int nt = (int)tiles.size();
-    // one pinned upload: node feat / bin / seg_beg / seg_end [nnode], defl
-    // (bytes) [nnode], tiles beg / node [nt], split table [nsplit x 4], parent slots
-    const int64_t nwords = 6LL * nnode + (nnode + 3) / 4 + 2LL * nt + 5LL * nsplit;
-    int32_t* hw = up.get<int32_t>(nwords);
-    std::memset(hw, 0, nwords * 4);
-    int32_t *h_feat = hw, *h_bin = hw + nnode, *h_sb = hw + 2 * nnode, *h_se = hw + 3 * nnode;
-    uint8_t* h_defl = reinterpret_cast<uint8_t*>(hw + 4 * nnode);
-    int32_t* h_tb = hw + 4 * nnode + (nnode + 3) / 4;
-    int32_t* h_tn = h_tb + nt;
-    int32_t* h_sp = h_tn + nt;
-    int32_t* h_par = h_sp + 4 * nsplit;
-    int32_t* h_lc = h_par + nsplit;      // partition cursors (device-updated)
-    int32_t* h_rc = h_lc + nnode;
-    for (int i = 0; i < nnode; ++i) h_feat[i] = -1;
-    std::vector<int64_t> small_len(nsplit);
-    for (int q = 0; q < nsplit; ++q) {
-      const int k = split_k[q], nd = frontier[k];
-      h_feat[nd] = feat[nd], h_bin[nd] = bin[nd], h_defl[nd] = (uint8_t)defl[nd];
-      const auto sg = seg[nd];
-      h_sb[nd] = sg.first, h_se[nd] = sg.second;
-      h_lc[nd] = sg.first, h_rc[nd] = sg.second;
-      // build the child with the smaller GLOBAL hessian, derive the other
-      const int l = left[nd], r = right[nd];
-      const int build_left = tot[l][1] <= tot[r][1] ? 1 : 0;
-      h_sp[4 * q] = nd, h_sp[4 * q + 1] = sg.first, h_sp[4 * q + 2] = sg.second,
-      h_sp[4 * q + 3] = build_left;
-      h_par[q] = k;
-      small_len[q] = sg.second - sg.first;  // upper bound of the built child's rows
-    }
-    for (int i = 0; i < nt; ++i) h_tb[i] = tiles[i].first, h_tn[i] = tiles[i].second;
-    auto dw32 = up.tensor().narrow(0, 0, nwords * 4).to(B.device(), true).view(torch::kInt32);
-    up.mark(s);
-    const int32_t* d = ptr<int32_t>(dw32);
-    const int32_t *d_feat = d, *d_bin = d + nnode, *d_sb = d + 2 * nnode;
-    const uint8_t* d_defl = reinterpret_cast<const uint8_t*>(d + 4 * nnode);
-    const int32_t* d_tb = d + 4 * nnode + (nnode + 3) / 4;
-    const int32_t* d_tn = d_tb + nt;
-    const int32_t* d_sp = d_tn + nt;
-    const int32_t* d_par = d_sp + 4 * nsplit;
-    int32_t* d_lc = const_cast<int32_t*>(d_par + nsplit);
-    int32_t* d_rc = d_lc + nnode;
-    // the built children's histogram tasks, sized by the host-side bounds
-    const HistPlan hplan = plan_hist(small_len);
-    auto ridx_new = torch::empty_like(ridx);
-    nleft_dev = torch::empty({nnode}, i32);
-    if (!wh::gbdt_partition_cursor(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F,
-                                   ptr<int32_t>(ridx), n, d_tb, 1, d_tn, nt, d_feat, d_bin, d_defl,
-                                   d_lc, d_rc, d_sb, nnode, ptr<int32_t>(nleft_dev),
-                                   ptr<int32_t>(ridx_new), s)) {
-      // position -> node map, flags, scan, per-node left counts, stable scatter
-      auto pos_node = torch::empty({n}, i32);
-      wh::gbdt_seg_fill(d_tb, d_tn, nt, n, ptr<int32_t>(pos_node), s);
-      auto sb64 = dw32.narrow(0, 2 * nnode, nnode).to(torch::kInt64);
-      auto se64 = dw32.narrow(0, 3 * nnode, nnode).to(torch::kInt64);
-      auto leftf = torch::empty({n}, i32);
-      wh::gbdt_goleft(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F, ptr<int32_t>(ridx), n,
-                      ptr<int32_t>(pos_node), d_feat, d_bin, d_defl, ptr<int32_t>(leftf), s);
-      auto lscan = torch::empty({n + 1}, B.options().dtype(torch::kInt64));
-      auto stmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-      wh::scan_i32(ptr<int32_t>(leftf), ptr<int64_t>(lscan), n, ptr<int64_t>(stmp), s);
-      nleft_dev = (lscan.index_select(0, se64) - lscan.index_select(0, sb64)).to(torch::kInt32);
-      wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), d_feat, d_sb,
-                       ptr<int32_t>(nleft_dev), ptr<int32_t>(leftf), ptr<int64_t>(lscan),
-                       ptr<int32_t>(ridx_new), s);
-    }
-    ridx = ridx_new;
-    // built children's rows, from the device counts
-    auto dseg = torch::empty({2 * nsplit}, i32);
-    wh::gbdt_child_segs(d_sp, nsplit, ptr<int32_t>(nleft_dev), ptr<int32_t>(dseg), s);
-    Tensor hs = run_hist(hplan, dseg);
-    auto H_next = torch::empty({2 * nsplit, F, nbin, 2}, f64);
-    wh::gbdt_sibling(ptr<double>(H_front), ptr<double>(hs), d_sp, d_par, nsplit, per,
-                     ptr<double>(H_next), s);
-    // next frontier [l, r] per split; unsplit frontier nodes are final leaves
-    std::vector<int> nf;
-    std::vector<bool> was_split(S, false);
-    for (int q = 0; q < nsplit; ++q) {
-      const int k = split_k[q], nd = frontier[k];
-      was_split[k] = true;
-      const auto sg = seg[nd];
-      pending.push_back({nd, left[nd], right[nd], sg.first, sg.second});
-      seg.erase(nd);
-      nf.push_back(left[nd]), nf.push_back(right[nd]);
-    }
-    for (int k = 0; k < S; ++k)
-      if (!was_split[k]) {
-        const int nd = frontier[k];
-        auto it = seg.find(nd);
-        if (it != seg.end()) {
-          done.push_back({nd, it->second.first, it->second.second});
-          seg.erase(it);
-        }
-      }
-    frontier = nf;
-    H_front = H_next;
-  }
-  if (!pending.empty()) {  // (a loop that ended right after a partition)
-    std::vector<int32_t> nl(nleft_dev.numel());
-    auto hn = nleft_dev.cpu();
-    for (auto& pd : pending) {
-      const int m = pd[3] + hn.data_ptr<int32_t>()[pd[0]];
-      seg[pd[1]] = {pd[3], m};
-      seg[pd[2]] = {m, pd[4]};
-    }
-  }
-  for (auto& kv : seg) done.push_back({kv.first, kv.second.first, kv.second.second});
-  std::vector<float> cond(feat.size(), 0.f);
-  for (size_t i = 0; i < feat.size(); ++i)
-    if (feat[i] >= 0) cond[i] = cut_vals[cut_off[feat[i]] + bin[i]];
-  py::list segs;
-  for (auto& dn : done) segs.append(py::make_tuple(dn[0], dn[1], dn[2]));
-  return py::make_tuple(feat, bin, cond, defl, left, right, parent, gain, cover, bw, leaf, segs,
-                        ridx);
-}
-
-// The same tree as gbdt_grow with the level loop on the device: heap-numbered
-// nodes, the split decisions, partition set-up, child segments and the
-// histogram task lists are written by kernels (gbdt.hip k_gd_apply /
-// k_gd_children), so the host enqueues every level without waiting and reads
-// the finished tree ONCE (gbdt_grow syncs once per level: ~1.5 ms of idle
-// GPU per depth-8 tree of 11M rows). Every max_depth level is enqueued; the
-// levels below a tree's last split find no live node and do no row work but
-// the partition's pass.
-// A device grower's heap node table (host copy, float64 [2^(D+1) - 1, REC])
-// -> the tree lists, renumbered breadth-first: (feat, bin, cond, defl, left,
-// right, parent, gain, cover, base weight, leaf, [(leaf id, begin, end)])
-py::tuple gbdt_tree_from_nodes(const Tensor& hn, const std::vector<float>& cut_vals,
-                               const std::vector<int64_t>& cut_off) {
-  const int REC = wh::gbdt_node_rec();
-  TORCH_CHECK(!hn.is_cuda() && hn.scalar_type() == torch::kFloat64 && hn.is_contiguous() &&
-                  hn.dim() == 2 && hn.size(1) == REC,
-              "gbdt_tree_from_nodes: a host float64 node table");
-  const int NN = (int)hn.size(0);
-  const double* r = hn.data_ptr<double>();
-  std::vector<int> id_of(NN, -1), order;
-  for (int h = 0; h < NN; ++h)
-    if (r[(int64_t)h * REC] != 0.0) {
-      id_of[h] = (int)order.size();
-      order.push_back(h);
-    }
-  const size_t M = order.size();
-  std::vector<int> feat(M), bin(M), defl(M), left(M, -1), right(M, -1), parent(M, -1);
-  std::vector<double> gain(M), cover(M), bw(M), leaf(M);
-  std::vector<float> cond(M, 0.f);
-  py::list segs;
-  for (size_t i = 0; i < M; ++i) {
-    const int h = order[i];
-    const double* q = r + (int64_t)h * REC;
-    feat[i] = (int)q[1], bin[i] = (int)q[2], defl[i] = (int)q[3];
-    gain[i] = q[4], cover[i] = q[5], bw[i] = q[6], leaf[i] = q[7];
-    if (feat[i] >= 0) {
-      TORCH_CHECK(2 * h + 2 < NN, "gbdt_tree_from_nodes: a split at the last depth");
-      left[i] = id_of[2 * h + 1], right[i] = id_of[2 * h + 2];
-      TORCH_CHECK(left[i] >= 0 && right[i] >= 0, "gbdt_tree_from_nodes: a split node lost a child");
-      parent[left[i]] = (int)i, parent[right[i]] = (int)i;
-      cond[i] = cut_vals[cut_off[feat[i]] + bin[i]];
-    } else {
-      segs.append(py::make_tuple((int)i, (int)q[8], (int)q[9]));
-    }
-  }
-  return py::make_tuple(feat, bin, cond, defl, left, right, parent, gain, cover, bw, leaf, segs);
-}
-
-// margin += the leaf value each row reaches in a device grower's heap node
-// table (device float64 [NN, REC]): the table becomes the walk's compact
-// arrays on the device (one small kernel), then the usual row walk
-void gbdt_walk_heap(const Tensor& B, const Tensor& nodes, const Tensor& margin, bool lds) {
-  CHECK_IN(B, torch::kUInt8);
-  CHECK_IN(nodes, torch::kFloat64);
-  CHECK_IN(margin, torch::kFloat32);
-  const int REC = wh::gbdt_node_rec();
-  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == REC && nodes.size(0) > 0 &&
-                  nodes.size(0) <= 65535,
-              "gbdt_walk_heap: a heap node table");
-  TORCH_CHECK(B.dim() == 2 && margin.numel() == B.size(0), "gbdt_walk_heap: B must be [n, f]");
-  c10::DeviceGuard g(B.device());
-  const int64_t NN = nodes.size(0);
-  auto buf = torch::empty({6 * NN}, B.options().dtype(torch::kInt32));
-  int32_t* b = ptr<int32_t>(buf);
-  int32_t *feat = b, *bin = b + NN, *left = b + 2 * NN, *right = b + 3 * NN;
-  float* leaf = reinterpret_cast<float*>(b + 4 * NN);
-  uint8_t* defl = reinterpret_cast<uint8_t*>(b + 5 * NN);
-  auto s = cur_stream(B);
-  wh::gbdt_heap_tree(ptr<double>(nodes), (int)NN, feat, bin, defl, left, right, leaf, s);
-  wh::gbdt_leaf_walk(ptr<uint8_t>(B), B.size(0), (int)B.size(1), (int)NN, feat, bin, defl, left,
-                     right, leaf, ptr<float>(margin), s, lds);
-}
-
-py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, const Tensor& gpair,
-                        const Tensor& qscale, const Tensor& valid, int64_t nbin,
-                        std::vector<std::pair<int64_t, int64_t>> fgroups, int64_t max_fcnt,
-                        const Tensor& root_tot, std::vector<float> cut_vals,
-                        std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
-                        double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
-                        py::object reduce_scatter, py::object pick, int64_t f_lo, bool walk,
-                        bool defer) {
-  // Multi-rank: either every level's built histograms are allreduced (all
-  // features on every rank), or -- reduce_scatter / pick given
-  // (models/gbdt.py HistExchange) -- each rank receives the global sums of
-  // its feature slice [f_lo, f_lo + Fl) only, keeps the node histograms of
-  // that slice, searches its features, and the per-slot best candidates are
-  // reduced over the ranks by `pick`.
-  CHECK_IN(root_tot, torch::kFloat64);  // {sum g, sum h} stays on the device: no host wait
-  TORCH_CHECK(root_tot.numel() == 2, "gbdt_grow_dev: root totals are {sum g, sum h}");
-  CHECK_IN(B, torch::kUInt8);
-  CHECK_IN(Bc, torch::kUInt8);
-  CHECK_IN(ridx0, torch::kInt32);
-  CHECK_IN(gpair, torch::kFloat32);
-  CHECK_IN(qscale, torch::kFloat32);
-  CHECK_DEV(valid);
-  TORCH_CHECK(max_depth >= 0 && max_depth <= 10, "gbdt_grow_dev: max_depth in [0, 10]");
-  c10::DeviceGuard g(B.device());
-  auto s = cur_stream(B);
-  const int64_t n = ridx0.numel();
-  const int F = (int)B.size(1);
-  TORCH_CHECK(n < (int64_t)INT32_MAX, "rows must fit int32");
-  const int G = (int)fgroups.size();
-  const bool dw = F % 4 == 0 && max_fcnt % 4 == 0;
-  auto f64 = B.options().dtype(torch::kFloat64);
-  auto i32 = B.options().dtype(torch::kInt32);
-  auto u8 = B.options().dtype(torch::kUInt8);
-  const int chunk = (int)std::max<int64_t>(8192, (n + 1023) / 1024);
-  const bool shard = !reduce_scatter.is_none();
-  TORCH_CHECK(!shard || !pick.is_none(), "gbdt_grow_dev: reduce_scatter needs pick");
-  const bool reduce = shard || !allreduce.is_none();
-  // rank partials -> global sums: all features, or this rank's slice
-  auto reduce_hist = [&](Tensor h) -> Tensor {
-    if (!reduce) return h;
-    if (!shard) {
-      allreduce(h);
-      return h;
-    }
-    Tensor r = reduce_scatter(h).cast<Tensor>();
-    TORCH_CHECK(r.scalar_type() == torch::kFloat64 && r.is_contiguous() &&
-                    r.device() == h.device() && r.dim() == 4 && r.size(0) == h.size(0) &&
-                    r.size(1) <= F && f_lo + r.size(1) <= F,
-                "gbdt_grow_dev: reduce_scatter returned a bad slice");
-    return r;
-  };
-  const int D = (int)max_depth, NN = (2 << D) - 1, Smax = 1 << D, REC = wh::gbdt_node_rec();
-  const int64_t pstride = wh::gbdt_hist_pstride((int)max_fcnt, (int)nbin);
-  // one small upload: root segment, feature groups, slot iota, then the root
-  // histogram's task list -- the same for every tree of a model, so kept
-  // per (device, rows, depth, groups) instead of uploaded per tree
-  std::vector<int32_t> hw;
-  hw.reserve(3 + 2 * G + Smax);
-  hw.push_back(0), hw.push_back((int32_t)n), hw.push_back(1);
-  for (auto& fg : fgroups) hw.push_back((int32_t)fg.first), hw.push_back((int32_t)fg.second);
-  for (int i = 0; i < Smax; ++i) hw.push_back(i);
-  const int64_t nch_root = std::max<int64_t>(1, (n + chunk - 1) / chunk);
-  std::vector<int32_t> root_tasks;
-  {
-    std::vector<int32_t> red;
-    for (int64_t c = 0; c < nch_root; ++c)
-      for (auto& fg : fgroups)
-        root_tasks.insert(root_tasks.end(), {0, (int)fg.first, (int)fg.second, (int)c, chunk});
-    for (int gi = 0; gi < G; ++gi)
-      red.insert(red.end(), {0, (int)fgroups[gi].first, (int)fgroups[gi].second, gi, (int)nch_root, G});
-    root_tasks.insert(root_tasks.end(), red.begin(), red.end());
-  }
-  // (never destroyed: device tensors must not be freed by static teardown)
-  static auto& upload_cache = *new std::map<std::vector<int32_t>, std::pair<Tensor, Tensor>>();
-  std::vector<int32_t> ukey = hw;
-  ukey.push_back((int32_t)B.device().index());
-  ukey.push_back(D);
-  auto uit = upload_cache.find(ukey);
-  if (uit == upload_cache.end()) {
-    if (upload_cache.size() > 16) upload_cache.clear();
-    auto a = torch::from_blob(hw.data(), {(int64_t)hw.size()}, torch::kInt32).to(B.device());
-    auto b = torch::from_blob(root_tasks.data(), {(int64_t)root_tasks.size()}, torch::kInt32)
-                 .to(B.device());
-    uit = upload_cache.emplace(ukey, std::make_pair(a, b)).first;
-  }
-  auto hdev = uit->second.first;
-  const int32_t* d_root_seg = ptr<int32_t>(hdev);
-  const int32_t* d_fg = d_root_seg + 3;
-  const int32_t* d_iota = d_fg + 2 * G;
-  Tensor tot_cur = root_tot;
-  Tensor seg_cur = hdev.narrow(0, 0, 2);
-  Tensor alive_cur = hdev.narrow(0, 2, 1).view(torch::kUInt8).narrow(0, 0, 1);  // (= 1: the root)
-  auto nodes = torch::empty({NN, REC}, f64);  // every depth's apply writes all its slots' records
-  const uint8_t* vp = reinterpret_cast<const uint8_t*>(valid.data_ptr());
-  Tensor ridx = ridx0;
-  // root histogram: the host's task list over [0, n)
-  Tensor H_front;
-  {
-    const Tensor& d = uit->second.second;
-    const int64_t nt = nch_root * G;
-    H_front = torch::empty({1, F, nbin, 2}, f64);
-    auto part = torch::empty({nt * pstride}, gpair.options().dtype(torch::kInt64));
-    wh::gbdt_hist(ptr<uint8_t>(B), F, (int)nbin, ptr<int32_t>(ridx), ptr<float>(gpair),
-                  ptr<float>(qscale), ptr<int32_t>(d), (int)nt, ptr<int32_t>(d) + nt * 5, G,
-                  (int)max_fcnt, dw, ptr<int64_t>(part), ptr<double>(H_front), s,
-                  ptr<int32_t>(seg_cur), chunk, nullptr, qscale.numel() == 3);
-    H_front = reduce_hist(H_front);
-  }
-  const int Fl = (int)H_front.size(1);  // features of the node histograms kept here
-  const int64_t per = (int64_t)Fl * nbin * 2;
-  for (int d = 0; d <= D; ++d) {
-    const int S = 1 << d;
-    const bool last = d == D;
-    Tensor so;
-    if (!last) {
-      so = torch::empty({S, 6}, f64);
-      if (Fl > 0) {
-        auto cand = torch::empty({(int64_t)S * Fl * 4}, f64);
-        TORCH_CHECK(wh::gbdt_split(ptr<double>(H_front), ptr<double>(tot_cur),
-                                   vp + (int64_t)f_lo * nbin, S, Fl, (int)nbin, alpha, lambda, mcw,
-                                   ptr<double>(cand), ptr<double>(so), s),
-                    "gbdt_split failed");
-      } else {  // (more ranks than features: this rank owns none)
-        so.zero_();
-        so.select(1, 0).fill_(-std::numeric_limits<double>::infinity());
-      }
-      if (shard) {
-        so.select(1, 1).add_((double)f_lo);  // global feature ids
-        so = pick(so).cast<Tensor>().contiguous();
-        TORCH_CHECK(so.scalar_type() == torch::kFloat64 && so.size(0) == S && so.size(1) == 6,
-                    "gbdt_grow_dev: pick returned a bad candidate table");
-      }
-    }
-    auto pi = torch::empty({4 * S}, i32);  // pfeat | pbin | lcur | rcur
-    auto pb = torch::empty({3 * S}, u8);   // pdefl | split | build_left
-    Tensor tot_next = last ? Tensor() : torch::empty({2 * S, 2}, f64);
-    int32_t* pfeat = ptr<int32_t>(pi);
-    uint8_t* pdefl = ptr<uint8_t>(pb);
-    wh::gbdt_dev_apply(S, S - 1, last, last ? nullptr : ptr<double>(so), ptr<double>(tot_cur),
-                       ptr<int32_t>(seg_cur), ptr<uint8_t>(alive_cur), eta, alpha, lambda, mcw,
-                       rt_eps, ptr<double>(nodes), pfeat, pfeat + S, pdefl, pfeat + 2 * S,
-                       pfeat + 3 * S, pdefl + S, pdefl + 2 * S,
-                       last ? nullptr : ptr<double>(tot_next), nullptr, s);
-    if (last) break;
-    // walk: the caller adds the leaf values by walking the tree over each
-    // row's bins (models/gbdt.py _finish), so the level whose children are
-    // the max-depth leaves needs neither their rows partitioned nor their
-    // histograms (never split): only the children's totals (from the split
-    // search, above) and the node table (~9 % of a depth-8 tree)
-    const bool leaves_next = walk && d + 1 == D;
-    // partition of the split slots' rows on the device segment table (the
-    // segment begins read in place from seg_cur's {begin, end} pairs; the
-    // children read the left cursors: no copy, no count kernel)
-    auto ridx_new = leaves_next ? ridx : torch::empty_like(ridx);
-    if (n > 0 && !leaves_next)
-      TORCH_CHECK(wh::gbdt_partition_cursor(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F,
-                                            ptr<int32_t>(ridx), n, ptr<int32_t>(seg_cur), 2, d_iota,
-                                            S, pfeat, pfeat + S, pdefl, pfeat + 2 * S, pfeat + 3 * S,
-                                            nullptr, S, nullptr, ptr<int32_t>(ridx_new), s),
-                  "gbdt_grow_dev: partition refused the segment table");
-    ridx = ridx_new;
-    // next level's segments, the built children, their histogram tasks
-    const int64_t ub = ((n + chunk - 1) / chunk + S) * G;  // >= the tasks of the built children
-    auto seg_next = torch::empty({4 * S}, i32);
-    auto alive_next = torch::empty({2 * S}, u8);
-    auto dseg = torch::empty({2 * S}, i32);
-    auto sp = torch::empty({5 * S + 1}, i32);  // sp [S x 4] | par [S] | ntask
-    auto tasks = torch::empty({std::max<int64_t>(ub, 1) * 5}, i32);
-    auto red = torch::empty({(int64_t)S * G * 6}, i32);
-    TORCH_CHECK(wh::gbdt_dev_children(S, ptr<int32_t>(seg_cur), pdefl + S, pdefl + 2 * S,
-                                      pfeat + 2 * S, d_fg, G, chunk, ptr<int32_t>(seg_next),
-                                      ptr<uint8_t>(alive_next), ptr<int32_t>(dseg),
-                                      ptr<int32_t>(sp), ptr<int32_t>(sp) + 4 * S, ptr<int32_t>(tasks),
-                                      ptr<int32_t>(sp) + 5 * S, ptr<int32_t>(red), s),
-                "gbdt_grow_dev: too many slots");
-    if (leaves_next) {  // (leaf segments: left child empty -- unused by the walk)
-      tot_cur = tot_next;
-      seg_cur = seg_next;
-      alive_cur = alive_next;
-      continue;
-    }
-    auto part = torch::empty({std::max<int64_t>(ub, 1) * pstride}, gpair.options().dtype(torch::kInt64));
-    auto H_next = torch::empty({2 * S, Fl, nbin, 2}, f64);
-    if (!reduce) {  // one rank: the reduce writes both children (no hs, no sibling launch)
-      wh::gbdt_hist(ptr<uint8_t>(B), F, (int)nbin, ptr<int32_t>(ridx), ptr<float>(gpair),
-                    ptr<float>(qscale), ptr<int32_t>(tasks), (int)std::max<int64_t>(ub, 1),
-                    ptr<int32_t>(red), S * G, (int)max_fcnt, dw, ptr<int64_t>(part),
-                    ptr<double>(H_next), s, ptr<int32_t>(dseg), chunk, ptr<int32_t>(sp) + 5 * S,
-                    qscale.numel() == 3, ptr<double>(H_front), ptr<int32_t>(sp),
-                    ptr<int32_t>(sp) + 4 * S);
-    } else {
-      auto hs = torch::empty({S, F, nbin, 2}, f64);
-      wh::gbdt_hist(ptr<uint8_t>(B), F, (int)nbin, ptr<int32_t>(ridx), ptr<float>(gpair),
-                    ptr<float>(qscale), ptr<int32_t>(tasks), (int)std::max<int64_t>(ub, 1),
-                    ptr<int32_t>(red), S * G, (int)max_fcnt, dw, ptr<int64_t>(part),
-                    ptr<double>(hs), s, ptr<int32_t>(dseg), chunk, ptr<int32_t>(sp) + 5 * S,
-                    qscale.numel() == 3);
-      hs = reduce_hist(hs);
-      wh::gbdt_sibling(ptr<double>(H_front), ptr<double>(hs), ptr<int32_t>(sp),
-                       ptr<int32_t>(sp) + 4 * S, S, per, ptr<double>(H_next), s);
-    }
-    H_front = H_next;
-    tot_cur = tot_next;
-    seg_cur = seg_next;
-    alive_cur = alive_next;
-  }
-  // the finished tree: ONE host read, renumbered breadth-first (the host
-  // grower's creation order) -- or, defer: the device node table itself, for
-  // a heap walk on the device (gbdt_walk_heap) and a host read one tree later
-  // (gbdt_tree_from_nodes), so the host's tree bookkeeping overlaps the next
-  // tree instead of idling the GPU between trees
-  if (defer) return py::make_tuple(nodes, ridx);
-  py::tuple t = gbdt_tree_from_nodes(nodes.cpu(), cut_vals, cut_off);
-  return py::make_tuple(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11],
-                        ridx);
 }
 
 }  // namespace
@@ -3700,81 +2182,11 @@ PYBIND11_MODULE(_hip, m) {
   m.def("synth_criteo", &synth_criteo);
   m.def("gather_rows", &gather_rows);
   m.def("vstride_for", &vstride_for);
-  m.def("spmv", &spmv, py::arg("offset"), py::arg("col"), py::arg("val"), py::arg("x"));
-  m.def("gbdt_bin", &gbdt_bin);
-  m.def("gbdt_hist", &gbdt_hist, py::arg("B"), py::arg("nbin"), py::arg("ridx"), py::arg("gpair"),
-        py::arg("qscale"), py::arg("tasks"), py::arg("red"), py::arg("max_fcnt"), py::arg("hist"));
-  m.def("gbdt_partition", &gbdt_partition, py::arg("B"), py::arg("ridx"), py::arg("pos_node"),
-        py::arg("node_feat"), py::arg("node_bin"), py::arg("node_defl"), py::arg("seg_beg"),
-        py::arg("seg_end"), py::arg("nleft"), py::arg("Bc") = py::none());
-  m.def("gbdt_seg_fill", &gbdt_seg_fill);
-  m.def("gbdt_split", &gbdt_split);
-  m.def("owlqn_dir", &owlqn_dir, py::arg("g"), py::arg("w"), py::arg("l1"),
-        py::arg("out") = py::none());
-  m.def("owlqn_fix_dot", &owlqn_fix_dot);
-  m.def("owlqn_step", &owlqn_step);
-  m.def("multi_dot", &multi_dot);
-  m.def("hist_dots", &hist_dots, py::arg("H"), py::arg("probes"));
-  m.def("dir_fix_dot", &dir_fix_dot, py::arg("H"), py::arg("rows"), py::arg("coef"),
-        py::arg("steep_row"), py::arg("fix"), py::arg("n") = -1);
-  m.def("glm_heads", &glm_heads, py::arg("csc_off"), py::arg("nnz"));
-  m.def("glm_fwd", &glm_fwd, py::arg("mode"), py::arg("offset"), py::arg("gcol"), py::arg("val"),
-        py::arg("w"), py::arg("bias"), py::arg("base"), py::arg("label"), py::arg("loss"));
-  m.def("glm_xtg", &glm_xtg, py::arg("crow"), py::arg("cval"), py::arg("hb"), py::arg("col0"),
-        py::arg("ucol"), py::arg("g"), py::arg("grad"), py::arg("all_atomic") = false);
-  m.def("glm_grad_from_margin", &glm_grad_from_margin, py::arg("margin"), py::arg("label"),
-        py::arg("loss"));
-  m.def("glm_runs_reduce", &glm_runs_reduce, py::arg("coff"), py::arg("rlist"), py::arg("S"),
-        py::arg("cgid"), py::arg("grad"));
-  m.def("gbdt_leaf_add", &gbdt_leaf_add);
-  m.def("gbdt_leaf_walk", &gbdt_leaf_walk, py::arg("B"), py::arg("feat"), py::arg("bin"),
-        py::arg("defl"), py::arg("left"), py::arg("right"), py::arg("val"), py::arg("margin"),
-        py::arg("lds") = true, "margins += the tree's leaf per row (lds: the LDS-resident walk "
-        "when the tree and row tile fit; else the global-memory walk)");
-  m.def("gbdt_predict", &gbdt_predict);
-  m.def("kmeans_pack_x", &kmeans_pack_x);
-  m.def("kmeans_pack_c", &kmeans_pack_c);
-  m.def("kmeans_assign", &kmeans_assign);
-  m.def("kmeans_accum", &kmeans_accum);
-  m.def("kmeans_update", &kmeans_update);
-  m.def("kmeans_assign_csr", &kmeans_assign_csr, py::arg("offset"), py::arg("col"),
-        py::arg("val"), py::arg("Ct"), py::arg("K"));
-  m.def("kmeans_accum_csr", &kmeans_accum_csr, py::arg("offset"), py::arg("col"), py::arg("val"),
-        py::arg("assign"), py::arg("K"), py::arg("F"));
-  m.def("kmeans_pack_x3", &kmeans_pack_x3);
-  // every argument named: the Python side calls these by keyword (a dropped
-  // argument fails on the CPU signature test, tests/test_native_signatures.py)
-  m.def("gbdt_grow", &gbdt_grow, py::arg("B"), py::arg("Bc"), py::arg("ridx0"), py::arg("gpair"),
-        py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
-        py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
-        py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
-        py::arg("allreduce"));
-  m.def("gbdt_grow_dev", &gbdt_grow_dev, py::arg("B"), py::arg("Bc"), py::arg("ridx0"), py::arg("gpair"),
-        py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
-        py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
-        py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
-        py::arg("allreduce"), py::arg("reduce_scatter") = py::none(), py::arg("pick") = py::none(),
-        py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false);
-  m.def("gbdt_tree_from_nodes", &gbdt_tree_from_nodes);
-  m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
-        py::arg("lds") = true);
-  m.def("gbdt_gpair", &gbdt_gpair);
-  m.def("gbdt_gpair_softmax", &gbdt_gpair_softmax);
-  m.def("gbdt_softmax_out", &gbdt_softmax_out);
-  m.def("gbdt_multi_eval", &gbdt_multi_eval);
-  m.def("gbdt_qscale", &gbdt_qscale);
-  // the ingest ops block on one small device read each: the GIL is released
-  // so a producer thread's parsing overlaps the training loop
-  m.def("parse_criteo", &parse_criteo, py::call_guard<py::gil_scoped_release>());
-  m.def("parse_libsvm", &parse_libsvm, py::call_guard<py::gil_scoped_release>());
-  m.def("csr_gather", &csr_gather, py::call_guard<py::gil_scoped_release>());
-  m.def("gbdt_bin_csr", &gbdt_bin_csr);
-  m.def("gbdt_hist_csr", &gbdt_hist_csr);
-  m.def("gbdt_split_csr", &gbdt_split_csr);
-  m.def("gbdt_partition_csr", &gbdt_partition_csr);
-  m.def("gbdt_predict_csr", &gbdt_predict_csr);
-  m.def("kmeans_pack_c3", &kmeans_pack_c3);
-  m.def("kmeans_assign_x3", &kmeans_assign_x3);
+  // the stateless families, each from its own translation unit
+  bind_bsp(m);
+  bind_gbdt(m);
+  bind_kmeans(m);
+  bind_ingest(m);
   m.def("spmv_t", &spmv_t, py::arg("csc_off"), py::arg("csc_row"), py::arg("csc_val"),
         py::arg("p"));
   py::class_<KVStore>(m, "KVStore")

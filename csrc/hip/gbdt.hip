@@ -453,7 +453,7 @@ void gbdt_hist(const uint8_t* B, int f, int nbin, const int32_t* ridx, const flo
                        qscale, hist, ntask_dev ? nullptr : dseg, chunk, sib_hf, sib_sp, sib_par);
 }
 
-// Level bookkeeping on the device (the host tree grower, csrc/bind/gbdt_grow.cc):
+// Level bookkeeping on the device (the host tree grower, csrc/bind/gbdt_ops.cc):
 // sp[k] = {parent node, parent begin, parent end, build_left} of split k ->
 // dseg[k] = rows of the child whose histogram is built (nleft from the
 // partition, never read by the host before the next level).

@@ -18,6 +18,7 @@
 
 #include "host/auc_host.h"
 #include "host/common.h"
+#include "host/gbdt_hist_plan.h"
 #include "host/io.h"
 #include "host/json.h"
 #include "host/parsers.h"
@@ -333,9 +334,53 @@ static void test_store_guard_plan() {
   EXPECT(wh::grown_vcap(1, 0) == 1 && wh::grown_vcap(64, 64) == 64 && wh::grown_vcap(65, 64) == 128);
 }
 
+// the growers' histogram task lists (tasks x 5, red x 6) on literal vectors
+static void test_gbdt_hist_plan() {
+  using V = std::vector<int32_t>;
+  using Groups = std::vector<std::pair<int64_t, int64_t>>;
+  const Groups one{{0, 4}};
+  auto plan = [](std::vector<int64_t> seglen, const Groups& fg, int chunk) {
+    std::pair<V, V> p;
+    wh::gbdt_hist_plan(seglen, fg, chunk, &p.first, &p.second);
+    return p;
+  };
+  // one row, and an empty segment: one chunk each
+  for (int64_t len : {1, 0}) {
+    auto p = plan({len}, one, 4);
+    EXPECT((p.first == V{0, 0, 4, 0, 4}));
+    EXPECT((p.second == V{0, 0, 4, 0, 1, 1}));
+  }
+  // exactly a chunk stays one task; one row more makes two
+  {
+    auto p = plan({4}, one, 4);
+    EXPECT((p.first == V{0, 0, 4, 0, 4}));
+    EXPECT((p.second == V{0, 0, 4, 0, 1, 1}));
+    p = plan({5}, one, 4);
+    EXPECT((p.first == V{0, 0, 4, 0, 4, 0, 0, 4, 1, 4}));
+    EXPECT((p.second == V{0, 0, 4, 0, 2, 1}));
+  }
+  // two segments (3 chunks and 1) of two feature groups: chunk-major tasks,
+  // the second segment's tasks begin at t0 = 6
+  {
+    auto p = plan({9, 3}, Groups{{0, 4}, {4, 3}}, 4);
+    EXPECT((p.first == V{0, 0, 4, 0, 4, 0, 4, 3, 0, 4, 0, 0, 4, 1, 4, 0, 4, 3, 1, 4,
+                         0, 0, 4, 2, 4, 0, 4, 3, 2, 4, 1, 0, 4, 0, 4, 1, 4, 3, 0, 4}));
+    EXPECT(p.first.size() / 5 == (3 + 1) * 2);
+    EXPECT((p.second == V{0, 0, 4, 0, 3, 2, 0, 4, 3, 1, 3, 2, 1, 0, 4, 6, 1, 2, 1, 4, 3, 7, 1, 2}));
+  }
+  // the lists are appended to: t0 counts the tasks already there
+  {
+    auto p = plan({1}, one, 4);
+    wh::gbdt_hist_plan({1}, one, 4, &p.first, &p.second);
+    EXPECT((p.first == V{0, 0, 4, 0, 4, 0, 0, 4, 0, 4}));
+    EXPECT((p.second == V{0, 0, 4, 0, 1, 1, 0, 0, 4, 1, 1, 1}));
+  }
+}
+
 int main() {
   test_auc();
   test_store_guard_plan();
+  test_gbdt_hist_plan();
   test_lz4();
   test_crb();
   test_parsers();

@@ -12,6 +12,6 @@ B=$ROOT/build
   -I$ROOT/csrc $FLAGS -c "$ROOT/csrc/hip/$SRC" -o "$OUT/$SRC.o"
 OBJS=$(ls $B/hip/*.hip.o | grep -v "/$SRC.o\$")
 TL=$(python3 -c 'from torch.utils import cpp_extension as c; print(c.library_paths()[0])')
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS "$OUT/$SRC.o" $B/bind/hip_ops.cc.o -o "$OUT/_hip.so" \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS "$OUT/$SRC.o" $B/bind/*.o -o "$OUT/_hip.so" \
   -L$TL -Wl,-rpath,$TL -lc10 -ltorch -ltorch_cpu -ltorch_python -lc10_hip -ltorch_hip -lamdhip64 -lrccl
 echo "ab/$NAME/_hip.so ($SRC $FLAGS)"
