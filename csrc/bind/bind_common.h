@@ -1,8 +1,9 @@
 // What every translation unit of the binding layer (module wormhole_amd._hip)
 // needs: the torch / pybind11 / HIP includes, the tensor checks and the
-// stateless helpers, and one registration function per op family. State
-// (device workspaces, the deterministic / timing switches, the KVStore)
-// lives in hip_ops.cc only.
+// stateless helpers, the process-wide switches (deterministic, timing) and
+// one registration function per op family. State lives with its owner: the
+// localize workspace in localize_ops.cc, every other device workspace and the
+// KVStore in hip_ops.cc.
 #pragma once
 #include <torch/extension.h>
 #include <pybind11/stl.h>
@@ -11,7 +12,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstdint>
+#include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "hip/wh_kernels.h"
@@ -55,6 +59,32 @@ inline int64_t next_pow2(int64_t x) {
   while (p < x) p <<= 1;
   return p;
 }
+
+// Sub-buffers of ONE allocation (separate tensors are separate trips through
+// the allocator and dispatcher, host time of the launch-bound steps): add()
+// every piece, alloc() the uint8 block, then take typed views, which keep the
+// block alive as long as any of them is in use, or raw pointers. Pieces start
+// on 256-byte boundaries.
+class Carve {
+ public:
+  int64_t add(int64_t bytes) {
+    const int64_t o = at_;
+    at_ += (bytes + 255) / 256 * 256;
+    return o;
+  }
+  void alloc(const torch::TensorOptions& like) {
+    blk_ = torch::empty({std::max<int64_t>(at_, 256)}, like.dtype(torch::kUInt8));
+  }
+  Tensor view(int64_t off, int64_t n, torch::ScalarType dt) const {
+    return blk_.narrow(0, off, n * (int64_t)c10::elementSize(dt)).view(dt);
+  }
+  template <typename T>
+  T* at(int64_t off) const { return reinterpret_cast<T*>(static_cast<char*>(blk_.data_ptr()) + off); }
+
+ private:
+  int64_t at_ = 0;
+  Tensor blk_;
+};
 
 class PinnedBuf {
  public:
@@ -100,11 +130,51 @@ class PinnedRing {
   int cur_ = N - 1;
 };
 
+// The host's wait for a step's one device read (the localize counts, the
+// store guard's summary): polled for up to 2 ms before a blocking wait. The
+// step's next launches go out the moment the read lands instead of after a
+// sleeping wait's wake-up (A/B on one box: headline 142.8-143.4 vs
+// 140.9-143.5 M, loopback 8 123.8 / 125.7 vs 123.2 / 125.1 M; within noise
+// elsewhere: profiles/round6_small_minibatch_host.txt).
+inline void wait_event(hipEvent_t e) {
+#if !defined(WH_BLOCKING_WAIT)
+  const auto t0 = std::chrono::steady_clock::now();
+  while (true) {
+    const hipError_t r = hipEventQuery(e);
+    if (r == hipSuccess) return;
+    WH_HIP_CHECK_HOST(r == hipErrorNotReady ? hipSuccess : r);
+    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
+  }
+#endif
+  WH_HIP_CHECK_HOST(hipEventSynchronize(e));
+}
+
+// WH_DETERMINISTIC=1: bitwise-repeatable training steps: the
+// hash + stable-sort localize and ordered (atomic-free) gradient reductions
+inline bool deterministic() {
+  static int on = -1;
+  if (on < 0) {
+    const char* d = std::getenv("WH_DETERMINISTIC");
+    on = d && std::string(d) == "1";
+  }
+  return on == 1;
+}
+
+// WH_TIMING: comma-separated profiling aids (docs/build.md): step, step2,
+// loc, ingest, comm. True when `what` is one of the listed items.
+inline bool timing_on(const char* what) {
+  const char* e = std::getenv("WH_TIMING");
+  if (!e) return false;
+  const std::string v = std::string(",") + e + ",";
+  return v.find(std::string(",") + what + ",") != std::string::npos;
+}
+
 // each family's m.def calls (defined in <family>_ops.cc, called by
 // PYBIND11_MODULE in hip_ops.cc)
 void bind_gbdt(py::module_& m);
 void bind_kmeans(py::module_& m);
 void bind_bsp(py::module_& m);
 void bind_ingest(py::module_& m);
+void bind_localize(py::module_& m);
 
 }  // namespace wh_bind

@@ -1,11 +1,13 @@
 // torch / pybind11 binding layer for the gfx950 HIP kernels (module
 // wormhole_amd._hip): the module itself and everything that shares the
-// parameter-server state -- localize, KVStore, FM, the native steps, RCCL,
-// the AUC chain, quantisation. The stateless BSP families have translation
-// units of their own (gbdt_ops.cc, kmeans_ops.cc, bsp_ops.cc, ingest_ops.cc;
-// registered from PYBIND11_MODULE below). Host-only: validates tensors, sizes
-// outputs and launches on the current PyTorch HIP stream.
+// parameter-server state -- KVStore, FM, the native steps, RCCL, the AUC
+// chain, quantisation. Localize (localize_ops.cc; the steps here use its job
+// through localize_job.h) and the stateless BSP families (gbdt_ops.cc,
+// kmeans_ops.cc, bsp_ops.cc, ingest_ops.cc) have translation units of their
+// own, registered from PYBIND11_MODULE below. Host-only: validates tensors,
+// sizes outputs and launches on the current PyTorch HIP stream.
 #include "bind_common.h"
+#include "localize_job.h"
 
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPCachingAllocator.h>
@@ -38,87 +40,19 @@ using namespace wh_bind;
 
 namespace {
 
-// The host's wait for a step's one device read (the localize counts, the
-// store guard's summary): polled for up to 2 ms before a blocking wait. The
-// step's next launches go out the moment the read lands instead of after a
-// sleeping wait's wake-up (A/B on one box: headline 142.8-143.4 vs
-// 140.9-143.5 M, loopback 8 123.8 / 125.7 vs 123.2 / 125.1 M; within noise
-// elsewhere: profiles/round6_small_minibatch_host.txt).
-inline void wait_event(hipEvent_t e) {
-#if !defined(WH_BLOCKING_WAIT)
-  const auto t0 = std::chrono::steady_clock::now();
-  while (true) {
-    const hipError_t r = hipEventQuery(e);
-    if (r == hipSuccess) return;
-    WH_HIP_CHECK_HOST(r == hipErrorNotReady ? hipSuccess : r);
-    if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
-  }
-#endif
-  WH_HIP_CHECK_HOST(hipEventSynchronize(e));
-}
-
 // Per-device persistent workspaces (allocated once, zero-initialised; the
 // kernels that use them leave them in that state). Intentionally leaked: they
-// must outlive every stream-ordered use and the process exit order.
+// must outlive every stream-ordered use and the process exit order. (Localize
+// keeps a workspace of its own in localize_ops.cc.)
 struct DevWs {
   Tensor lb;          // look-back scan granules + ticket (wh_lookback.h)
   Tensor auc;         // AUC bucket counters / min-max / area / ticket
   Tensor fwd_ticket;  // arrival counter of the forward's last-block reduction
-  // localize hash tables (all ~0 between minibatches) and overflow counters
-  // (0 between minibatches), double-buffered so that minibatch i+1's insert
-  // can be enqueued before minibatch i's assign has emptied its table
-  Tensor loc_tab[2];
-  Tensor loc_ovf[2];
-  // partitioned localize: its own look-back workspace (a localize may be
-  // begun on a side stream, concurrently with other look-back users) and
-  // {per-partition publish words, arrival counter}
-  Tensor lb_loc, part_ws;
-  // heavy-id hints, double-buffered by job parity: keys [2][kPartMaxHeavy]
-  // u64, then counts [2][kPartMaxOwners] u32
-  Tensor heavy_ws;
   // the backward's scratch (wh::fm_bwd_layout bytes) per stream, grow-only:
   // reused in stream order by the next backward on the same stream (eight
   // allocations per call were ~20 us of host time, the bound of the
   // small-minibatch multi-shard step)
   std::map<hipStream_t, Tensor> bwd_scratch;
-  int heavy_parity = 0;
-  int64_t heavy_layout = -1;  // nshard * 65536 + nho of the set the last job elected
-  int part_inflight = 0;
-  // (non-zeros, unique ids) of the last finished localize: a caller's hint
-  // is the previous minibatch's unique count, scaled here by the non-zero
-  // ratio when this minibatch is larger (uneven minibatches: CRB records cut
-  // parts into short and long blocks; an unscaled hint under-sized the plan,
-  // every partition overflowed LDS and the job fell back to the hash path)
-  int64_t last_nnz = 0, last_u = -1;
-  // pinned count buffers + events of the localize jobs' one host read,
-  // reused (a pinned allocation, an event create and destroy per job were
-  // host time of the launch-bound small-minibatch step)
-  struct PinnedRead {
-    int64_t* host = nullptr;
-    int64_t cap = 0;
-    hipEvent_t ev = nullptr;
-    bool busy = false;
-  };
-  std::vector<std::unique_ptr<PinnedRead>> reads;
-  PinnedRead* acquire_read(int64_t n) {
-    for (auto& r : reads)
-      if (!r->busy && r->cap >= n) {
-        r->busy = true;
-        return r.get();
-      }
-    auto r = std::make_unique<PinnedRead>();
-    r->cap = std::max<int64_t>(n, 64);
-    void* p = nullptr;
-    WH_HIP_CHECK_HOST(hipHostMalloc(&p, r->cap * sizeof(int64_t), hipHostMallocDefault));
-    r->host = static_cast<int64_t*>(p);
-    WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&r->ev, hipEventDisableTiming));
-    r->busy = true;
-    reads.push_back(std::move(r));
-    return reads.back().get();
-  }
-  bool loc_dirty[2] = {false, false};
-  bool loc_busy[2] = {false, false};
-  int loc_next = 0;
 };
 
 DevWs& dev_ws(const torch::Device& d) {
@@ -132,13 +66,6 @@ DevWs& dev_ws(const torch::Device& d) {
     w->auc = torch::zeros({wh::auc_ws_persistent_bytes() / 8}, o.dtype(torch::kInt64));
     w->auc.select(0, wh::auc_ws_lohi_offset() / 8).fill_(-1);
     w->fwd_ticket = torch::zeros({wh::fwd_ticket_words()}, o.dtype(torch::kInt32));
-    w->lb_loc = torch::zeros({wh::lookback_ws_words()}, o.dtype(torch::kInt64));
-    w->part_ws = torch::zeros({wh::kPartMaxDigits + 2}, o.dtype(torch::kInt64));
-    w->heavy_ws = torch::zeros({2 * wh::kPartMaxHeavy + wh::kPartMaxOwners}, o.dtype(torch::kInt64));
-    for (int b = 0; b < 2; ++b) {
-      w->loc_tab[b] = torch::full({1024}, -1, o.dtype(torch::kInt64));
-      w->loc_ovf[b] = torch::zeros({1}, o.dtype(torch::kInt64));
-    }
     ws[i] = w;
   }
   return *ws[i];
@@ -162,485 +89,6 @@ Tensor scan_excl(const Tensor& in) {
     wh::scan_i64(ptr<int64_t>(in), ptr<int64_t>(o), n, ptr<int64_t>(tmp), cur_stream(in));
   }
   return o;
-}
-
-// -------------------------------------------------------------- localize
-// Returns (uniq i64[U], ucnt i32[U], owner_cnt i64[P], lid i32[nnz],
-//          csc_off i64[U+1], csc_row i32[nnz], csc_val f32[nnz|0], recv i64[2W|0])
-//
-// exchange (multi-rank): a callable that takes the device owner counts
-// i64[nshard + 1] (last = table-overflow count) and returns the device i64
-// [2W] {count from rank q, overflow flag of rank q} of a count all-to-all.
-// It runs before the one host read, so the read returns both this rank's
-// counts and its peers' (one synchronisation per minibatch instead of two).
-// Every rank sees every rank's overflow flag, so all ranks retry together.
-//
-// Two phases, so that a caller can hide the host read: begin() enqueues the
-// hash insert, the owner counts, the count exchange and an ASYNC copy of the
-// counts into pinned host memory (+ an event); finish() waits for that event
-// only, sizes the outputs and enqueues the rest. A learner begins minibatch
-// i+1 right after finishing minibatch i, so the wait overlaps i's training.
-// WH_DETERMINISTIC=1: bitwise-repeatable training steps: the
-// hash + stable-sort localize and ordered (atomic-free) gradient reductions
-bool deterministic() {
-  static int on = -1;
-  if (on < 0) {
-    const char* d = std::getenv("WH_DETERMINISTIC");
-    on = d && std::string(d) == "1";
-  }
-  return on == 1;
-}
-
-// WH_TIMING: comma-separated profiling aids (docs/build.md): step, step2,
-// loc, ingest, comm. True when `what` is one of the listed items.
-bool timing_on(const char* what) {
-  const char* e = std::getenv("WH_TIMING");
-  if (!e) return false;
-  const std::string v = std::string(",") + e + ",";
-  return v.find(std::string(",") + what + ",") != std::string::npos;
-}
-
-// WH_TIMING=loc: the partitioned dedup stores per-partition phase
-// timestamps (100 MHz) into a device buffer (loc_timing_read)
-bool loc_timing() {
-  static int on = -1;
-  if (on < 0) on = timing_on("loc") ? 1 : 0;
-  return on == 1;
-}
-Tensor& loc_timing_buf() {
-  static Tensor t;
-  if (!t.defined())
-    t = torch::zeros({4 * wh::kPartMaxDigits},
-                     torch::TensorOptions().dtype(torch::kInt64).device(torch::kCUDA));
-  return t;
-}
-
-// localize retries after a partition overflowed its LDS table (diagnostics)
-int64_t& loc_retries() {
-  static int64_t n = 0;
-  return n;
-}
-
-// The count exchange of a localize job issued from C++ (kv/psx.py's C0,
-// ported by PsxStep): returns (payload [owner_cnt (nshard+1) | stride values
-// per peer | extra], the stream the payload is ready on, stride, world).
-using NativeExchange =
-    std::function<std::tuple<Tensor, hipStream_t, int64_t, int64_t>(const Tensor&)>;
-
-class LocalizeJob {
- public:
-  // defer_exchange: enqueue the localize kernels now, but call the count
-  // exchange (and its async host read) only at exchange(): the multi-shard
-  // step begins the next minibatch's localize early on its own stream and
-  // issues its count collective later, once the payload it carries (the V
-  // row counts of this minibatch's open) exists.
-  LocalizeJob(const Tensor& keys, const Tensor& offset, const c10::optional<Tensor>& val,
-              int64_t nshard, int64_t hint, py::object exchange, bool defer_exchange = false)
-      : keys_(keys), offset_(offset), nshard_(nshard), exchange_(exchange),
-        defer_(defer_exchange) {
-    init(val, hint);
-  }
-  LocalizeJob(const Tensor& keys, const Tensor& offset, const c10::optional<Tensor>& val,
-              int64_t nshard, int64_t hint, NativeExchange nex, bool defer_exchange)
-      : keys_(keys), offset_(offset), nshard_(nshard), exchange_(py::none()), nex_(std::move(nex)),
-        defer_(defer_exchange) {
-    init(val, hint);
-  }
-
-  void init(const c10::optional<Tensor>& val, int64_t hint) {
-    const Tensor& keys = keys_;
-    const Tensor& offset = offset_;
-    const int64_t nshard = nshard_;
-    CHECK_IN(keys, torch::kInt64);
-    CHECK_IN(offset, torch::kInt64);
-    TORCH_CHECK(nshard >= 1 && nshard <= 1024, "nshard out of range");
-    nnz_ = keys.numel();
-    TORCH_CHECK(nnz_ < (int64_t)INT32_MAX, "minibatch too large for int32 local ids");
-    if (val.has_value() && val->defined() && val->numel() > 0) {
-      CHECK_IN((*val), torch::kFloat32);
-      TORCH_CHECK(val->numel() == nnz_);
-      val_ = *val;
-    }
-    {
-      DevWs& ws = dev_ws(keys.device());
-      if (hint > 0 && hint == ws.last_u && ws.last_nnz > 0 && nnz_ > ws.last_nnz)
-        hint = std::min<int64_t>(nnz_, hint * nnz_ / ws.last_nnz + 1);
-    }
-    // Table size: >= 2*nnz can never overflow; with a hint (the previous
-    // minibatch's unique count) use ~2.5x the hint instead, which keeps the
-    // scratch table small enough to stay cache resident, and fall back to the
-    // safe size if this minibatch overflowed it.
-    safe_ = next_pow2(std::max<int64_t>(2 * nnz_, 1024));
-    tsize_ = hint > 0 ? std::min(safe_, next_pow2(std::max<int64_t>(hint * 5 / 2, 1024))) : safe_;
-    c10::DeviceGuard g(keys.device());
-    // the partitioned path unless a deterministic localize is asked for (or
-    // the minibatch does not fit its plan); the hash path is the fallback
-    const int64_t uest = hint > 0 ? std::min<int64_t>(nnz_, hint * 5 / 4 + 1024) : nnz_;
-    plan_ = wh::loc_part_plan(nnz_, offset.numel() - 1, (int)nshard, uest, true);
-    part_ = plan_.ok && part_enabled();
-    if (!part_) acquire_table();
-    enqueue();
-  }
-
-  // the hash path is the deterministic one (WH_DETERMINISTIC=1)
-  static bool part_enabled() { return !deterministic(); }
-
-  ~LocalizeJob() {
-    if (rd_) {  // abandoned before its read: the copy may still be in flight
-      (void)hipEventSynchronize(rd_->ev);
-      rd_->busy = false;
-    }
-    if (counted_) dev_ws(keys_.device()).part_inflight--;
-    if (tab_ >= 0 && !done_) {
-      DevWs& ws = dev_ws(keys_.device());
-      ws.loc_busy[tab_] = false;  // abandoned: the table may hold keys
-      ws.loc_dirty[tab_] = true;
-    }
-  }
-
-  // The one host read: waits for the count exchange (retrying the whole
-  // begin at the safe table size if any rank overflowed) and returns the
-  // host (owner counts [nshard], everything the exchange appended). A
-  // caller may enqueue unrelated work between counts() and finish().
-  // the deferred count exchange (a no-op unless defer_exchange was given)
-  void exchange() {
-    TORCH_CHECK(!done_, "localize job already finished");
-    if (!defer_ || exchanged_) return;
-    c10::DeviceGuard g(keys_.device());
-    exchanged_ = true;
-    exchange_and_read(owner_cnt_, cur_stream(keys_));
-  }
-
-  std::vector<Tensor> counts() {
-    TORCH_CHECK(!done_, "localize job already finished");
-    if (owner_cnt_h_.defined()) return {owner_cnt_h_, recv_h_};
-    TORCH_CHECK(!defer_ || exchanged_, "localize: counts() before the deferred exchange()");
-    c10::DeviceGuard g(keys_.device());
-    DevWs& ws = dev_ws(keys_.device());
-    while (true) {
-      wait_event(rd_->ev);
-      const int64_t* h = rd_->host;
-      const bool own = h[nshard_] != 0;
-      bool over = own;
-      for (int64_t q = 1; q < nrecv_; q += stride_) over |= h[nshard_ + 1 + q] != 0;
-      if (!over) break;
-      if (part_) {  // a partition overflowed its LDS table (here or on a peer)
-        ++loc_retries();
-        part_ = false;
-        if (counted_) {
-          ws.part_inflight--;
-          counted_ = false;
-        }
-        acquire_table();
-        tsize_ = safe_;
-        enqueue();
-        continue;
-      }
-      TORCH_CHECK(!(own && tsize_ >= safe_), "localize: table overflow");
-      // every rank saw the same flags: all retry at the safe size together
-      ws.loc_dirty[tab_] = true;
-      tsize_ = safe_;
-      enqueue();
-    }
-    const int64_t* h = rd_->host;
-    owner_cnt_h_ = torch::empty({nshard_}, torch::kInt64);
-    for (int64_t p = 0; p < nshard_; ++p) owner_cnt_h_.data_ptr<int64_t>()[p] = h[p];
-    // everything after the owner counts (the peers' values and any extra)
-    const int64_t ntail = dev_counts_.numel() - nshard_ - 1;
-    recv_h_ = torch::empty({nrecv_ ? ntail : 0}, torch::kInt64);
-    for (int64_t q = 0; q < recv_h_.numel(); ++q)
-      recv_h_.data_ptr<int64_t>()[q] = h[nshard_ + 1 + q];
-    rd_->busy = false;  // read and copied out: back to the pool
-    rd_ = nullptr;
-    return {owner_cnt_h_, recv_h_};
-  }
-
-  // the partitioned path: every output is produced on the job's stream
-  // before the count read. (The hash path finishes on the caller's stream
-  // and returns its scratch table to the device pool from there: a job
-  // begun later on another stream must be ordered after that finish.)
-  bool partitioned() const { return part_; }
-
-  std::vector<Tensor> finish() {
-    counts();
-    c10::DeviceGuard g(keys_.device());
-    auto s = cur_stream(keys_);
-    DevWs& ws = dev_ws(keys_.device());
-    auto i32 = keys_.options().dtype(torch::kInt32);
-    auto i64 = keys_.options().dtype(torch::kInt64);
-    Tensor owner_cnt_h = owner_cnt_h_, recv_h = recv_h_;
-    int64_t U = 0;
-    for (int64_t p = 0; p < nshard_; ++p) U += owner_cnt_h.data_ptr<int64_t>()[p];
-    ws.last_nnz = nnz_;
-    ws.last_u = U;
-    if (part_) {  // everything was computed before the host read
-      done_ = true;
-      if (counted_) {
-        ws.part_inflight--;
-        counted_ = false;
-      }
-      return {uniq_.narrow(0, 0, U), ucnt_.narrow(0, 0, U), owner_cnt_h, lid_,
-              csc_off_.narrow(0, 0, U + 1), csc_row_, csc_val_, recv_h};
-    }
-    const int64_t nnz = nnz_, nrows = offset_.numel() - 1;
-    const float* vp = val_.defined() ? ptr<float>(val_) : nullptr;
-    auto tlid = torch::empty({tsize_}, i32);
-    auto uniq = torch::empty({U}, i64);
-    wh::loc_assign(reinterpret_cast<uint64_t*>(tkeys_.data_ptr()), tsize_, (int)nshard_,
-                   ptr<int64_t>(blkoff_), ptr<int32_t>(tlid),
-                   reinterpret_cast<uint64_t*>(uniq.data_ptr()), s);
-    ws.loc_dirty[tab_] = false;  // loc_assign empties the table again
-    ws.loc_busy[tab_] = false;
-    done_ = true;
-    auto row_of = torch::empty({std::max<int64_t>(nnz, 1)}, i32);
-    const int64_t n1 = std::max<int64_t>(nnz, 1);
-    auto lid = torch::empty({nnz}, i32);
-    auto work = torch::empty({3 * n1}, i32);  // pos | sorted lid | sorted pos
-    wh::loc_rows_lid(ptr<int64_t>(offset_), nrows, ptr<int32_t>(slot_of_), ptr<int32_t>(tlid),
-                     ptr<int32_t>(row_of), ptr<int32_t>(lid), vp ? ptr<int32_t>(work) : nullptr,
-                     s);
-    const size_t sbytes = wh::loc_sort_tmp_bytes(nnz, U);
-    auto stmp = torch::empty({(int64_t)sbytes + 16}, keys_.options().dtype(torch::kUInt8));
-    auto csc_off = torch::empty({U + 1}, i64);
-    auto ucnt = torch::empty({U}, i32);
-    auto csc_row = torch::empty({nnz}, i32);
-    auto csc_val = vp ? torch::empty({nnz}, keys_.options().dtype(torch::kFloat32))
-                      : torch::empty({0}, keys_.options().dtype(torch::kFloat32));
-    int32_t* wp = ptr<int32_t>(work);
-    wh::loc_csc(ptr<int32_t>(row_of), vp, nnz, U, ptr<int32_t>(lid), wp, wp + n1, wp + 2 * n1,
-                stmp.data_ptr(), sbytes, ptr<int64_t>(csc_off), ptr<int32_t>(ucnt),
-                ptr<int32_t>(csc_row), vp ? ptr<float>(csc_val) : nullptr, s);
-    return {uniq, ucnt, owner_cnt_h, lid, csc_off, csc_row, csc_val, recv_h};
-  }
-
- private:
-  void acquire_table() {
-    DevWs& ws = dev_ws(keys_.device());
-    tab_ = ws.loc_next;
-    if (ws.loc_busy[tab_]) tab_ ^= 1;
-    TORCH_CHECK(!ws.loc_busy[tab_], "localize: at most two minibatches in flight per device");
-    ws.loc_busy[tab_] = true;
-    ws.loc_next = tab_ ^ 1;
-  }
-
-  // partitioned path: every output is produced before the count read
-  Tensor enqueue_part() {
-    auto s = cur_stream(keys_);
-    DevWs& ws = dev_ws(keys_.device());
-    auto i32 = keys_.options().dtype(torch::kInt32);
-    auto i64 = keys_.options().dtype(torch::kInt64);
-    const int64_t nnz = nnz_, nrows = offset_.numel() - 1;
-    const int nsh = (int)nshard_;
-    const float* vp = val_.defined() ? ptr<float>(val_) : nullptr;
-    auto owner_cnt = torch::empty({nshard_ + 1}, i64);
-    {
-      // the job's outputs carved from ONE allocation (six separate tensors
-      // were six trips through the allocator per minibatch; the views keep
-      // the block alive as long as any of them is in use)
-      int64_t at = 0;
-      auto carve = [&](int64_t bytes) {
-        const int64_t o = at;
-        at += (bytes + 255) / 256 * 256;
-        return o;
-      };
-      const int64_t o_u = carve(nnz * 8), o_c = carve(nnz * 4), o_o = carve((nnz + 1) * 8),
-                    o_r = carve(nnz * 4), o_v = carve(vp ? nnz * 4 : 0), o_l = carve(nnz * 4);
-      auto blk = torch::empty({std::max<int64_t>(at, 256)}, keys_.options().dtype(torch::kUInt8));
-      auto view = [&](int64_t o, int64_t n, torch::ScalarType dt, int64_t esz) {
-        return blk.narrow(0, o, n * esz).view(dt);
-      };
-      uniq_ = view(o_u, nnz, torch::kInt64, 8);
-      ucnt_ = view(o_c, nnz, torch::kInt32, 4);
-      csc_off_ = view(o_o, nnz + 1, torch::kInt64, 8);
-      csc_row_ = view(o_r, nnz, torch::kInt32, 4);
-      csc_val_ = view(o_v, vp ? nnz : 0, torch::kFloat32, 4);
-      lid_ = view(o_l, nnz, torch::kInt32, 4);
-    }
-    // heavy-id hints: read the set the previous job elected, elect into the
-    // other buffer; a job begun while another is in flight uses none
-    wh::PartHeavy hv{};
-    if (plan_.nho > 0) {
-      auto* hk = reinterpret_cast<uint64_t*>(ws.heavy_ws.data_ptr());
-      auto* hc = reinterpret_cast<uint32_t*>(hk + 2 * wh::kPartMaxHeavy);
-      const int cur = ws.heavy_parity, nxt = cur ^ 1;
-      if (ws.part_inflight == 0) {
-        const int64_t layout = nshard_ * 65536 + plan_.nho;
-        hv.keys = hk + cur * wh::kPartMaxHeavy;
-        hv.cnt = hc + cur * wh::kPartMaxOwners;
-        hv.nho = ws.heavy_layout == layout ? plan_.nho : 0;  // else: elected for another layout
-        ws.heavy_layout = layout;
-        hv.next_keys = hk + nxt * wh::kPartMaxHeavy;
-        hv.next_cnt = hc + nxt * wh::kPartMaxOwners;
-        hv.nho_next = plan_.nho;
-        hv.thr = (uint32_t)std::max<int64_t>(1024, nnz / 1024);
-        ws.heavy_parity = nxt;
-      }
-    }
-    ws.part_inflight++;
-    counted_ = true;
-    // the job's temporaries in ONE allocation (eight separate tensors were
-    // eight trips through the allocator and dispatcher per minibatch: host
-    // time is the bound of the multi-shard step at 10k rows); the stream-
-    // ordered allocator keeps it safe to drop at the end of this call
-    const int64_t nh = (int64_t)plan_.ndig * plan_.ntiles;
-    const int64_t ng = wh::loc_part_groups(plan_) * plan_.ndig;
-    int64_t at = 0;
-    auto carve = [&](int64_t bytes) {
-      const int64_t o = at;
-      at += (bytes + 255) / 256 * 256;
-      return o;
-    };
-    const int64_t o_hist = carve(nh * 4), o_gsum = carve(ng * 4),
-                  o_base = carve((plan_.ndig + 1) * 8), o_pk = carve(nnz * 8), o_pr = carve(nnz * 4),
-                  o_pv = carve(vp ? nnz * 4 : 0), o_pos = carve(nnz * 4), o_plid = carve(nnz * 4);
-    auto tmp = torch::empty({std::max<int64_t>(at, 256)}, keys_.options().dtype(torch::kUInt8));
-    char* tb = static_cast<char*>(tmp.data_ptr());
-    auto* hist = reinterpret_cast<uint32_t*>(tb + o_hist);
-    auto* gsum = reinterpret_cast<uint32_t*>(tb + o_gsum);
-    auto* base = reinterpret_cast<int64_t*>(tb + o_base);
-    auto* pk = reinterpret_cast<uint64_t*>(tb + o_pk);
-    auto* pr = reinterpret_cast<int32_t*>(tb + o_pr);
-    auto* pv = vp ? reinterpret_cast<float*>(tb + o_pv) : nullptr;
-    auto* pos_of = reinterpret_cast<int32_t*>(tb + o_pos);
-    auto* plid = reinterpret_cast<int32_t*>(tb + o_plid);
-    const auto* kp = reinterpret_cast<const uint64_t*>(keys_.data_ptr());
-    wh::loc_part_hist(kp, ptr<int64_t>(offset_), nrows, nsh, plan_, hv, hist, s);
-    wh::loc_part_offsets(plan_, hist, gsum, base, s);
-    wh::loc_part_scatter(kp, vp, ptr<int64_t>(offset_), nrows, nsh, plan_, hv, base, gsum, hist, pk,
-                         pr, pv, pos_of, s);
-    auto* pw = reinterpret_cast<unsigned long long*>(ws.part_ws.data_ptr());
-    wh::loc_part_dedup(pk, pr, pv, nnz, nsh, plan_, hv, base,
-                       wh::lookback_bind(ws.lb_loc.data_ptr()),
-                       reinterpret_cast<uint64_t*>(uniq_.data_ptr()), ptr<int32_t>(ucnt_),
-                       ptr<int64_t>(csc_off_), ptr<int32_t>(csc_row_),
-                       vp ? ptr<float>(csc_val_) : nullptr, plid, pw,
-                       reinterpret_cast<unsigned int*>(pw + wh::kPartMaxDigits),
-                       ptr<int64_t>(owner_cnt), s, loc_timing() ? ptr<int64_t>(loc_timing_buf()) : nullptr);
-    wh::loc_part_lid(pos_of, plid, nnz, ptr<int32_t>(lid_), s);
-    return owner_cnt;
-  }
-
-  void enqueue() {
-    auto s = cur_stream(keys_);
-    DevWs& ws = dev_ws(keys_.device());
-    auto i32 = keys_.options().dtype(torch::kInt32);
-    auto i64 = keys_.options().dtype(torch::kInt64);
-    Tensor owner_cnt;
-    if (part_) {
-      owner_cnt = enqueue_part();
-    } else {
-      owner_cnt = enqueue_hash(ws, s, i32, i64);
-    }
-    owner_cnt_ = owner_cnt;
-    // (an overflow retry from counts() exchanges at once: every rank retries
-    // there together)
-    if (!defer_ || exchanged_) exchange_and_read(owner_cnt, s);
-  }
-
-  Tensor enqueue_hash(DevWs& ws, hipStream_t s, const torch::TensorOptions& i32,
-                      const torch::TensorOptions& i64) {
-    // The table is a persistent per-device slab that loc_assign leaves
-    // empty, so a minibatch costs no clearing pass; it is re-filled only
-    // after an overflow retry or an abandoned job (loc_dirty).
-    if (ws.loc_tab[tab_].numel() < tsize_) {
-      ws.loc_tab[tab_] = torch::full({safe_}, -1, i64);
-      ws.loc_ovf[tab_].zero_();
-      ws.loc_dirty[tab_] = false;
-    } else if (ws.loc_dirty[tab_]) {
-      ws.loc_tab[tab_].fill_(-1);
-      ws.loc_ovf[tab_].zero_();
-      ws.loc_dirty[tab_] = false;
-    }
-    tkeys_ = ws.loc_tab[tab_].narrow(0, 0, tsize_);
-    ws.loc_dirty[tab_] = true;  // until loc_assign has run
-    slot_of_ = torch::empty({std::max<int64_t>(nnz_, 1)}, i32);
-    auto owner_cnt = torch::empty({nshard_ + 1}, i64);  // [nshard] = overflow count
-    wh::loc_insert(reinterpret_cast<const uint64_t*>(keys_.data_ptr()), nnz_,
-                   reinterpret_cast<uint64_t*>(tkeys_.data_ptr()), tsize_,
-                   ptr<int32_t>(slot_of_), ptr<int64_t>(ws.loc_ovf[tab_]), s);
-    blkoff_ = torch::empty({nshard_ * wh::loc_owner_blocks(tsize_)}, i64);
-    wh::loc_owner_count(reinterpret_cast<const uint64_t*>(tkeys_.data_ptr()), tsize_,
-                        (int)nshard_, ptr<int64_t>(blkoff_), ptr<int64_t>(owner_cnt),
-                        ptr<int64_t>(ws.loc_ovf[tab_]), s);
-    return owner_cnt;
-  }
-
-  void exchange_and_read(const Tensor& owner_cnt, hipStream_t s) {
-    Tensor both = owner_cnt;
-    nrecv_ = 0;
-    hipStream_t cs = s;  // stream of the count read
-    if (nex_) {
-      auto r = nex_(owner_cnt);
-      both = std::get<0>(r);
-      cs = std::get<1>(r);
-      stride_ = std::get<2>(r);
-      const int64_t world = std::get<3>(r);
-      TORCH_CHECK(both.scalar_type() == torch::kInt64 && stride_ >= 2 &&
-                      both.numel() >= nshard_ + 1 + stride_ * world,
-                  "localize: bad native exchange payload");
-      nrecv_ = stride_ * world;
-    } else if (!exchange_.is_none()) {
-      py::object r = exchange_(owner_cnt);
-      if (py::isinstance<py::tuple>(r)) {
-        // extended protocol (kv/psx.py): (payload, stream handle, stride,
-        // world). payload = [owner_cnt (nshard+1) | stride values per peer,
-        // {count, overflow flag, ...} | extra], already on that stream;
-        // the read goes on that stream so the compute stream never waits
-        // for the exchange.
-        auto t = r.cast<py::tuple>();
-        TORCH_CHECK(t.size() == 4, "localize: extended exchange returns 4 items");
-        both = t[0].cast<Tensor>();
-        cs = reinterpret_cast<hipStream_t>(t[1].cast<intptr_t>());
-        stride_ = t[2].cast<int64_t>();
-        const int64_t world = t[3].cast<int64_t>();
-        TORCH_CHECK(both.scalar_type() == torch::kInt64 && stride_ >= 2 &&
-                        both.numel() >= nshard_ + 1 + stride_ * world,
-                    "localize: bad extended exchange payload");
-        nrecv_ = stride_ * world;
-      } else {
-        Tensor recv = r.cast<Tensor>();
-        TORCH_CHECK(recv.scalar_type() == torch::kInt64 && recv.numel() % 2 == 0,
-                    "localize: exchange must return int64 [2 * world]");
-        stride_ = 2;
-        nrecv_ = recv.numel();
-        both = torch::cat({owner_cnt, recv.reshape({-1}).to(owner_cnt.device())});
-      }
-    }
-    dev_counts_ = both.contiguous();
-    DevWs& ws = dev_ws(keys_.device());
-    if (rd_ && rd_->cap < dev_counts_.numel()) {  // (a retry: the last copy was waited for)
-      rd_->busy = false;
-      rd_ = nullptr;
-    }
-    if (!rd_) rd_ = ws.acquire_read(dev_counts_.numel());
-    // an async copy into pinned memory + an event: nothing blocks here
-    WH_HIP_CHECK_HOST(hipMemcpyAsync(rd_->host, dev_counts_.data_ptr(),
-                                     dev_counts_.numel() * sizeof(int64_t),
-                                     hipMemcpyDeviceToHost, cs));
-    WH_HIP_CHECK_HOST(hipEventRecord(rd_->ev, cs));
-  }
-
-  Tensor keys_, offset_, val_;
-  int64_t nshard_, nnz_ = 0, safe_ = 0, tsize_ = 0, nrecv_ = 0, stride_ = 2;
-  py::object exchange_;
-  NativeExchange nex_;
-  bool defer_ = false, exchanged_ = false;
-  Tensor owner_cnt_;
-  int tab_ = -1;
-  bool done_ = false;
-  Tensor tkeys_, slot_of_, blkoff_, dev_counts_, owner_cnt_h_, recv_h_;
-  Tensor uniq_, ucnt_, csc_off_, csc_row_, csc_val_, lid_;  // partitioned path outputs
-  wh::PartPlan plan_{};
-  bool part_ = false;
-  bool counted_ = false;  // in DevWs::part_inflight
-  DevWs::PinnedRead* rd_ = nullptr;  // the count read's pinned buffer + event
-};
-
-std::vector<Tensor> localize(const Tensor& keys, const Tensor& offset,
-                             const c10::optional<Tensor>& val, int64_t nshard, int64_t hint,
-                             py::object exchange) {
-  LocalizeJob job(keys, offset, val, nshard, hint, exchange);
-  return job.finish();
 }
 
 // --------------------------------------------------------------- KVStore
@@ -904,20 +352,15 @@ class KVStore {
     auto s = cur_stream(keys);
     auto i32 = keys.options().dtype(torch::kInt32);
     auto f32 = keys.options().dtype(torch::kFloat32);
-    // the open's outputs from ONE allocation (see LocalizeJob::enqueue_part)
+    // the open's outputs from ONE allocation
     const int64_t n1 = std::max<int64_t>(n, 1);
-    int64_t at = 0;
-    auto carve = [&](int64_t bytes) {
-      const int64_t o = at;
-      at += (bytes + 255) / 256 * 256;
-      return o;
-    };
-    const int64_t o_s = carve(n1 * 4), o_w = carve(n1 * 4), o_p = carve((n + 1) * 8),
-                  o_h = carve(n1);
-    auto blk = torch::empty({at}, keys.options().dtype(torch::kUInt8));
-    auto slot = blk.narrow(0, o_s, n1 * 4).view(torch::kInt32);
-    auto wout = blk.narrow(0, o_w, n1 * 4).view(torch::kFloat32);
-    auto vpos = blk.narrow(0, o_p, (n + 1) * 8).view(torch::kInt64);
+    Carve c;
+    const int64_t o_s = c.add(n1 * 4), o_w = c.add(n1 * 4), o_p = c.add((n + 1) * 8),
+                  o_h = c.add(n1);
+    c.alloc(keys.options());
+    auto slot = c.view(o_s, n1, torch::kInt32);
+    auto wout = c.view(o_w, n1, torch::kFloat32);
+    auto vpos = c.view(o_p, n + 1, torch::kInt64);
     const bool prepped = chain_in.has_value() && chain_in->defined() && chain_in->numel() > 0;
     if (prepped) {
       CHECK_IN((*chain_in), torch::kInt32);
@@ -925,7 +368,7 @@ class KVStore {
       TORCH_CHECK(vbase_.defined(), "ps_open: prepped without a push prep");
     }
     auto chain = prepped ? *chain_in : torch::empty({n1}, i32);
-    auto head = blk.narrow(0, o_h, n1);
+    auto head = c.view(o_h, n1, torch::kUInt8);
     // linear (vstride 0): the reply is w_out itself (returned in rbuf's place)
     auto rbuf = torch::empty({vstride_ > 0 ? rows_cap : 0, (int64_t)std::max(vstride_, 1)}, f32);
     // linear: no V rows, a cached all-zero vcnt (read only; no fill launch per open)
@@ -1158,20 +601,15 @@ std::vector<Tensor> fm_forward(const Tensor& offset, const Tensor& lid,
   c10::DeviceGuard g(offset.device());
   // py, dual, xv and the metric partials from ONE allocation (the views keep
   // it alive; four allocations were host time of the small-minibatch step)
-  int64_t at = 0;
-  auto carve = [&](int64_t bytes) {
-    const int64_t o = at;
-    at += (bytes + 255) / 256 * 256;
-    return o;
-  };
+  Carve c;
   const int64_t nxv = vstride > 0 ? nrows * vstride : 0;
-  const int64_t o_py = carve(nrows * 4), o_du = carve(nrows * 4), o_xv = carve(nxv * 4),
-                o_pt = carve(wh::fm_fwd_partials() * 8);
-  auto blk = torch::empty({std::max<int64_t>(at, 256)}, offset.options().dtype(torch::kUInt8));
-  auto py = blk.narrow(0, o_py, nrows * 4).view(torch::kFloat32);
-  auto dual = blk.narrow(0, o_du, nrows * 4).view(torch::kFloat32);
-  auto xv = blk.narrow(0, o_xv, nxv * 4).view(torch::kFloat32);
-  auto part = blk.narrow(0, o_pt, wh::fm_fwd_partials() * 8).view(torch::kFloat64);
+  const int64_t o_py = c.add(nrows * 4), o_du = c.add(nrows * 4), o_xv = c.add(nxv * 4),
+                o_pt = c.add(wh::fm_fwd_partials() * 8);
+  c.alloc(offset.options());
+  auto py = c.view(o_py, nrows, torch::kFloat32);
+  auto dual = c.view(o_du, nrows, torch::kFloat32);
+  auto xv = c.view(o_xv, nxv, torch::kFloat32);
+  auto part = c.view(o_pt, wh::fm_fwd_partials(), torch::kFloat64);
   // a 5th metric slot asks for the per-minibatch flipped accuracy (linear)
   const int lossf = (int)loss | (met.numel() >= 5 ? 256 : 0);
   wh::fm_forward(nrows, ptr<int64_t>(offset), ptr<int32_t>(lid), vp, ptr<float>(w_or_hdr), vcp,
@@ -2047,18 +1485,7 @@ Tensor spmv_t(const Tensor& csc_off, const Tensor& csc_row, const c10::optional<
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "wormhole_amd gfx950 HIP kernels";
   m.def("scan_excl", &scan_excl);
-  py::class_<LocalizeJob>(m, "LocalizeJob")
-      .def(py::init<const Tensor&, const Tensor&, const c10::optional<Tensor>&, int64_t, int64_t,
-                    py::object, bool>(),
-           py::arg("keys"), py::arg("offset"), py::arg("val") = py::none(), py::arg("nshard") = 1,
-           py::arg("hint") = 0, py::arg("exchange") = py::none(),
-           py::arg("defer_exchange") = false)
-      .def("exchange", &LocalizeJob::exchange)
-      .def("counts", &LocalizeJob::counts)
-      .def("finish", &LocalizeJob::finish);
-  m.def("loc_timing_read", []() { return loc_timing_buf().clone(); });
-  m.def("loc_retries", []() { return loc_retries(); },
-        "localize jobs redone on the hash path after a partition overflow (count)");
+  bind_localize(m);
   py::class_<LinearStep>(m, "LinearStep")
       .def(py::init<KVStore*, int64_t, double, double, double, double, int64_t, double, bool>(),
            py::arg("store"), py::arg("algo"), py::arg("alpha"), py::arg("beta"), py::arg("l1"),
@@ -2137,8 +1564,6 @@ PYBIND11_MODULE(_hip, m) {
       .def_property_readonly("vgrows", &DifactoStep::vgrows);
   m.def("c10d_a2a_rows", &c10d_a2a_rows, py::arg("pg"), py::arg("x"), py::arg("send_rows"),
         py::arg("recv_rows"));
-  m.def("localize", &localize, py::arg("keys"), py::arg("offset"), py::arg("val") = py::none(),
-        py::arg("nshard") = 1, py::arg("hint") = 0, py::arg("exchange") = py::none());
   m.def("fm_forward", &fm_forward);
   m.def("set_cu_reserve", [](int64_t n) { wh::fm_set_cu_reserve((int)n); },
         "CUs the persistent FM kernels leave free for concurrent collectives");

@@ -88,7 +88,8 @@ class StoreGuard {
 // ---- localize look-ahead: the NEXT minibatch's localize begins on the
 // localize stream while this one trains on the compute stream S; the next
 // call takes its outputs, or localizes on S when no job was begun for its
-// minibatch. Both streams use the device's localize workspace.
+// minibatch. Both streams use the device's localize workspace
+// (localize_ops.cc; the job's interface is localize_job.h).
 class LocalizeAhead {
  public:
   explicit LocalizeAhead(const c10::Device& device) : dev_(device.index()) {

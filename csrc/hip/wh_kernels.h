@@ -2,7 +2,7 @@
 //
 // Every launcher takes raw device pointers plus the HIP stream to enqueue on;
 // none allocates, frees or synchronises, so every call is hipGraph-capturable.
-// The torch binding layer (csrc/bind/hip_ops.cc) validates shapes/dtypes and
+// The torch binding layer (csrc/bind/*.cc) validates shapes/dtypes and
 // passes the current PyTorch HIP stream.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -541,7 +541,7 @@ void gbdt_hist(const uint8_t* B, int f, int nbin, const int32_t* ridx, const flo
 // int32 (see k_hist)
 // ntask_dev (optional): the task count of a device-built list (ntask is then
 // its upper bound; the reduce entries carry exact task counts)
-// ---- the level loop on the device (gbdt_grow_dev in csrc/bind/hip_ops.cc)
+// ---- the level loop on the device (gbdt_grow_dev in csrc/bind/gbdt_ops.cc)
 int gbdt_node_rec();
 // heap node records [nn x gbdt_node_rec()] -> the leaf walk's tree arrays
 void gbdt_heap_tree(const double* nodes, int nn, int32_t* feat, int32_t* bin, uint8_t* defl,

@@ -7,7 +7,8 @@
 // and RecordIO), the multi-threaded ordered ThreadedReader / MinibatchIter,
 // the conf parser, the WorkloadPool under concurrent workers and the
 // control-plane transport (Van) with live reader threads; and the pure
-// arithmetic of the exact AUC and of the store guard's growth plan.
+// arithmetic of the exact AUC, of the store guard's growth plan, of the
+// localize job's bookkeeping and of the GBDT histogram task lists.
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "host/gbdt_hist_plan.h"
 #include "host/io.h"
 #include "host/json.h"
+#include "host/localize_plan.h"
 #include "host/parsers.h"
 #include "host/store_guard_plan.h"
 #include "host/van.h"
@@ -377,9 +379,164 @@ static void test_gbdt_hist_plan() {
   }
 }
 
+// the localize job's bookkeeping (host/localize_plan.h) through the job
+// sequences the GPU tests rely on. A Job mirrors what LocalizeJob holds.
+static void test_localize_plan() {
+  struct Job {
+    int tab = -1;
+    bool counted = false;
+  };
+  using Pool = wh::LocTablePool;
+  // two jobs in flight and a third refused; slots alternate
+  {
+    Pool p;
+    Job a, b;
+    a.tab = p.acquire();
+    b.tab = p.acquire();
+    EXPECT(a.tab == 0 && b.tab == 1 && p.acquire() == -1);
+    EXPECT(p.prepare(a.tab, 1024, 1024) == Pool::kReady);
+    p.assigned(a.tab);
+    EXPECT(!p.busy[0] && !p.dirty[0] && p.busy[1]);
+    // `next` points at the held slot: the free one is taken instead
+    EXPECT(p.next == 0);
+    a.tab = p.acquire();
+    EXPECT(a.tab == 0 && p.next == 1 && p.acquire() == -1);
+    p.assigned(b.tab);
+    p.assigned(a.tab);
+    EXPECT(p.acquire() == 1 && p.acquire() == 0);
+  }
+  // abandon -> dirty -> refill before reuse; a clean slot needs nothing
+  {
+    Pool p;
+    int t = p.acquire();
+    EXPECT(p.prepare(t, 4096, 2048) == Pool::kReady && p.dirty[t]);
+    p.abandoned(t);
+    EXPECT(!p.busy[t] && p.dirty[t]);
+    EXPECT(p.acquire() == 1);  // the other slot first
+    p.assigned(1);
+    EXPECT(p.acquire() == t);
+    EXPECT(p.prepare(t, 4096, 2048) == Pool::kRefill);
+    p.assigned(t);
+    EXPECT(p.acquire() == 1);
+    p.assigned(1);
+    EXPECT(p.acquire() == t && p.prepare(t, 4096, 2048) == Pool::kReady);
+  }
+  // the hinted size overflows -> retry at the safe size on the same slot:
+  // a table that is too small is reallocated, a large enough one refilled
+  {
+    const int64_t nnz = 100000, hint = 1000;
+    const int64_t safe = wh::loc_safe_size(nnz), ts = wh::loc_hinted_size(hint, safe);
+    EXPECT(safe == 262144 && ts == 4096);
+    EXPECT(wh::loc_hinted_size(0, safe) == safe && wh::loc_hinted_size(safe, safe) == safe);
+    EXPECT(wh::loc_safe_size(0) == 1024 && wh::loc_hinted_size(1, 1024) == 1024);
+    Pool p;
+    const int t = p.acquire();
+    EXPECT(p.prepare(t, 1024, ts) == Pool::kRealloc);   // first use: 1024 entries
+    EXPECT(p.prepare(t, safe, safe) == Pool::kRefill);  // (realloc is to the safe size)
+    EXPECT(p.busy[t] && p.next == (t ^ 1));
+    p.assigned(t);
+    const int t2 = p.acquire(), t3 = p.acquire();
+    EXPECT(t2 == (t ^ 1) && t3 == t && p.prepare(t3, safe, ts) == Pool::kReady);
+    EXPECT(p.prepare(t3, safe, safe) == Pool::kRefill);
+  }
+  // the overflow decision: own flag at [nshard], the peers' at stride
+  {
+    const int64_t none[] = {5, 6, 0};
+    auto o = wh::loc_overflow(none, 2, 0, 2);
+    EXPECT(!o.own && !o.any);
+    const int64_t own[] = {5, 6, 3};
+    o = wh::loc_overflow(own, 2, 0, 2);
+    EXPECT(o.own && o.any);
+    // stride 3, world 2: {count, flag, extra} per peer; extras are not flags
+    const int64_t peer[] = {5, 6, 0, 7, 0, 9, 8, 1, 9};
+    o = wh::loc_overflow(peer, 2, 6, 3);
+    EXPECT(!o.own && o.any);
+    const int64_t extra[] = {5, 6, 0, 7, 0, 9, 8, 0, 9};
+    o = wh::loc_overflow(extra, 2, 6, 3);
+    EXPECT(!o.own && !o.any);
+  }
+  // a partition overflow -> fall back to the hash path: the in-flight count
+  // is released once and never goes below zero, whichever of finish, retry
+  // and destruction come, in any order
+  {
+    const int order[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    for (const auto& ord : order) {
+      wh::LocHeavyElection h;
+      Pool p;
+      Job j, other;
+      h.begin(1, 4, other.counted);
+      h.begin(1, 4, j.counted);
+      EXPECT(h.inflight == 2 && j.counted);
+      for (int step : ord) {
+        if (step == 1 && j.tab < 0) j.tab = p.acquire();  // the retry takes a table
+        h.release(j.counted);
+        EXPECT(h.inflight == 1 && !j.counted);
+      }
+      h.release(other.counted);
+      EXPECT(h.inflight == 0);
+      h.release(other.counted);
+      EXPECT(h.inflight == 0);
+    }
+  }
+  // heavy hints: the first job elects but reads none; the next reads what it
+  // elected; a layout change and a job begun while another is in flight read
+  // none, and the latter elects none and leaves parity and layout alone
+  {
+    wh::LocHeavyElection h;
+    Job a, b, c;
+    auto k = h.begin(3, 2, a.counted);
+    EXPECT(k.elect && k.read == 0 && k.write == 1 && k.nho_read == 0);
+    h.release(a.counted);
+    k = h.begin(3, 2, a.counted);
+    EXPECT(k.elect && k.read == 1 && k.write == 0 && k.nho_read == 2);
+    k = h.begin(3, 2, b.counted);  // a is in flight
+    EXPECT(!k.elect && k.nho_read == 0 && h.parity == 0 && h.inflight == 2);
+    h.release(a.counted);
+    h.release(b.counted);
+    k = h.begin(3, 2, c.counted);  // reads what a elected
+    EXPECT(k.elect && k.read == 0 && k.write == 1 && k.nho_read == 2);
+    h.release(c.counted);
+    k = h.begin(4, 2, c.counted);  // another shard count
+    EXPECT(k.elect && k.read == 1 && k.nho_read == 0 && h.layout == 4 * 65536 + 2);
+    h.release(c.counted);
+    k = h.begin(4, 3, c.counted);  // another heavy-owner count
+    EXPECT(k.elect && k.nho_read == 0);
+    h.release(c.counted);
+    k = h.begin(4, 0, c.counted);  // a plan without heavy owners: counted all the same
+    EXPECT(!k.elect && c.counted && h.inflight == 1 && h.layout == 4 * 65536 + 3);
+    h.release(c.counted);
+    k = h.begin(4, 3, c.counted);
+    EXPECT(k.elect && k.nho_read == 3);
+  }
+  // the hint sequence of uneven minibatches (rows x 8 non-zeros; the caller
+  // hints with the previous minibatch's unique count): scaled up when the
+  // minibatch grew, never below the caller's hint, never above nnz
+  {
+    wh::LocHintScale s;
+    int64_t hint = 0;
+    const int64_t rows[] = {200000, 2000, 200000, 500, 150000, 3000, 200000};
+    for (int64_t r : rows) {
+      const int64_t nnz = r * 8, prev = s.last_nnz;
+      const int64_t sc = s.scaled(hint, nnz);
+      EXPECT(sc >= hint && sc <= std::max(nnz, hint));
+      if (hint > 0 && nnz > prev) EXPECT(sc == std::min(nnz, hint * nnz / prev + 1));
+      else EXPECT(sc == hint);
+      EXPECT(wh::loc_uest(sc, nnz) <= nnz && wh::loc_uest(sc, nnz) >= std::min(sc, nnz));
+      const int64_t u = nnz / 5 + 7;  // (any unique count)
+      s.finished(nnz, u);
+      hint = u;
+    }
+    EXPECT(s.scaled(hint + 1, 1 << 30) == hint + 1);  // not the last job's count: as given
+    EXPECT(s.scaled(0, 1 << 30) == 0);
+    EXPECT(wh::loc_uest(0, 777) == 777 && wh::loc_uest(100, 5000) == 1149);
+    EXPECT(wh::loc_heavy_thr(1000) == 1024 && wh::loc_heavy_thr(4 << 20) == 4096);
+  }
+}
+
 int main() {
   test_auc();
   test_store_guard_plan();
+  test_localize_plan();
   test_gbdt_hist_plan();
   test_lz4();
   test_crb();

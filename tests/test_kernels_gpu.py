@@ -608,6 +608,34 @@ def test_localize_job_pipelined(hip):
         assert torch.equal(a[4][1:] - a[4][:-1], a[1].long())
 
 
+def test_localize_partition_fallback_then_partitioned(hip):
+    """A job whose hint undersizes its partition plan (798K distinct ids in
+    the 192 LDS tables of 4096 that hint 1 plans for; 748K still fit) is
+    redone on the hash path; the next job is partitioned again, and so is one
+    begun while it is in flight. All three are exact, and exactly one job
+    fell back."""
+    from wormhole_amd import ops
+    batches = [_rand_batch(40000, 20, 1 << 40, 0, skew=False), _rand_batch(2000, 20, 8000, 1),
+               _rand_batch(2000, 20, 8000, 2)]
+    dev = [(k.to(DEV), o.to(DEV), None) for k, o, _, _ in batches]
+    ref_out = [ops.localize(k, o, v, 3, 0) for k, o, v in dev]
+    before = hip.loc_retries()
+    outs = [ops.localize_finish(ops.localize_begin(*dev[0], 3, 1))]
+    assert hip.loc_retries() == before + 1
+    j1 = ops.localize_begin(*dev[1], 3, 0)
+    j2 = ops.localize_begin(*dev[2], 3, 0)  # begun while j1 is in flight
+    outs += [ops.localize_finish(j1), ops.localize_finish(j2)]
+    assert hip.loc_retries() == before + 1
+    for (k, o, v), a, b in zip(dev, outs, ref_out):
+        assert torch.equal(a[0][a[3].long()], k)
+        ia, ib = torch.argsort(a[0]), torch.argsort(b[0])
+        assert torch.equal(a[0][ia], b[0][ib])
+        assert torch.equal(a[1][ia], b[1][ib])
+        assert torch.equal(a[2], b[2])
+        assert int(a[4][0]) == 0 and int(a[4][-1]) == k.numel()
+        assert torch.equal((a[4][1:] - a[4][:-1])[ia], (b[4][1:] - b[4][:-1])[ib])
+
+
 def test_learner_pipelined_matches_plain(hip):
     from wormhole_amd.config.schema import DifactoConfig, Embedding
     from wormhole_amd.data.synthetic import CRITEO_TB_CARD
