@@ -2,8 +2,8 @@
 // needs: the torch / pybind11 / HIP includes, the tensor checks and the
 // stateless helpers, the process-wide switches (deterministic, timing) and
 // one registration function per op family. State lives with its owner: the
-// localize workspace in localize_ops.cc, every other device workspace and the
-// KVStore in hip_ops.cc.
+// localize workspace in localize_ops.cc, every other device workspace in
+// hip_ops.cc; the KVStore is kv_store.h.
 #pragma once
 #include <torch/extension.h>
 #include <pybind11/stl.h>
@@ -101,32 +101,53 @@ class PinnedBuf {
   Tensor t_;
 };
 
-// A ring of pinned staging buffers for stream-ordered uploads: a slot is
+// A HIP event that dies with its holder. Default-constructed it is empty: a
+// holder creates its events in its constructor's body, under its device
+// guard. Holders whose destructor synchronises the device keep their events
+// as members, which are destroyed after the destructor's body.
+class Event {
+ public:
+  Event() = default;
+  explicit Event(bool timing) { create(timing); }
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (e_) (void)hipEventDestroy(e_);
+  }
+  void create(bool timing = false) {
+    TORCH_CHECK(!e_, "Event: created twice");
+    WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e_, timing ? hipEventDefault : hipEventDisableTiming));
+  }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+// A ring of N pinned staging buffers for stream-ordered uploads: a slot is
 // rewritten only after the copy that last read it has run (its event), so
 // the host never has to drain the stream to reuse staging memory.
+template <int N>
 class PinnedRing {
  public:
-  static constexpr int N = 4;
-  ~PinnedRing() {
-    for (auto& e : ev_)
-      if (e) (void)hipEventDestroy(e);
-  }
+  // the next get() waits for the copy that last read its slot
+  bool next_used() const { return ev_[(cur_ + 1) % N] != nullptr; }
   template <typename T>
   T* get(int64_t n) {
     cur_ = (cur_ + 1) % N;
     if (ev_[cur_]) WH_HIP_CHECK_HOST(hipEventSynchronize(ev_[cur_]));
-    return buf_[cur_].get<T>(n);
+    return buf_[cur_].template get<T>(n);
   }
   Tensor tensor() const { return buf_[cur_].tensor(); }
   // after enqueuing the copy that reads the current slot
   void mark(hipStream_t s) {
-    if (!ev_[cur_]) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&ev_[cur_], hipEventDisableTiming));
+    if (!ev_[cur_]) ev_[cur_].create();
     WH_HIP_CHECK_HOST(hipEventRecord(ev_[cur_], s));
   }
 
  private:
   PinnedBuf buf_[N];
-  hipEvent_t ev_[N] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_[N];
   int cur_ = N - 1;
 };
 
@@ -176,5 +197,6 @@ void bind_kmeans(py::module_& m);
 void bind_bsp(py::module_& m);
 void bind_ingest(py::module_& m);
 void bind_localize(py::module_& m);
+void bind_psx(py::module_& m);
 
 }  // namespace wh_bind

@@ -1,5 +1,5 @@
 // The single-shard DiFacto training / evaluation step in ONE native call
-// (included by hip_ops.cc after the multi-shard step; the Python twin, kept
+// (included by hip_ops.cc after linear_step.inl; the Python twin, kept
 // as the CPU path and the test oracle, is models/difacto.py
 // DifactoLearner.process with WH_DIFACTO_NATIVE=0).
 //

@@ -494,7 +494,7 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   std::vector<std::array<int, 3>> done;    // finished leaves: node, b, e
   // staging rings for the uploads (node tables, task lists), a plain buffer
   // for the one download per level (read right after its synchronisation)
-  PinnedRing up, up_tasks;
+  PinnedRing<4> up, up_tasks;
   PinnedBuf down;
   Tensor ridx = ridx0;
   // histogram of the given (slot -> [b, e) device segments); tasks by chunk.

@@ -1,5 +1,5 @@
 // ------------------------------------------------------ native P=1 step
-// (included by hip_ops.cc after step_common.inl)
+// (included by hip_ops.cc after localize_ahead.inl)
 // The single-shard linear training step in ONE native call (reference
 // AsgdWorker::ProcessMinibatch, learn/linear/async_sgd.h:240-288, on one
 // server shard): finish this minibatch's localize (begun by the previous

@@ -1,6 +1,6 @@
-// Native driver of the pipelined multi-shard parameter-server step
-// (included by hip_ops.cc after LinearStep; the Python twin, kept as the
-// test oracle, is wormhole_amd/kv/psx.py Psx.train).
+// Native driver of the pipelined multi-shard parameter-server step (module
+// class _hip.PsxStep; the Python twin, kept as the test oracle, is
+// wormhole_amd/kv/psx.py Psx.train), its transports and RcclComm's bindings.
 //
 // Reference per-minibatch flow: learn/difacto/async_sgd.h:372-424 (push the
 // feature counts -> ZVPull(w, V) -> compute -> ZVPush(gw, gV)) and
@@ -25,38 +25,51 @@
 //               all-to-all-v, host -> device, synchronously; the multi-
 //               process correctness rehearsal of the RCCL path;
 //   kTxIdentity P virtual shards in one process, no transfer (--loopback).
+//
+// What goes on the wire -- segment tables, rows per peer, the filter's region
+// tables, the count payload's layout -- is host arithmetic of its own:
+// csrc/host/psx_plan.h.
+#include "kv_store.h"
+#include "localize_job.h"
+#include "ps_ops.h"
+#include "rccl_comm.h"
+#include "store_guard.h"
+
+#include <c10/hip/HIPCachingAllocator.h>
+#include <c10/hip/HIPGuard.h>
+#include <torch/csrc/distributed/c10d/ProcessGroup.hpp>
+#include <torch/csrc/distributed/c10d/Work.hpp>
 
 #include <condition_variable>
+#include <cstdio>
+#include <cstring>
+#include <deque>
+#include <memory>
+#include <mutex>
+#include <numeric>
 #include <thread>
 #include <unistd.h>
 
+#include "host/psx_plan.h"
+
+namespace wh_bind {
 namespace {
 
 enum PsxTx { kTxIdentity = 0, kTxRccl = 1, kTxStaged = 2 };
 
-struct PsxEv {  // a HIP event shared by an exchange and the watchdog's log
-  hipEvent_t e = nullptr;
-  explicit PsxEv(bool timing = false) {
-    WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, timing ? hipEventDefault : hipEventDisableTiming));
-  }
-  PsxEv(const PsxEv&) = delete;
-  PsxEv& operator=(const PsxEv&) = delete;
-  ~PsxEv() {
-    if (e) (void)hipEventDestroy(e);
-  }
-};
-using PsxEvP = std::shared_ptr<PsxEv>;
+using Rows = wh::PsxRows;
+using EventP = std::shared_ptr<Event>;  // shared by an exchange and the watchdog's log
 
 struct PsxWork {  // an issued exchange and the tensor it reads
   Tensor keep;
-  PsxEvP ev;  // end of the transfer on the exchange stream
+  EventP ev;  // end of the transfer on the exchange stream
   bool pending = false;
   PsxWork() = default;
   PsxWork(const PsxWork&) = delete;
   PsxWork& operator=(const PsxWork&) = delete;
   void wait() {  // the current stream waits for the transfer
     if (pending)
-      WH_HIP_CHECK_HOST(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), ev->e, 0));
+      WH_HIP_CHECK_HOST(hipStreamWaitEvent(c10::hip::getCurrentHIPStream().stream(), *ev, 0));
     pending = false;
     keep = Tensor();
   }
@@ -82,8 +95,8 @@ struct PsxXLog {
   int cls = -1;
   int64_t step = -1;
   const char* stream = "";
-  std::vector<int64_t> send, recv;
-  PsxEvP ev;  // completion on the issuing stream (null: not tracked)
+  Rows send, recv;
+  EventP ev;  // completion on the issuing stream (null: not tracked)
 };
 
 class PsxWatchdog {
@@ -140,7 +153,7 @@ class PsxWatchdog {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch())
         .count();
   }
-  static std::string rows(const std::vector<int64_t>& v) {
+  static std::string rows(const Rows& v) {
     std::string s = "[";
     for (size_t i = 0; i < v.size(); ++i) s += (i ? "," : "") + std::to_string(v[i]);
     return s + "]";
@@ -176,7 +189,7 @@ class PsxWatchdog {
     for (int64_t i = ri_ - n; i < ri_; ++i) {
       const PsxXLog& x = ring_[i % kLog];
       const char* st = "issued";
-      if (x.ev) st = hipEventQuery(x.ev->e) == hipSuccess ? "done" : "PENDING";
+      if (x.ev) st = hipEventQuery(*x.ev) == hipSuccess ? "done" : "PENDING";
       std::fprintf(stderr,
                    "[psx watchdog] rank %d:   C%d of step %lld on %s: send rows %s recv rows %s "
                    "-- %s\n",
@@ -227,33 +240,13 @@ void parse_xstall(int64_t rank, int64_t* step) {
   if (f && std::sscanf(f, "xstall:%lld:%lld", &r, &s) == 2 && r == rank) *step = s;
 }
 
-struct PsxSt {  // one minibatch in flight (kv/psx.py _Step)
-  bool train = false, use_cnt = false, have_v = false;
-  int64_t U = 0, seed_step = 0;
-  std::vector<int64_t> send, recv, Hw, Ho, vown, vrecv;
-  Tensor label, uniq, ucnt, lid, offset, val, csc_off, csc_row, csc_val;
-  Tensor tabs, segS_w, segHS_w, segS_o, segHS_o, vrecv_d;
-  Tensor keys_o, slot, vpos, chain, head, rbuf, vcnt;
-  Tensor rrecv, hdr, rows, py, dual, xv, gpush, gvc;
-  // fixed_bytes filter: the receiving side's region table (device) and float
-  // extent of C2 / C3's wire rows (q2_desc / q3_desc undefined: exact floats)
-  Tensor q2_desc, q3_desc;
-  int64_t q2_ext = 0, q3_ext = 0;
-  // C2 / C3 wait for these only: the open's and the backward's ends on S
-  // (the step's own pair from PsxStep::sev_, recorded once each)
-  hipEvent_t ev_open = nullptr, ev_grad = nullptr;
-  hipEvent_t own_open = nullptr, own_grad = nullptr;
-  PsxWork w_c1, w_c2, w_c3;
-};
-using PsxStP = std::shared_ptr<PsxSt>;
-
-int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-int64_t vsum(const std::vector<int64_t>& v) { return std::accumulate(v.begin(), v.end(), (int64_t)0); }
+int64_t vsum(const Rows& v) { return std::accumulate(v.begin(), v.end(), (int64_t)0); }
 
 // kTxStaged's host all-to-all-v: row-wise alltoall_base over a (gloo)
 // process group, exposed for a multi-rank CPU test.
-Tensor c10d_rows(const c10::intrusive_ptr<c10d::ProcessGroup>& g, const Tensor& x,
-                 const std::vector<int64_t>& send_rows, const std::vector<int64_t>& recv_rows) {
+Tensor c10d_a2a_rows(py::object pg, const Tensor& x, const Rows& send_rows,
+                     const Rows& recv_rows) {
+  auto g = pg.cast<c10::intrusive_ptr<c10d::ProcessGroup>>();
   Tensor xc = x.contiguous();
   int64_t width = 1;
   for (int64_t d = 1; d < xc.dim(); ++d) width *= xc.size(d);
@@ -269,22 +262,300 @@ Tensor c10d_rows(const c10::intrusive_ptr<c10d::ProcessGroup>& g, const Tensor& 
   return out;
 }
 
-}  // namespace
+// ------------------------------------------------------------ transport
+// The step's data plane: the transport kind with its process group or
+// communicators, and what watches every exchange go by -- the watchdog's
+// marks and log, WH_FAULT's stall, the sampled exchange timing and the wire
+// byte counters. The phases of PsxStep only name an exchange: its class, the
+// rows per peer, the stream to issue it on and the event that stream waits
+// for first.
+class PsxTransport {
+ public:
+  // pg: the gloo process group of kTxStaged; rccl: the communicator(s) of
+  // kTxRccl (P ranks, or 1 for the loopback rehearsal); step: the owner's
+  // step counter, read by marks, the log and the timing's sampling
+  void open(int64_t tx, py::object pg, py::object rccl, int64_t P, int64_t rank,
+            c10::DeviceIndex dev, const int64_t* step) {
+    P_ = P;
+    rank_ = rank;
+    step_ = step;
+    TORCH_CHECK(tx >= kTxIdentity && tx <= kTxStaged, "PsxStep: unknown transport");
+    tx_ = (PsxTx)tx;
+    if (tx_ == kTxStaged) {
+      TORCH_CHECK(!pg.is_none(), "PsxStep: the staged transport needs a process group");
+      pg_ = pg.cast<c10::intrusive_ptr<c10d::ProcessGroup>>();
+      TORCH_CHECK(pg_->getSize() == P && pg_->getRank() == rank,
+                  "PsxStep: the process group must have P ranks");
+    } else if (tx_ == kTxRccl) {
+      // (c0, c1, c23): RCCL runs every operation of ONE communicator in issue
+      // order, whatever stream it was issued on, so the count exchange C0 and
+      // the keys C1 -- both on the path to the next open -- get
+      // communicators of their own instead of queueing behind the big pull /
+      // push transfers C2 / C3 of earlier minibatches. One communicator for
+      // all three is accepted too (tests).
+      TORCH_CHECK(!rccl.is_none(), "PsxStep: the RCCL transport needs a communicator");
+      if (py::isinstance<py::sequence>(rccl)) {
+        auto seq = rccl.cast<py::sequence>();
+        TORCH_CHECK(seq.size() == 3, "PsxStep: rccl = (c0, c1, c23) communicators");
+        for (int i = 0; i < 3; ++i) comm_[i] = seq[i].cast<std::shared_ptr<RcclComm>>();
+      } else {
+        comm_[0] = comm_[1] = comm_[2] = rccl.cast<std::shared_ptr<RcclComm>>();
+      }
+      for (const auto& c : comm_)
+        TORCH_CHECK((c->size() == P && c->rank() == rank) || c->size() == 1,
+                    "PsxStep: the communicators must have P ranks (or 1: loopback rehearsal)");
+    }
+    for (const auto& c : comm_)
+      TORCH_CHECK(!c || c->device() == dev, "PsxStep: communicator on another device");
+    parse_xstall(rank_, &fault_step_);
+    if (tx_ != kTxIdentity) {  // (the identity transport cannot stall on a peer)
+      const char* t = std::getenv("WH_RCCL_TIMEOUT_S");
+      const double dl = t && std::atof(t) > 0 ? std::atof(t) : 120.0;
+      std::vector<std::shared_ptr<RcclComm>> cs;
+      if (tx_ == kTxRccl) cs.assign(comm_, comm_ + 3);
+      wd_ = std::make_unique<PsxWatchdog>((int)rank_, dl, cs);
+    }
+    xt_on_ = tx_ == kTxRccl;
+    if (timing_on("comm")) xt_every_ = 1;  // WH_TIMING=comm: every exchange timed
+  }
+  void stop_watchdog() { wd_.reset(); }
+
+  PsxTx kind() const { return tx_; }
+  bool identity() const { return tx_ == kTxIdentity; }
+  // the compute stream of the running call: where exchanged rows are read
+  void set_compute(const c10::hip::HIPStream& S) { S_ = S; }
+
+  struct Call {  // a PsxStep call the deadline applies to
+    PsxWatchdog* w;
+    Call(PsxTransport& t, const char* c) : w(t.wd_.get()) {
+      if (w) w->enter(c, *t.step_);
+    }
+    ~Call() {
+      if (w) w->leave();
+    }
+  };
+  void mark(const char* what, int c) {
+    if (wd_) wd_->phase(what, c, *step_);
+  }
+  double deadline() const { return wd_ ? wd_->deadline() : 0.0; }
+
+  // One exchange of class c (C0..C3): peer q gets send_rows[q] rows of x and
+  // recv_rows[q] rows of the result come from q. Issued on the stream `on`
+  // (`name` in the watchdog's log), which first waits for `ready` if given;
+  // `work` (C1..C3) keeps x alive and, when `on` is not the compute stream,
+  // is what the compute stream waits for before it reads the result. C0 has
+  // no work: its reader is the host.
+  Tensor exchange(int c, const Tensor& x, const Rows& send_rows, const Rows& recv_rows,
+                  const c10::hip::HIPStream& on, const char* name, hipEvent_t ready,
+                  PsxWork* work) {
+    int64_t row = x.element_size();
+    for (int64_t d = 1; d < x.dim(); ++d) row *= x.size(d);
+    if (c) wire_[c] += row * (vsum(send_rows) - send_rows[rank_]);  // (C0 is not counted)
+    if (work) {
+      work->pending = false;
+      work->keep = Tensor();
+    }
+    if (tx_ == kTxIdentity) return x;
+    fault(c);
+    Tensor xc = x.contiguous();
+    if (tx_ == kTxStaged) {
+      mark("staged exchange", c);
+      xlog(c, send_rows, recv_rows, "host (staged)", nullptr);
+      Tensor r = staged_a2a(xc, send_rows, recv_rows);
+      mark("staged exchange returned", c);
+      return r;
+    }
+    std::vector<int64_t> shape(xc.sizes().begin(), xc.sizes().end());
+    shape[0] = vsum(recv_rows);
+    if (ready) {
+      WH_HIP_CHECK_HOST(hipStreamWaitEvent(on.stream(), ready, 0));
+      c10::hip::HIPCachingAllocator::recordStream(xc.storage().data_ptr(), on);
+    }
+    c10::hip::HIPStreamGuard sg(on);
+    Tensor out = torch::empty(shape, xc.options());
+    if (ready)  // allocated on `on`, read on S
+      c10::hip::HIPCachingAllocator::recordStream(out.storage().data_ptr(), S_);
+    EventP t0 = xt_begin(on.stream());
+    comm_[std::min(c, 2)]->a2av(xc.data_ptr(), out.data_ptr(), row, send_rows, recv_rows,
+                                on.stream());
+    xt_end(c, std::move(t0), on.stream());
+    // the transfer's end on `on`: what the compute stream waits for, or (C0)
+    // only what the watchdog's log reports on
+    EventP done;
+    if (work ? on.stream() != S_.stream() : (bool)wd_) {
+      done = work && work->ev ? work->ev : std::make_shared<Event>(false);
+      WH_HIP_CHECK_HOST(hipEventRecord(*done, on.stream()));
+    }
+    if (work) {
+      work->keep = xc;
+      work->ev = done ? done : work->ev;
+      work->pending = (bool)done;
+    }
+    mark("exchange issued", c);
+    xlog(c, send_rows, recv_rows, name, std::move(done));
+    return out;
+  }
+
+  std::vector<int64_t> wire() const { return {wire_[0], wire_[1], wire_[2], wire_[3]}; }
+  void wire_reset() {
+    wire_[0] = wire_[1] = wire_[2] = wire_[3] = 0;
+    xt_harvest(true);
+    for (int c = 0; c < 4; ++c) xt_us_[c] = 0, xt_n_[c] = 0;
+  }
+  // sampled GPU time per exchange class C0..C3 (RCCL transport; every
+  // 16th step, every step with WH_TIMING=comm; events around the grouped send / recv on its stream;
+  // it includes the wait for the slowest peer): {mean us x4, samples x4}
+  std::vector<double> xtime() {
+    xt_harvest(true);
+    std::vector<double> o(8, 0.0);
+    for (int c = 0; c < 4; ++c) {
+      o[c] = xt_n_[c] ? xt_us_[c] / (double)xt_n_[c] : 0.0;
+      o[4 + c] = (double)xt_n_[c];
+    }
+    return o;
+  }
+
+ private:
+  // kTxStaged: the rows through host memory and the gloo group, in order on
+  // the current stream (blocking: the correctness rehearsal of the RCCL
+  // path with several ranks on one GPU)
+  // It executes the same a2a_plan() as RcclComm::a2av (per-peer offsets,
+  // the own segment a local copy, zero-byte segments skipped) with one c10d
+  // send / recv per peer.
+  Tensor staged_a2a(const Tensor& xc, const Rows& send_rows, const Rows& recv_rows) {
+    Tensor h = xc.to(torch::kCPU).contiguous();  // (waits for the current stream's queue)
+    int64_t row = h.element_size();
+    for (int64_t d = 1; d < h.dim(); ++d) row *= h.size(d);
+    std::vector<int64_t> shape(h.sizes().begin(), h.sizes().end());
+    if (shape.empty()) shape.push_back(0);
+    shape[0] = vsum(recv_rows);
+    Tensor out = torch::empty(shape, h.options());
+    const A2aPlan pl = a2a_plan((int)rank_, (int)P_, row, send_rows, recv_rows);
+    Tensor hb = h.reshape({-1}).view(torch::kUInt8), ob = out.view({-1}).view(torch::kUInt8);
+    std::vector<c10::intrusive_ptr<c10d::Work>> ws;
+    for (const auto& g : pl.recvs) {
+      std::vector<Tensor> t{ob.narrow(0, g.off, g.bytes)};
+      ws.push_back(pg_->recv(t, g.peer, kStagedTag));
+    }
+    for (const auto& g : pl.sends) {
+      std::vector<Tensor> t{hb.narrow(0, g.off, g.bytes)};
+      ws.push_back(pg_->send(t, g.peer, kStagedTag));
+    }
+    if (pl.own_bytes > 0)
+      ob.narrow(0, pl.own_dst, pl.own_bytes).copy_(hb.narrow(0, pl.own_src, pl.own_bytes));
+    for (auto& w : ws)
+      if (w) w->wait();
+    return out.to(xc.device());
+  }
+
+  void xlog(int c, const Rows& s, const Rows& r, const char* stream, EventP ev) {
+    if (wd_) wd_->log(PsxXLog{c, *step_, stream, s, r, std::move(ev)});
+  }
+  void fault(int c) {
+    if (fault_step_ < 0 || *step_ != fault_step_) return;
+    fault_step_ = -1;
+    std::fprintf(stderr, "[psx] WH_FAULT: rank %lld stalls before C%d of step %lld\n",
+                 (long long)rank_, c, (long long)*step_);
+    std::fflush(stderr);
+    mark("WH_FAULT stall", c);
+    std::this_thread::sleep_for(std::chrono::hours(1));
+  }
+
+  // sampled exchange timing (RCCL transport)
+  EventP xt_begin(hipStream_t s) {
+    if (!xt_on_ || *step_ % xt_every_ != 0) return nullptr;
+    auto e = std::make_shared<Event>(true);
+    WH_HIP_CHECK_HOST(hipEventRecord(*e, s));
+    return e;
+  }
+  void xt_end(int c, EventP a, hipStream_t s) {
+    if (!a) return;
+    auto b = std::make_shared<Event>(true);
+    WH_HIP_CHECK_HOST(hipEventRecord(*b, s));
+    xt_pend_.push_back({c, std::move(a), std::move(b)});
+    if (xt_pend_.size() > 64) xt_harvest(false);
+  }
+  void xt_harvest(bool sync) {
+    std::vector<XtPend> keep;
+    for (auto& p : xt_pend_) {
+      if (sync) {
+        mark("exchange timing read (host wait)", p.cls);
+        WH_HIP_CHECK_HOST(hipEventSynchronize(*p.b));
+      } else if (hipEventQuery(*p.b) != hipSuccess) {
+        keep.push_back(std::move(p));
+        continue;
+      }
+      float ms = 0.f;
+      if (hipEventElapsedTime(&ms, *p.a, *p.b) == hipSuccess) {
+        xt_us_[p.cls] += 1000.0 * ms;
+        xt_n_[p.cls] += 1;
+      }
+    }
+    xt_pend_.swap(keep);
+  }
+
+  static constexpr int kStagedTag = 7;
+  struct XtPend {
+    int cls;
+    EventP a, b;
+  };
+  PsxTx tx_ = kTxIdentity;
+  int64_t P_ = 0, rank_ = 0;
+  const int64_t* step_ = nullptr;
+  c10::intrusive_ptr<c10d::ProcessGroup> pg_;  // kTxStaged
+  std::shared_ptr<RcclComm> comm_[3];          // kTxRccl: C0, C1, C2 / C3
+  c10::hip::HIPStream S_ = c10::hip::getDefaultHIPStream();
+  std::unique_ptr<PsxWatchdog> wd_;  // (transports with peers)
+  int64_t fault_step_ = -1;          // WH_FAULT=xstall
+  int64_t wire_[4] = {0, 0, 0, 0};
+  bool xt_on_ = false;
+  int64_t xt_every_ = 16;
+  std::vector<XtPend> xt_pend_;
+  double xt_us_[4] = {0, 0, 0, 0};
+  int64_t xt_n_[4] = {0, 0, 0, 0};
+};
+
+struct PsxSt {  // one minibatch in flight (kv/psx.py _Step)
+  bool train = false, use_cnt = false, have_v = false;
+  int64_t U = 0, seed_step = 0;
+  Rows send, recv, Hw, Ho, vown, vrecv;
+  Tensor label, uniq, ucnt, lid, offset, val, csc_off, csc_row, csc_val;
+  Tensor tabs, segS_w, segHS_w, segS_o, segHS_o, vrecv_d;
+  Tensor keys_o, slot, vpos, chain, head, rbuf, vcnt;
+  Tensor rrecv, hdr, rows, py, dual, xv, gpush, gvc;
+  // fixed_bytes filter: the receiving side's region table (device) and float
+  // extent of C2 / C3's wire rows (q2_desc / q3_desc undefined: exact floats)
+  Tensor q2_desc, q3_desc;
+  int64_t q2_ext = 0, q3_ext = 0;
+  // C2 / C3 wait for these only: the open's and the backward's ends on S
+  // (the step's own pair from PsxStep::sev_, recorded once each)
+  hipEvent_t ev_open = nullptr, ev_grad = nullptr;
+  hipEvent_t own_open = nullptr, own_grad = nullptr;
+  PsxWork w_c1, w_c2, w_c3;
+
+  void set_v(Rows vr, Rows vo) {  // the V rows per peer (from a count payload)
+    vrecv = std::move(vr);
+    vown = std::move(vo);
+    have_v = true;
+  }
+  wh::PsxSides sides(bool linear) const {
+    return wh::psx_sides(linear, send, recv, Hw, Ho, vown, vrecv);
+  }
+};
+using PsxStP = std::shared_ptr<PsxSt>;
 
 class PsxStep {
  public:
-  // tx: the transport (PsxTx); pg: the gloo process group of kTxStaged;
-  // rccl: the communicator of kTxRccl (P ranks, or 1 for the loopback
-  // rehearsal); lin_hp: (algo, alpha, beta, l1, l2) of the linear wire
-  // format's owner push; hp / threshold / l1_shrk / seed: DiFacto's
-  // (kv/psx.py reads the same from the learner); met / auc_sum: the
-  // learner's device progress accumulators.
+  // tx: the transport (PsxTx) with pg / rccl (PsxTransport::open); lin_hp:
+  // (algo, alpha, beta, l1, l2) of the linear wire format's owner push; hp /
+  // threshold / l1_shrk / seed: DiFacto's (kv/psx.py reads the same from the
+  // learner); met / auc_sum: the learner's device progress accumulators.
   PsxStep(KVStore* store, int64_t P, int64_t S, int64_t rank, int64_t tx, py::object pg,
           py::object rccl, bool linear, std::vector<double> lin_hp, std::vector<double> hp,
           int64_t threshold, bool l1_shrk, int64_t seed, int64_t loss, Tensor met, Tensor auc_sum,
           int64_t tau, double max_load, int64_t cu_reserve, std::vector<int64_t> filt,
           std::vector<double> post)
-      : store_(store), P_(P), S_(S), rank_(rank), linear_(linear), lin_hp_(std::move(lin_hp)),
+      : store_(store), P_(P), S_(S), linear_(linear), lin_hp_(std::move(lin_hp)),
         hp_(std::move(hp)), threshold_(threshold), l1_shrk_(l1_shrk), seed_(seed), loss_(loss),
         met_(std::move(met)), auc_sum_(std::move(auc_sum)), tau_(tau), guard_(store, max_load) {
     TORCH_CHECK(P >= 2 && S >= 1 && S <= P && rank >= 0 && rank < P, "PsxStep: bad P / S / rank");
@@ -306,72 +577,23 @@ class PsxStep {
                 kMaxTau);
     vs_ = store->vstride();
     TORCH_CHECK(linear_ == (vs_ == 0), "PsxStep: the linear wire format is the vstride-0 store");
-    TORCH_CHECK(tx >= kTxIdentity && tx <= kTxStaged, "PsxStep: unknown transport");
-    tx_ = (PsxTx)tx;
-    if (tx_ == kTxStaged) {
-      TORCH_CHECK(!pg.is_none(), "PsxStep: the staged transport needs a process group");
-      pg_ = pg.cast<c10::intrusive_ptr<c10d::ProcessGroup>>();
-      TORCH_CHECK(pg_->getSize() == P && pg_->getRank() == rank,
-                  "PsxStep: the process group must have P ranks");
-    } else if (tx_ == kTxRccl) {
-      // (c0, c1, c23): RCCL runs every operation of ONE communicator in issue
-      // order, whatever stream it was issued on, so the count exchange C0 and
-      // the keys C1 -- both on the path to the next open -- get
-      // communicators of their own instead of queueing behind the big pull /
-      // push transfers C2 / C3 of earlier minibatches. One communicator for
-      // all three is accepted too (tests).
-      TORCH_CHECK(!rccl.is_none(), "PsxStep: the RCCL transport needs a communicator");
-      if (py::isinstance<py::sequence>(rccl)) {
-        auto seq = rccl.cast<py::sequence>();
-        TORCH_CHECK(seq.size() == 3, "PsxStep: rccl = (c0, c1, c23) communicators");
-        rccl_c0_ = seq[0].cast<std::shared_ptr<RcclComm>>();
-        rccl_c1_ = seq[1].cast<std::shared_ptr<RcclComm>>();
-        rccl_ = seq[2].cast<std::shared_ptr<RcclComm>>();
-      } else {
-        rccl_ = rccl_c0_ = rccl_c1_ = rccl.cast<std::shared_ptr<RcclComm>>();
-      }
-      for (const auto& c : {rccl_c0_, rccl_c1_, rccl_})
-        TORCH_CHECK((c->size() == P && c->rank() == rank) || c->size() == 1,
-                    "PsxStep: the communicators must have P ranks (or 1: loopback rehearsal)");
-    }
     dev_ = store->slots_.device().index();
-    for (const auto& c : {rccl_c0_, rccl_c1_, rccl_})
-      TORCH_CHECK(!c || c->device() == dev_, "PsxStep: communicator on another device");
+    tx_.open(tx, std::move(pg), std::move(rccl), P, rank, dev_, &step_);
     c10::DeviceGuard g(store->slots_.device());
     // streams of our own (as Python's torch.cuda.Stream()): the pool's
     // round-robin streams are shared with other users, and a localize queued
     // behind a collective on a shared stream serialises the step. The linear
     // step keeps every phase on the compute stream (see the file comment).
     one_ = sx_ = linear_;
-    if (!one_) {
-      ls_h_ = own_stream(dev_, kStreamPsxLs);
-      ls_ = c10::hip::getStreamFromExternal(ls_h_, dev_);
-    }
+    if (!one_) ls_ = c10::hip::getStreamFromExternal(own_stream(dev_, kStreamPsxLs), dev_);
     if (!sx_) {
-      cs_h_ = own_stream(dev_, kStreamPsxCs);
-      xs_h_ = own_stream(dev_, kStreamPsxXs);
-      cs_ = c10::hip::getStreamFromExternal(cs_h_, dev_);
-      xs_ = c10::hip::getStreamFromExternal(xs_h_, dev_);
+      cs_ = c10::hip::getStreamFromExternal(own_stream(dev_, kStreamPsxCs), dev_);
+      xs_ = c10::hip::getStreamFromExternal(own_stream(dev_, kStreamPsxXs), dev_);
     }
-    for (auto& e : ring_) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto& e : ring_) e.create();
     for (auto& p : sev_)
-      for (auto& e : p) WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (tx_ == kTxRccl) wh::fm_set_cu_reserve((int)cu_reserve);
-    const int64_t dflt = std::max<int64_t>(4 * (P + 1) + P, 64);
-    for (int i = 0; i < kPins; ++i) {
-      pins_[i] = torch::empty({dflt}, torch::TensorOptions().dtype(torch::kInt64).pinned_memory(true));
-      WH_HIP_CHECK_HOST(hipEventCreateWithFlags(&pin_ev_[i], hipEventDisableTiming));
-    }
-    parse_xstall(rank_, &fault_step_);
-    if (tx_ != kTxIdentity) {  // (the identity transport cannot stall on a peer)
-      const char* t = std::getenv("WH_RCCL_TIMEOUT_S");
-      const double dl = t && std::atof(t) > 0 ? std::atof(t) : 120.0;
-      std::vector<std::shared_ptr<RcclComm>> cs;
-      if (tx_ == kTxRccl) cs = {rccl_c0_, rccl_c1_, rccl_};
-      wd_ = std::make_unique<PsxWatchdog>((int)rank_, dl, cs);
-    }
-    xt_on_ = tx_ == kTxRccl;
-    if (timing_on("comm")) xt_every_ = 1;  // WH_TIMING=comm: every exchange timed
+      for (auto& e : p) e.create();
+    if (tx_.kind() == kTxRccl) wh::fm_set_cu_reserve((int)cu_reserve);
     if (qnb_) {
       qW_ = linear_ ? 64 : std::max(vs_, 1);
       qR_ = (4 + qW_ * qnb_ + 3) / 4 * 4;  // ops/ref.py quant_record_bytes
@@ -379,14 +601,10 @@ class PsxStep {
   }
 
   ~PsxStep() {
-    wd_.reset();
+    tx_.stop_watchdog();
     if (timing_) timing_->print();
     job_.reset();
-    (void)hipDeviceSynchronize();
-    for (auto& e : ring_) (void)hipEventDestroy(e);
-    for (auto& p : sev_)
-      for (auto& e : p) (void)hipEventDestroy(e);
-    for (auto& e : pin_ev_) (void)hipEventDestroy(e);
+    (void)hipDeviceSynchronize();  // (the members' events are destroyed after this)
   }
 
   // One training minibatch (Psx.train). Returns (has_data, minibatches
@@ -396,7 +614,7 @@ class PsxStep {
                   const c10::optional<Tensor>& noffset, const c10::optional<Tensor>& nval,
                   int64_t ready) {
     c10::DeviceGuard g(keys.device());
-    WdCall wc(wd_.get(), "train", step_);
+    PsxTransport::Call wc(tx_, "train");
     // WH_TIMING=step: host us per phase, printed every 1000 calls: s0 job,
     // s1 count read (the host WAIT), s2 tables + C2/C3 issue, s3 localize
     // finish + next begin + C1, s4 reply (forward), s5 owner push, s6 open,
@@ -407,8 +625,8 @@ class PsxStep {
     fwd_mb_ = 0;
     ensure_job(keys, offset, val);
     ht.mark(0);
-    std::vector<int64_t> send, recv;
-    const bool empty = counts(send, recv);
+    Rows send, recv;
+    const bool empty = counts(&send, &recv);
     ht.mark(1);
     if (empty) {
       finish_job();
@@ -473,14 +691,11 @@ class PsxStep {
   // forwarded here.
   int64_t flush() {
     c10::DeviceGuard g(store_->slots_.device());
-    WdCall wc(wd_.get(), "flush", step_);
+    PsxTransport::Call wc(tx_, "flush");
     set_streams();
     fwd_mb_ = 0;
     if (!pushes_.empty() && pushes_.back()->gvc.defined()) c3(*pushes_.back());
-    if (job_ && job_carried_) {  // the begun job carries the last pull's V counts
-      std::vector<int64_t> a, b;
-      counts(a, b);
-    }
+    if (job_ && job_carried_) counts();  // the begun job carries the last pull's V counts
     PsxStP st = pull_;
     if (st) {
       if (!st->have_v) vcount_exchange(*st);
@@ -499,38 +714,22 @@ class PsxStep {
   // drop a begun localize (before the Python step runs an evaluation /
   // read-only pull of its own: every rank does it at the same point)
   void drop_job() {
-    WdCall wc(wd_.get(), "drop_job", step_);
+    PsxTransport::Call wc(tx_, "drop_job");
     if (job_) {
       if (job_deferred_) {
         c10::hip::HIPStreamGuard sg(ls_);
         job_->exchange();
       }
-      std::vector<int64_t> a, b;
-      counts(a, b);
+      counts();
       finish_job();
     }
   }
 
   bool busy() const { return (bool)pull_ || !pushes_.empty() || (bool)job_; }
-  std::vector<int64_t> wire() const { return {wire_[0], wire_[1], wire_[2], wire_[3]}; }
-  void wire_reset() {
-    wire_[0] = wire_[1] = wire_[2] = wire_[3] = 0;
-    xt_harvest(true);
-    for (int c = 0; c < 4; ++c) xt_us_[c] = 0, xt_n_[c] = 0;
-  }
-  // sampled GPU time per exchange class C0..C3 (RCCL transport; every
-  // 16th step, every step with WH_TIMING=comm; events around the grouped send / recv on its stream;
-  // it includes the wait for the slowest peer): {mean us x4, samples x4}
-  std::vector<double> xtime() {
-    xt_harvest(true);
-    std::vector<double> o(8, 0.0);
-    for (int c = 0; c < 4; ++c) {
-      o[c] = xt_n_[c] ? xt_us_[c] / (double)xt_n_[c] : 0.0;
-      o[4 + c] = (double)xt_n_[c];
-    }
-    return o;
-  }
-  double watchdog_deadline() const { return wd_ ? wd_->deadline() : 0.0; }
+  std::vector<int64_t> wire() const { return tx_.wire(); }
+  void wire_reset() { tx_.wire_reset(); }
+  std::vector<double> xtime() { return tx_.xtime(); }
+  double watchdog_deadline() const { return tx_.deadline(); }
   int64_t grows() const { return guard_.grows(); }
   int64_t vgrows() const { return guard_.vgrows(); }
   int64_t requests() const { return requests_; }
@@ -540,121 +739,36 @@ class PsxStep {
   // the guard's last summary {keys, failed inserts, V overflows, V rows}
   std::vector<int64_t> guard_sync() {
     summarise();
-    mark("store summary read (host wait)", -1);
+    tx_.mark("store summary read (host wait)", -1);
     return guard_.sync();
   }
 
  private:
-  // ------------------------------------------------------------ transport
-  Tensor a2a(int c, const Tensor& x, const std::vector<int64_t>& send_rows,
-             const std::vector<int64_t>& recv_rows, hipEvent_t ready, PsxWork* work) {
-    int64_t row = x.element_size();
-    for (int64_t d = 1; d < x.dim(); ++d) row *= x.size(d);
-    wire_[c] += row * (vsum(send_rows) - send_rows[rank_]);
-    work->pending = false;
-    work->keep = Tensor();
-    if (tx_ == kTxIdentity) return x;
-    fault(c);
-    Tensor xc = x.contiguous();
-    if (tx_ == kTxStaged) {
-      mark("staged exchange", c);
-      xlog(c, send_rows, recv_rows, "host (staged)", nullptr);
-      Tensor r = staged_a2a(xc, send_rows, recv_rows);
-      mark("staged exchange returned", c);
-      return r;
-    }
-    std::vector<int64_t> shape(xc.sizes().begin(), xc.sizes().end());
-    shape[0] = vsum(recv_rows);
-    // issued from xs behind the producer's event only (the compute stream
-    // goes on with the work enqueued after the producer: C2 of minibatch
-    // i-1 overlaps the backward of i-2), or on S itself when no event is
-    // given (C1; the linear step's single stream)
-    c10::hip::HIPStream xs = ready ? xs_ : S_stream_;
-    if (ready) {
-      WH_HIP_CHECK_HOST(hipStreamWaitEvent(xs_.stream(), ready, 0));
-      c10::hip::HIPCachingAllocator::recordStream(xc.storage().data_ptr(), xs_);
-    }
-    c10::hip::HIPStreamGuard sg(xs);
-    Tensor out = torch::empty(shape, xc.options());
-    if (ready)  // allocated on xs, read on S
-      c10::hip::HIPCachingAllocator::recordStream(out.storage().data_ptr(), S_stream_);
-    PsxEvP t0 = xt_begin(xs.stream());
-    (c == 1 ? rccl_c1_ : rccl_)->a2av(xc.data_ptr(), out.data_ptr(), row, send_rows, recv_rows,
-                                      xs.stream());
-    xt_end(c, std::move(t0), xs.stream());
-    work->keep = xc;
-    if (xs.stream() != S_stream_.stream()) {
-      if (!work->ev) work->ev = std::make_shared<PsxEv>();
-      WH_HIP_CHECK_HOST(hipEventRecord(work->ev->e, xs.stream()));
-      work->pending = true;
-    }
-    mark("exchange issued", c);
-    xlog(c, send_rows, recv_rows, xs.stream() == xs_.stream() && !sx_ ? "xs" : "S",
-         work->pending ? work->ev : nullptr);
-    return out;
+  // ------------------------------------------------------------ exchanges
+  // C1..C3: issued from xs behind the producer's event only (the compute
+  // stream goes on with the work enqueued after the producer: C2 of
+  // minibatch i-1 overlaps the backward of i-2), or on S itself when no
+  // event is given (C1; the linear step's single stream)
+  Tensor a2a(int c, const Tensor& x, const Rows& send_rows, const Rows& recv_rows,
+             hipEvent_t ready, PsxWork* work) {
+    return ready ? tx_.exchange(c, x, send_rows, recv_rows, xs_, "xs", ready, work)
+                 : tx_.exchange(c, x, send_rows, recv_rows, S_stream_, "S", nullptr, work);
   }
 
-  // kTxStaged: the rows through host memory and the gloo group, in order on
-  // the current stream (blocking: the correctness rehearsal of the RCCL
-  // path with several ranks on one GPU)
-  // It executes the same a2a_plan() as RcclComm::a2av (per-peer offsets,
-  // the own segment a local copy, zero-byte segments skipped) with one c10d
-  // send / recv per peer.
-  Tensor staged_a2a(const Tensor& xc, const std::vector<int64_t>& send_rows,
-                    const std::vector<int64_t>& recv_rows) {
-    Tensor h = xc.to(torch::kCPU).contiguous();  // (waits for the current stream's queue)
-    int64_t row = h.element_size();
-    for (int64_t d = 1; d < h.dim(); ++d) row *= h.size(d);
-    std::vector<int64_t> shape(h.sizes().begin(), h.sizes().end());
-    if (shape.empty()) shape.push_back(0);
-    shape[0] = vsum(recv_rows);
-    Tensor out = torch::empty(shape, h.options());
-    const A2aPlan pl = a2a_plan((int)rank_, (int)P_, row, send_rows, recv_rows);
-    Tensor hb = h.reshape({-1}).view(torch::kUInt8), ob = out.view({-1}).view(torch::kUInt8);
-    std::vector<c10::intrusive_ptr<c10d::Work>> ws;
-    for (const auto& g : pl.recvs) {
-      std::vector<Tensor> t{ob.narrow(0, g.off, g.bytes)};
-      ws.push_back(pg_->recv(t, g.peer, kStagedTag));
+  // C0 on the current stream cs: the count payload int64 [S + 1 + 5P] of
+  // (owner counts, V row counts), its 4P-word receive slot filled by one
+  // 32-byte send / recv per peer -- this tiny exchange sits on the path of
+  // the step's one host read (loopback identity: the kernel fills the slot
+  // itself)
+  Tensor c0(const Tensor& owner_cnt, const Tensor& vc, int64_t flag) {
+    auto b = ps_c0(owner_cnt, vc.defined() ? c10::optional<Tensor>(vc) : c10::nullopt, P_, flag,
+                   tx_.identity());
+    if (!tx_.identity()) {
+      const Rows four(P_, 4);
+      b[1].narrow(0, S_ + 1, 4 * P_)
+          .copy_(tx_.exchange(0, b[0], four, four, cs_, sx_ ? "S" : "cs", nullptr, nullptr));
     }
-    for (const auto& g : pl.sends) {
-      std::vector<Tensor> t{hb.narrow(0, g.off, g.bytes)};
-      ws.push_back(pg_->send(t, g.peer, kStagedTag));
-    }
-    if (pl.own_bytes > 0)
-      ob.narrow(0, pl.own_dst, pl.own_bytes).copy_(hb.narrow(0, pl.own_src, pl.own_bytes));
-    for (auto& w : ws)
-      if (w) w->wait();
-    return out.to(xc.device());
-  }
-
-  // int64 [4P] per peer -> the peers' [4P], on the current stream
-  Tensor exchange_counts(const Tensor& send) {
-    if (tx_ == kTxIdentity) return send.clone();
-    fault(0);
-    std::vector<int64_t> four(P_, 4);
-    Tensor s = send.contiguous();
-    if (tx_ == kTxStaged) {
-      mark("staged exchange", 0);
-      xlog(0, four, four, "host (staged)", nullptr);
-      Tensor r = staged_a2a(s, four, four);
-      mark("staged exchange returned", 0);
-      return r;
-    }
-    // one 32-byte send / recv per peer on the current stream (cs): this tiny
-    // exchange sits on the path of the step's one host read
-    Tensor r = torch::empty_like(s);
-    const hipStream_t cur = c10::hip::getCurrentHIPStream(dev_).stream();
-    PsxEvP t0 = xt_begin(cur);
-    rccl_c0_->a2av(s.data_ptr(), r.data_ptr(), sizeof(int64_t), four, four, cur);
-    xt_end(0, std::move(t0), cur);
-    PsxEvP ev;
-    if (wd_) {
-      ev = std::make_shared<PsxEv>();
-      WH_HIP_CHECK_HOST(hipEventRecord(ev->e, cur));
-    }
-    mark("exchange issued", 0);
-    xlog(0, four, four, cur == cs_h_ ? "cs" : "S", std::move(ev));
-    return r;
+    return b[1];
   }
 
   hipEvent_t record(const c10::hip::HIPStream& s) {
@@ -668,94 +782,17 @@ class PsxStep {
     WH_HIP_CHECK_HOST(hipStreamWaitEvent(waiter.stream(), record(producer), 0));
   }
 
-  // small int64 tables host -> device through a ring of pinned buffers
-  Tensor put(const std::vector<int64_t>& a) {
-    const int k = pin_i_;
-    pin_i_ = (pin_i_ + 1) % kPins;
-    if (pin_used_[k]) {
-      mark("pinned table ring (host wait)", -1);
-      WH_HIP_CHECK_HOST(hipEventSynchronize(pin_ev_[k]));
-    }
-    if ((int64_t)a.size() > pins_[k].numel())
-      pins_[k] = torch::empty({2 * (int64_t)a.size()},
-                              torch::TensorOptions().dtype(torch::kInt64).pinned_memory(true));
-    std::memcpy(pins_[k].data_ptr(), a.data(), a.size() * sizeof(int64_t));
+  // small int64 tables host -> device through the ring of pinned buffers
+  Tensor put(const Rows& a) {
+    if (pins_.next_used()) tx_.mark("pinned table ring (host wait)", -1);
+    std::memcpy(pins_.get<int64_t>((int64_t)a.size()), a.data(), a.size() * sizeof(int64_t));
     Tensor d = torch::empty({(int64_t)a.size()},
                             torch::TensorOptions().dtype(torch::kInt64).device(torch::kCUDA, dev_));
     if (!a.empty())
-      WH_HIP_CHECK_HOST(hipMemcpyAsync(d.data_ptr(), pins_[k].data_ptr(), a.size() * 8,
+      WH_HIP_CHECK_HOST(hipMemcpyAsync(d.data_ptr(), pins_.tensor().data_ptr(), a.size() * 8,
                                        hipMemcpyHostToDevice, S_stream_.stream()));
-    WH_HIP_CHECK_HOST(hipEventRecord(pin_ev_[k], S_stream_.stream()));
-    pin_used_[k] = true;
+    pins_.mark(S_stream_.stream());
     return d;
-  }
-
-  // ------------------------------------------------------------ watchdog
-  struct WdCall {  // a call the deadline applies to
-    PsxWatchdog* w;
-    WdCall(PsxWatchdog* w_, const char* c, int64_t s) : w(w_) {
-      if (w) w->enter(c, s);
-    }
-    ~WdCall() {
-      if (w) w->leave();
-    }
-  };
-  void mark(const char* what, int c) {
-    if (wd_) wd_->phase(what, c, step_);
-  }
-  void xlog(int c, const std::vector<int64_t>& s, const std::vector<int64_t>& r, const char* stream,
-            PsxEvP ev) {
-    if (!wd_) return;
-    PsxXLog x;
-    x.cls = c;
-    x.step = step_;
-    x.stream = stream;
-    x.send = s;
-    x.recv = r;
-    x.ev = std::move(ev);
-    wd_->log(std::move(x));
-  }
-  void fault(int c) {
-    if (fault_step_ < 0 || step_ != fault_step_) return;
-    fault_step_ = -1;
-    std::fprintf(stderr, "[psx] WH_FAULT: rank %lld stalls before C%d of step %lld\n",
-                 (long long)rank_, c, (long long)step_);
-    std::fflush(stderr);
-    mark("WH_FAULT stall", c);
-    std::this_thread::sleep_for(std::chrono::hours(1));
-  }
-
-  // sampled exchange timing (RCCL transport)
-  PsxEvP xt_begin(hipStream_t s) {
-    if (!xt_on_ || step_ % xt_every_ != 0) return nullptr;
-    auto e = std::make_shared<PsxEv>(true);
-    WH_HIP_CHECK_HOST(hipEventRecord(e->e, s));
-    return e;
-  }
-  void xt_end(int c, PsxEvP a, hipStream_t s) {
-    if (!a) return;
-    auto b = std::make_shared<PsxEv>(true);
-    WH_HIP_CHECK_HOST(hipEventRecord(b->e, s));
-    xt_pend_.push_back({c, std::move(a), std::move(b)});
-    if (xt_pend_.size() > 64) xt_harvest(false);
-  }
-  void xt_harvest(bool sync) {
-    std::vector<XtPend> keep;
-    for (auto& p : xt_pend_) {
-      if (sync) {
-        mark("exchange timing read (host wait)", p.cls);
-        WH_HIP_CHECK_HOST(hipEventSynchronize(p.b->e));
-      } else if (hipEventQuery(p.b->e) != hipSuccess) {
-        keep.push_back(std::move(p));
-        continue;
-      }
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, p.a->e, p.b->e) == hipSuccess) {
-        xt_us_[p.cls] += 1000.0 * ms;
-        xt_n_[p.cls] += 1;
-      }
-    }
-    xt_pend_.swap(keep);
   }
 
   // ------------------------------------------------------------ localize
@@ -768,11 +805,7 @@ class PsxStep {
       c10::hip::HIPCachingAllocator::recordStream(owner_cnt.storage().data_ptr(), cs_);
       if (vc.defined()) c10::hip::HIPCachingAllocator::recordStream(vc.storage().data_ptr(), cs_);
       c10::hip::HIPStreamGuard sg(cs_);
-      // (loopback identity: the kernel fills the receive slot itself)
-      auto c0 = ps_c0(owner_cnt, vc.defined() ? c10::optional<Tensor>(vc) : c10::nullopt, P_, flag,
-                      tx_ == kTxIdentity);
-      if (tx_ != kTxIdentity) c0[1].narrow(0, S_ + 1, 4 * P_).copy_(exchange_counts(c0[0]));
-      return std::make_tuple(c0[1], cs_.stream(), (int64_t)4, P_);
+      return std::make_tuple(c0(owner_cnt, vc, flag), cs_.stream(), (int64_t)4, P_);
     };
   }
 
@@ -810,8 +843,7 @@ class PsxStep {
   void ensure_job(const Tensor& keys, const Tensor& offset, const c10::optional<Tensor>& val) {
     if (job_ && job_keys_.is_same(keys)) return;
     if (job_) {  // a stale job (never expected): finish it in order
-      std::vector<int64_t> a, b;
-      counts(a, b);
+      counts();
       finish_job();
     }
     begin(keys, offset, val, (pull_ && !pull_->have_v) ? pull_ : PsxStP(), 0, false);
@@ -820,34 +852,21 @@ class PsxStep {
   // the one host read of the step (count exchange C0 of the begun job):
   // send / recv per peer; fills the carried step's V counts; true when no
   // rank has data
-  bool counts(std::vector<int64_t>& send, std::vector<int64_t>& recv) {
+  bool counts(Rows* send = nullptr, Rows* recv = nullptr) {
     exchange_deferred();
-    mark("C0 count read (host wait)", 0);
+    tx_.mark("C0 count read (host wait)", 0);
     auto c = job_->counts();
-    mark("C0 counts read", 0);
-    const int64_t* oc = c[0].data_ptr<int64_t>();
-    const Tensor& tail = c[1];
-    const int64_t* t = tail.data_ptr<int64_t>();
-    TORCH_CHECK(tail.numel() >= 5 * P_, "psx: short count payload");
-    if (job_carried_ && !job_carried_->have_v) {
-      auto& ca = *job_carried_;
-      ca.vrecv.assign(P_, 0);
-      ca.vown.assign(P_, 0);
-      for (int64_t q = 0; q < P_; ++q) {
-        ca.vrecv[q] = t[2 + 4 * q];
-        ca.vown[q] = t[4 * P_ + q];
-      }
-      ca.have_v = true;
+    tx_.mark("C0 counts read", 0);
+    TORCH_CHECK(c[1].numel() >= 5 * P_, "psx: short count payload");
+    wh::PsxCounts pc = wh::psx_counts(c[1].data_ptr<int64_t>(), P_);
+    if (job_carried_ && !job_carried_->have_v) job_carried_->set_v(pc.vrecv, pc.vown);
+    if (send) {
+      const int64_t* oc = c[0].data_ptr<int64_t>();
+      send->assign(oc, oc + S_);
+      send->resize(P_, 0);
+      *recv = std::move(pc.recv);
     }
-    send.assign(P_, 0);
-    recv.assign(P_, 0);
-    bool any = false;
-    for (int64_t p = 0; p < S_; ++p) send[p] = oc[p];
-    for (int64_t q = 0; q < P_; ++q) {
-      recv[q] = t[4 * q];
-      any = any || t[3 + 4 * q] != 0;
-    }
-    return !any;
+    return !pc.any;
   }
 
   std::vector<Tensor> finish_job() {
@@ -860,33 +879,21 @@ class PsxStep {
   }
 
   void vcount_exchange(PsxSt& st) {
-    if (linear_) {
-      st.vrecv.assign(P_, 0);
-      st.vown.assign(P_, 0);
-      st.have_v = true;
-      return;
-    }
+    if (linear_) return st.set_v(Rows(P_, 0), Rows(P_, 0));
     auto zero = torch::zeros({S_ + 1}, st.vcnt.options());
     wait_on(cs_, S_stream_);
     c10::hip::HIPStreamGuard sg(cs_);
-    auto c0 = ps_c0(zero, st.vcnt, P_, 1, tx_ == kTxIdentity);
-    if (tx_ != kTxIdentity) c0[1].narrow(0, S_ + 1, 4 * P_).copy_(exchange_counts(c0[0]));
-    mark("C0 V-count read (host wait)", 0);
-    Tensor v = c0[1].cpu();
-    mark("C0 V-counts read", 0);
-    const int64_t* h = v.data_ptr<int64_t>();
-    st.vrecv.assign(P_, 0);
-    st.vown.assign(P_, 0);
-    for (int64_t q = 0; q < P_; ++q) {
-      st.vrecv[q] = h[S_ + 3 + 4 * q];
-      st.vown[q] = h[S_ + 1 + 4 * P_ + q];
-    }
-    st.have_v = true;
+    Tensor payload = c0(zero, st.vcnt, 1);
+    tx_.mark("C0 V-count read (host wait)", 0);
+    Tensor v = payload.cpu();
+    tx_.mark("C0 V-counts read", 0);
+    wh::PsxCounts pc = wh::psx_counts(v.data_ptr<int64_t>() + S_ + 1, P_);
+    st.set_v(std::move(pc.vrecv), std::move(pc.vown));
   }
 
   // ------------------------------------------------------------ tables
-  PsxStP new_step(const std::vector<int64_t>& send, const std::vector<int64_t>& recv,
-                  const Tensor& label, bool train, int64_t data_pass, PsxSt* prev) {
+  PsxStP new_step(const Rows& send, const Rows& recv, const Tensor& label, bool train,
+                  int64_t data_pass, PsxSt* prev) {
     auto st = std::make_shared<PsxSt>();
     st->send = send;
     st->recv = recv;
@@ -901,24 +908,10 @@ class PsxStep {
     st->own_open = sev_[sev_i_][0];
     st->own_grad = sev_[sev_i_][1];
     sev_i_ = (sev_i_ + 1) % kStepEv;
-    const int64_t vs = std::max<int64_t>(vs_, 1);
-    st->Hw.assign(P_, 0);
-    st->Ho.assign(P_, 0);
-    if (!linear_)
-      for (int64_t p = 0; p < P_; ++p) {
-        st->Hw[p] = cdiv64(2 * send[p], vs);
-        st->Ho[p] = cdiv64(2 * recv[p], vs);
-      }
-    std::vector<int64_t> a(4 * (P_ + 1) + P_, 0);
-    for (int64_t p = 0; p < P_; ++p) {
-      a[p + 1] = a[p] + send[p];
-      a[P_ + 2 + p] = a[P_ + 1 + p] + st->Hw[p];
-      a[2 * P_ + 3 + p] = a[2 * P_ + 2 + p] + recv[p];
-      a[3 * P_ + 4 + p] = a[3 * P_ + 3 + p] + st->Ho[p];
-    }
-    if (prev)
-      for (int64_t q = 0; q < P_; ++q) a[4 * P_ + 4 + q] = prev->vrecv[q];
-    Tensor t = put(a);
+    wh::PsxSegs sg = wh::psx_segs(send, recv, vs_, linear_, prev ? &prev->vrecv : nullptr);
+    st->Hw = std::move(sg.Hw);
+    st->Ho = std::move(sg.Ho);
+    Tensor t = put(sg.table);
     st->tabs = t;
     st->segS_w = t.narrow(0, 0, P_ + 1);
     st->segHS_w = t.narrow(0, P_ + 1, P_ + 1);
@@ -951,6 +944,7 @@ class PsxStep {
   // the compute stream of this call; one stream: every phase on it
   void set_streams() {
     S_stream_ = c10::hip::getCurrentHIPStream(dev_);
+    tx_.set_compute(S_stream_);
     if (one_) ls_ = S_stream_;
     if (sx_) cs_ = xs_ = S_stream_;
   }
@@ -970,7 +964,7 @@ class PsxStep {
     // on the exchange stream behind the records (RCCL copies the keys there
     // while the compute stream goes on with the previous minibatch's forward;
     // on the compute stream itself the forward queued behind the transfer)
-    hipEvent_t ready = (tx_ == kTxRccl && !sx_) ? record(S_stream_) : nullptr;
+    hipEvent_t ready = (tx_.kind() == kTxRccl && !sx_) ? record(S_stream_) : nullptr;
     st.keys_o = a2a(1, rec, st.send, st.recv, ready, &st.w_c1);
   }
 
@@ -978,7 +972,7 @@ class PsxStep {
     st.w_c1.wait();
     const int64_t n = vsum(st.recv);
     if (insert) {
-      if (guard_.pending()) mark("store summary read (host wait)", -1);
+      if (guard_.pending()) tx_.mark("store summary read (host wait)", -1);
       Tensor remap = guard_.before(n);
       if (remap.defined()) {  // the table grew: the live steps' slot ids move with it
         std::vector<PsxSt*> live{pull_.get()};
@@ -1008,67 +1002,38 @@ class PsxStep {
     if (insert && ++gskip_ >= gevery_) summarise();
   }
 
+  // the pull: the owner side's rows out, the worker side's in
   void c2(PsxSt& st) {
-    std::vector<int64_t> send_rows(P_), recv_rows(P_);
-    for (int64_t p = 0; p < P_; ++p) {
-      send_rows[p] = linear_ ? st.recv[p] : st.Ho[p] + st.vown[p];
-      recv_rows[p] = linear_ ? st.send[p] : st.Hw[p] + st.vrecv[p];
-    }
-    Tensor x = st.rbuf.narrow(0, 0, vsum(send_rows));
+    wh::PsxSides sd = st.sides(linear_);
+    Tensor x = st.rbuf.narrow(0, 0, vsum(sd.owner));
     hipEvent_t ready = st.ev_open;
     if (qnb_ && !linear_) {  // (linear pulls travel exact)
-      x = qpack(x, st.recv, st.send, st.vown, st.vrecv, st.Ho, st.Hw, send_rows, recv_rows,
-                &st.q2_desc, &st.q2_ext);
+      x = qpack(x, owner_side(st), worker_side(st), sd.owner, sd.worker, &st.q2_desc, &st.q2_ext);
       ready = sx_ ? nullptr : record(S_stream_);
     }
-    st.rrecv = a2a(2, x, send_rows, recv_rows, ready, &st.w_c2);
+    st.rrecv = a2a(2, x, sd.owner, sd.worker, ready, &st.w_c2);
     st.ev_open = nullptr;
     st.rbuf = Tensor();
   }
 
-  // fixed_bytes: the float regions x (this side: n keys, v embedding rows, H
-  // header rows per peer) -> uint8 wire rows, on S (kv/psx.py Psx._qpack);
-  // rows out / in per peer replace send_rows / recv_rows, and the receiving
-  // side's table and float extent are kept for qunpack
-  struct QLayout {
-    std::vector<int64_t> desc, rows;
-    int64_t ext = 0;
+  // fixed_bytes: the float regions x of the sending side (n keys, v embedding
+  // rows, H header rows per peer) -> uint8 wire rows, on S (kv/psx.py
+  // Psx._qpack); rows out / in per peer replace send_rows / recv_rows, and
+  // the receiving side's table and float extent are kept for qunpack
+  struct QSide {
+    const Rows &n, &v, &H;
   };
-  QLayout qlayout(const std::vector<int64_t>& n, const std::vector<int64_t>& v,
-                  const std::vector<int64_t>& H) const {
-    QLayout L;
-    L.desc.assign(6 * P_, 0);
-    int64_t sf = 0, sq = 0;
-    for (int64_t p = 0; p < P_; ++p) {
-      int64_t a, vf, nf, ha, nr, ext;
-      if (linear_) {
-        a = 0, vf = 0, nf = n[p], ha = 0;
-        nr = cdiv64(n[p], qW_);
-        ext = n[p];
-      } else {
-        a = 2 * n[p], vf = H[p] * vs_, nf = v[p] * vs_;
-        ha = cdiv64(4 * a, qR_);
-        nr = v[p];
-        ext = (H[p] + v[p]) * vs_;
-      }
-      const int64_t d[6] = {sf, a, vf, nf, sq, ha};
-      for (int k = 0; k < 6; ++k) L.desc[6 * p + k] = d[k];
-      L.rows.push_back(ha + nr);
-      sf += ext;
-      sq += ha + nr;
-    }
-    L.ext = sf;
-    return L;
+  static QSide owner_side(const PsxSt& st) { return {st.recv, st.vown, st.Ho}; }
+  static QSide worker_side(const PsxSt& st) { return {st.send, st.vrecv, st.Hw}; }
+  wh::PsxQLayout qlayout(const QSide& s) const {
+    return wh::psx_qlayout(linear_, vs_, qW_, qR_, s.n, s.v, s.H);
   }
-  Tensor qpack(const Tensor& x, const std::vector<int64_t>& ns, const std::vector<int64_t>& nr,
-               const std::vector<int64_t>& vs, const std::vector<int64_t>& vr,
-               const std::vector<int64_t>& Hs, const std::vector<int64_t>& Hr,
-               std::vector<int64_t>& send_rows, std::vector<int64_t>& recv_rows, Tensor* rdesc,
-               int64_t* rext) {
-    const QLayout ls = qlayout(ns, vs, Hs), lr = qlayout(nr, vr, Hr);
+  Tensor qpack(const Tensor& x, const QSide& from, const QSide& to, Rows& send_rows,
+               Rows& recv_rows, Tensor* rdesc, int64_t* rext) {
+    const wh::PsxQLayout ls = qlayout(from), lr = qlayout(to);
     TORCH_CHECK(ls.ext == x.numel(), "psx filter: region layout ", ls.ext, " floats vs buffer ",
                 x.numel());
-    std::vector<int64_t> both(ls.desc);
+    Rows both(ls.desc);
     both.insert(both.end(), lr.desc.begin(), lr.desc.end());
     Tensor t = put(both);
     ++qcalls_;
@@ -1152,20 +1117,16 @@ class PsxStep {
     fm_grad_post(gvc, st.rows, pdim_, clip_, dropout_, seed_ + 7919 * st.seed_step + 1, gnorm_);
   }
 
+  // the push: the worker side's rows out, the owner side's in
   void c3(PsxSt& st) {
-    std::vector<int64_t> send_rows(P_), recv_rows(P_);
-    for (int64_t p = 0; p < P_; ++p) {
-      send_rows[p] = linear_ ? st.send[p] : st.Hw[p] + st.vrecv[p];
-      recv_rows[p] = linear_ ? st.recv[p] : st.Ho[p] + st.vown[p];
-    }
+    wh::PsxSides sd = st.sides(linear_);
     Tensor x = st.gvc;
     hipEvent_t ready = st.ev_grad;
     if (qnb_) {
-      x = qpack(x, st.send, st.recv, st.vrecv, st.vown, st.Hw, st.Ho, send_rows, recv_rows,
-                &st.q3_desc, &st.q3_ext);
+      x = qpack(x, worker_side(st), owner_side(st), sd.worker, sd.owner, &st.q3_desc, &st.q3_ext);
       ready = sx_ ? nullptr : record(S_stream_);
     }
-    st.gpush = a2a(3, x, send_rows, recv_rows, ready, &st.w_c3);
+    st.gpush = a2a(3, x, sd.worker, sd.owner, ready, &st.w_c3);
     st.ev_grad = nullptr;
     st.gvc = Tensor();
   }
@@ -1200,13 +1161,8 @@ class PsxStep {
 
   static constexpr int kMaxTau = 8;
   static constexpr int kRing = 32, kPins = 8, kStepEv = kMaxTau + 4;
-  static constexpr int kStagedTag = 7;
-  struct XtPend {
-    int cls;
-    PsxEvP a, b;
-  };
   KVStore* store_;
-  int64_t P_, S_, rank_;
+  int64_t P_, S_;
   bool linear_;
   std::vector<double> lin_hp_, hp_;
   int64_t threshold_;
@@ -1215,38 +1171,26 @@ class PsxStep {
   Tensor met_, auc_sum_;
   int64_t tau_;
   int vs_ = 0;
-  PsxTx tx_ = kTxIdentity;
-  c10::intrusive_ptr<c10d::ProcessGroup> pg_;  // kTxStaged
-  std::shared_ptr<RcclComm> rccl_, rccl_c0_, rccl_c1_;  // kTxRccl: C2 / C3, C0, C1
+  PsxTransport tx_;
   c10::DeviceIndex dev_ = 0;
   c10::hip::HIPStream S_stream_ = c10::hip::getDefaultHIPStream();
   c10::hip::HIPStream ls_ = c10::hip::getDefaultHIPStream();
   c10::hip::HIPStream cs_ = c10::hip::getDefaultHIPStream();
   c10::hip::HIPStream xs_ = c10::hip::getDefaultHIPStream();
-  hipStream_t ls_h_ = nullptr, cs_h_ = nullptr, xs_h_ = nullptr;
-  hipEvent_t ring_[kRing] = {};
-  hipEvent_t sev_[kStepEv][2] = {};
+  Event ring_[kRing];
+  Event sev_[kStepEv][2];
   int sev_i_ = 0;
   int ring_i_ = 0;
-  Tensor pins_[kPins];
-  hipEvent_t pin_ev_[kPins] = {};
-  bool pin_used_[kPins] = {};
-  int pin_i_ = 0;
+  PinnedRing<kPins> pins_;
   std::unique_ptr<LocalizeJob> job_;
   Tensor job_keys_;
   PsxStP job_carried_, pull_;
   std::deque<PsxStP> pushes_;  // backward done, push not yet applied (oldest first)
   bool job_deferred_ = false;
   int64_t uhint_ = 0, step_ = 0, requests_ = 0, fwd_mb_ = 0, last_u_ = 0, last_v_ = 0;
-  int64_t wire_[4] = {0, 0, 0, 0};
   std::unique_ptr<HostSplit> timing_{host_split("psx native step")};
   bool one_ = false, sx_ = false;
   HostTimer* ht_ = nullptr;  // (WH_TIMING=step: the running call's marks, for grad's split)
-  std::unique_ptr<PsxWatchdog> wd_;  // (transports with peers)
-  int64_t fault_step_ = -1;          // WH_FAULT=xstall
-  bool xt_on_ = false;
-  int64_t xt_every_ = 16;
-  std::vector<XtPend> xt_pend_;
   // fixed_bytes filter (qnb_ > 0): bytes per float, seed, floats and bytes
   // per wire record; the seed sequence follows kv/psx.py _QFilter.next_seed
   int qnb_ = 0, qW_ = 0, qR_ = 0;
@@ -1255,8 +1199,6 @@ class PsxStep {
   double clip_ = 0, dropout_ = 0;
   bool gnorm_ = false, post_on_ = false;
   int64_t pdim_ = 0;
-  double xt_us_[4] = {0, 0, 0, 0};
-  int64_t xt_n_[4] = {0, 0, 0, 0};
   // guard: opens per store summary (the linear step: a launch, an event and
   // a host read less on 3 of 4 steps)
   const int gevery_ = linear_ ? 4 : 1;
@@ -1264,7 +1206,56 @@ class PsxStep {
   StoreGuard guard_;
 };
 
-Tensor c10d_a2a_rows(py::object pg, const Tensor& x, const std::vector<int64_t>& send_rows,
-                     const std::vector<int64_t>& recv_rows) {
-  return c10d_rows(pg.cast<c10::intrusive_ptr<c10d::ProcessGroup>>(), x, send_rows, recv_rows);
+}  // namespace
+
+void bind_psx(py::module_& m) {
+  py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
+      .def(py::init<const std::string&, int64_t, int64_t, int64_t>(), py::arg("uid"),
+           py::arg("nranks"), py::arg("rank"), py::arg("device"))
+      .def_static("unique_id", &RcclComm::unique_id)
+      .def("close", &RcclComm::close)
+      .def("a2av", &RcclComm::a2av_t, py::arg("x"), py::arg("send_rows"), py::arg("recv_rows"))
+      .def("allreduce_sum", [](RcclComm& c, Tensor t) { c.allreduce_sum(t); })
+      .def_property_readonly("size", &RcclComm::size)
+      .def_property_readonly("rank", &RcclComm::rank)
+      .def_property_readonly("device", &RcclComm::device);
+  m.attr("PSX_TX_IDENTITY") = (int)kTxIdentity;
+  m.attr("PSX_TX_RCCL") = (int)kTxRccl;
+  m.attr("PSX_TX_STAGED") = (int)kTxStaged;
+  py::class_<PsxStep>(m, "PsxStep")
+      .def(py::init<KVStore*, int64_t, int64_t, int64_t, int64_t, py::object, py::object, bool,
+                    std::vector<double>, std::vector<double>, int64_t, bool, int64_t, int64_t,
+                    Tensor, Tensor, int64_t, double, int64_t, std::vector<int64_t>,
+                    std::vector<double>>(),
+           py::arg("store"), py::arg("P"), py::arg("S"), py::arg("rank"), py::arg("tx"),
+           py::arg("pg"), py::arg("rccl"), py::arg("linear"), py::arg("lin_hp"), py::arg("hp"), py::arg("threshold"),
+           py::arg("l1_shrk"), py::arg("seed"), py::arg("loss"), py::arg("met"),
+           py::arg("auc_sum"), py::arg("tau"), py::arg("max_load"), py::arg("cu_reserve"),
+           py::arg("filt") = std::vector<int64_t>{0, 0},
+           py::arg("post") = std::vector<double>{0.0, 0.0, 0.0, 0.0},
+           py::keep_alive<1, 2>())
+      .def("train", &PsxStep::train, py::arg("keys"), py::arg("offset"), py::arg("val"),
+           py::arg("label"), py::arg("data_pass"), py::arg("next_keys") = py::none(),
+           py::arg("next_offset") = py::none(), py::arg("next_val") = py::none(),
+           py::arg("ready") = 0)
+      .def("flush", &PsxStep::flush)
+      .def("drop_job", &PsxStep::drop_job)
+      .def("guard_sync", &PsxStep::guard_sync)
+      .def("wire", &PsxStep::wire)
+      .def("wire_reset", &PsxStep::wire_reset)
+      .def("xtime", &PsxStep::xtime,
+           "sampled GPU us per exchange C0..C3 and the sample counts (RCCL transport)")
+      .def_property_readonly("watchdog_deadline", &PsxStep::watchdog_deadline)
+      .def_property_readonly("busy", &PsxStep::busy)
+      .def_property_readonly("grows", &PsxStep::grows)
+      .def_property_readonly("vgrows", &PsxStep::vgrows)
+      .def_property("requests", &PsxStep::requests, &PsxStep::set_requests)
+      .def_property("step", &PsxStep::step, &PsxStep::set_step);
+  m.def("a2a_plan", &a2a_plan_py, py::arg("rank"), py::arg("world"), py::arg("row_bytes"),
+        py::arg("send_rows"), py::arg("recv_rows"),
+        "one rank's per-peer all-to-all-v plan: (esz, (own_src, own_dst, own_bytes), sends, recvs)");
+  m.def("c10d_a2a_rows", &c10d_a2a_rows, py::arg("pg"), py::arg("x"), py::arg("send_rows"),
+        py::arg("recv_rows"));
 }
+
+}  // namespace wh_bind

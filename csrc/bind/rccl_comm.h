@@ -1,5 +1,5 @@
 // A communicator of our own on RCCL's C API: the data plane of the
-// multi-shard parameter-server step (csrc/bind/psx_native.inl) over xGMI.
+// multi-shard parameter-server step (csrc/bind/psx_ops.cc) over xGMI.
 //
 // Replaces ps-lite's per-minibatch ZPull / ZPush / ZVPull / ZVPush messages
 // (learn/linear/async_sgd.h:252-287, learn/difacto/async_sgd.h:373-424) with
@@ -12,7 +12,7 @@
 //
 // The per-peer work of one rank is computed once, by a2a_plan(), and the
 // transports only execute it: RcclComm::a2av below (ncclSend / ncclRecv per
-// peer) and the gloo-staged rehearsal of psx_native.inl (c10d send / recv per
+// peer) and the gloo-staged rehearsal of psx_ops.cc (c10d send / recv per
 // peer on host copies), so the multi-process CPU / shared-GPU tests run the
 // very offsets, own-segment copy and zero-row skips an 8-GPU run takes.
 //
@@ -22,6 +22,7 @@
 // stands in for P virtual peers in the one-GPU loopback rehearsal (the own
 // segment a device copy, the other P-1 one send / recv pair to self).
 #pragma once
+#include "bind_common.h"
 
 #include <rccl/rccl.h>
 
@@ -35,6 +36,8 @@
     ncclResult_t r_ = (x);                                                            \
     TORCH_CHECK(r_ == ncclSuccess, "RCCL error in ", #x, ": ", ncclGetErrorString(r_)); \
   } while (0)
+
+namespace wh_bind {
 
 // One rank's share of a row-wise all-to-all-v, in bytes.
 struct A2aPlan {
@@ -249,3 +252,5 @@ inline py::tuple a2a_plan_py(int64_t rank, int64_t world, int64_t row_bytes,
   for (const auto& g : pl.recvs) r.append(py::make_tuple(g.peer, g.off, g.bytes));
   return py::make_tuple(pl.esz, py::make_tuple(pl.own_src, pl.own_dst, pl.own_bytes), s, r);
 }
+
+}  // namespace wh_bind

@@ -24,6 +24,7 @@
 #include "host/json.h"
 #include "host/localize_plan.h"
 #include "host/parsers.h"
+#include "host/psx_plan.h"
 #include "host/store_guard_plan.h"
 #include "host/van.h"
 #include "host/workload_pool.h"
@@ -533,10 +534,69 @@ static void test_localize_plan() {
   }
 }
 
+// what the multi-shard step puts on the wire (host/psx_plan.h). Expected
+// values from the Python twin kv/psx.py: _QFilter.layout with H = ceil(2n /
+// vs), Psx._upload, the row rules of Psx._c2 / _c3 and the tail slices of
+// Psx._counts / _vcount_exchange.
+static void test_psx_plan() {
+  using R = wh::PsxRows;
+  // filter layout: DiFacto nb=1 vs=8 (W=8, R=12), nb=3 vs=16 (W=16, R=52),
+  // linear nb=2 (W=64)
+  {
+    auto L = wh::psx_qlayout(false, 8, 8, 12, {3, 0, 5}, {2, 0, 1}, {1, 0, 2});
+    EXPECT((L.desc == R{0, 6, 8, 16, 0, 2, 24, 0, 0, 0, 4, 0, 24, 10, 16, 8, 4, 4}));
+    EXPECT((L.rows == R{4, 0, 5}) && L.ext == 48);
+    L = wh::psx_qlayout(false, 16, 16, 52, {0, 7}, {0, 4}, {0, 1});
+    EXPECT((L.desc == R{0, 0, 0, 0, 0, 0, 0, 14, 16, 64, 0, 2}));
+    EXPECT((L.rows == R{0, 6}) && L.ext == 80);
+    L = wh::psx_qlayout(true, 0, 64, 132, {65, 0, 64, 1}, {}, {});
+    EXPECT((L.desc == R{0, 0, 0, 65, 0, 0, 65, 0, 0, 0, 2, 0, 65, 0, 0, 64, 2, 0, 129, 0, 0, 1, 3, 0}));
+    EXPECT((L.rows == R{2, 0, 1, 1}) && L.ext == 130);
+  }
+  // segment tables: P=3, vs=8, with the previous step's vrecv; without one
+  // the last P words stay zero; linear (vs=0): no header rows
+  const R send{3, 0, 5}, recv{2, 4, 0}, pv{1, 0, 2};
+  {
+    auto s = wh::psx_segs(send, recv, 8, false, &pv);
+    EXPECT((s.Hw == R{1, 0, 2}) && (s.Ho == R{1, 1, 0}));
+    EXPECT((s.table == R{0, 3, 3, 8, 0, 1, 1, 3, 0, 2, 6, 6, 0, 1, 2, 2, 1, 0, 2}));
+    s = wh::psx_segs(send, recv, 8, false, nullptr);
+    EXPECT((s.table == R{0, 3, 3, 8, 0, 1, 1, 3, 0, 2, 6, 6, 0, 1, 2, 2, 0, 0, 0}));
+    s = wh::psx_segs(send, recv, 0, true, &pv);
+    EXPECT((s.Hw == R{0, 0, 0}) && (s.Ho == R{0, 0, 0}));
+    EXPECT((s.table == R{0, 3, 3, 8, 0, 0, 0, 0, 0, 2, 6, 6, 0, 0, 0, 0, 1, 0, 2}));
+  }
+  // rows per peer: C2 sends the owner side and receives the worker side, C3
+  // the other way round (here: as each exchange would name them)
+  {
+    const R Hw{1, 0, 2}, Ho{1, 1, 0}, vown{2, 1, 0}, vrecv{1, 0, 2}, z{0, 0, 0};
+    auto d = wh::psx_sides(false, send, recv, Hw, Ho, vown, vrecv);
+    const R c2_send = d.owner, c2_recv = d.worker, c3_send = d.worker, c3_recv = d.owner;
+    EXPECT((c2_send == R{3, 2, 0}) && (c2_recv == R{2, 0, 4}));
+    EXPECT(c3_send == c2_recv && c3_recv == c2_send);
+    auto l = wh::psx_sides(true, send, recv, z, z, z, z);
+    EXPECT(l.owner == recv && l.worker == send);  // C2: send recv's rows, get send's; C3 swaps
+  }
+  // count payload, P=2: {recv, overflow, vrecv, has-data} per peer, then vown
+  {
+    const int64_t tail[10] = {11, 91, 13, 0, 21, 92, 23, 1, 31, 32};
+    auto c = wh::psx_counts(tail, 2);
+    EXPECT((c.recv == R{11, 21}) && (c.vrecv == R{13, 23}) && (c.vown == R{31, 32}) && c.any);
+    const int64_t none[10] = {0, 1, 5, 0, 0, 0, 6, 0, 7, 8};
+    c = wh::psx_counts(none, 2);
+    EXPECT(!c.any && (c.vrecv == R{5, 6}) && (c.vown == R{7, 8}));  // "empty": no rank has data
+    // the V-count exchange reads the same layout at offset S + 1 (S = 1)
+    const int64_t buf[12] = {-1, -2, 11, 91, 13, 0, 21, 92, 23, 1, 31, 32};
+    c = wh::psx_counts(buf + 1 + 1, 2);
+    EXPECT((c.recv == R{11, 21}) && (c.vrecv == R{13, 23}) && (c.vown == R{31, 32}) && c.any);
+  }
+}
+
 int main() {
   test_auc();
   test_store_guard_plan();
   test_localize_plan();
+  test_psx_plan();
   test_gbdt_hist_plan();
   test_lz4();
   test_crb();

@@ -430,7 +430,7 @@ def test_loopback_gpu_long_run_crosses_tag_wrap(max_conc):
 
 # ---------------------------------------------------------------- linear
 def _lin_run(comm, device, algo=3, steps=6, rows=300, seed=17, max_conc=1, nshard=None,
-             batches=None, fixed_bytes=0):
+             batches=None, fixed_bytes=0, nxt=True):
     from wormhole_amd.config.schema import LinearConfig
     from wormhole_amd.data.synthetic import criteo_batch_cpu
     from wormhole_amd.models.linear import LinearLearner
@@ -441,7 +441,9 @@ def _lin_run(comm, device, algo=3, steps=6, rows=300, seed=17, max_conc=1, nshar
         batches = [[t.to(device) for t in criteo_batch_cpu(rows, seed, s, CARD)]
                    for s in range(steps)]
     for s, (keys, label, off) in enumerate(batches):
-        nb = (batches[s + 1][0], batches[s + 1][2], None) if s + 1 < len(batches) else None
+        nb = None
+        if nxt and s + 1 < len(batches):
+            nb = (batches[s + 1][0], batches[s + 1][2], None)
         lr.process(keys, off, None, label, 0, 0, next_batch=nb)
     lr.flush()
     return lr, lr.take_progress(), batches
@@ -594,16 +596,21 @@ def test_linear_loopback_gpu_matches_cpu(algo, max_conc):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("model,max_conc,opts", [
-    ("difacto", 2, ""), ("difacto", 1, ""), ("linear", 2, ""), ("linear", 1, ""),
-    ("difacto", 2, "fb1"), ("difacto", 1, "fb3clipdrop"), ("difacto", 2, "clipnorm"),
-    ("linear", 2, "fb2")])
-def test_native_step_matches_python_step(model, max_conc, opts, monkeypatch):
-    """The C++ driver of the multi-shard step (csrc/bind/psx_native.inl
-    PsxStep) trains the same model as the Python step it ports (kv/psx.py
-    Psx.train, WH_PSX_NATIVE=0), pipelined and strict, on 4 loopback shards;
-    with the fixed_bytes filter (the same stochastic-rounding seeds in the
-    same order) and the embedding-gradient post-processing too."""
+@pytest.mark.parametrize("model,max_conc,opts,nxt", [
+    pytest.param(m, c, o, True, id="%s-%d-%s" % (m, c, o)) for m, c, o in [
+        ("difacto", 2, ""), ("difacto", 1, ""), ("linear", 2, ""), ("linear", 1, ""),
+        ("difacto", 2, "fb1"), ("difacto", 1, "fb3clipdrop"), ("difacto", 2, "clipnorm"),
+        ("linear", 2, "fb2")]] + [
+    pytest.param("difacto", 2, "", False, id="difacto-2-nonext"),
+    pytest.param("linear", 1, "", False, id="linear-1-nonext")])
+def test_native_step_matches_python_step(model, max_conc, opts, nxt, monkeypatch):
+    """The C++ driver of the multi-shard step (csrc/bind/psx_ops.cc PsxStep)
+    trains the same model as the Python step it ports (kv/psx.py Psx.train,
+    WH_PSX_NATIVE=0), pipelined and strict, on 4 loopback shards; with the
+    fixed_bytes filter (the same stochastic-rounding seeds in the same order)
+    and the embedding-gradient post-processing too; and without a look-ahead
+    batch (nxt=False), where each call begins its own localize job, which
+    carries the previous pull's V counts."""
     from wormhole_amd.parallel.comm import LoopbackComm
     dev = torch.device("cuda", 0)
     runs = {}
@@ -611,12 +618,12 @@ def test_native_step_matches_python_step(model, max_conc, opts, monkeypatch):
         monkeypatch.setenv("WH_PSX_NATIVE", native)
         if model == "difacto":
             lr, prog, b = _run(LoopbackComm(4, dev), _conf(max_conc=max_conc, opts=opts), dev,
-                               steps=8, rows=3000)
+                               steps=8, rows=3000, nxt=nxt)
             runs[native] = (_model(lr), prog, bool(lr.psx._nat))
         else:
             fb = int(opts[opts.index("fb") + 2]) if "fb" in opts else 0
             lr, prog, b = _lin_run(LoopbackComm(4, dev), dev, 3, steps=8, rows=3000,
-                                   max_conc=max_conc, fixed_bytes=fb)
+                                   max_conc=max_conc, fixed_bytes=fb, nxt=nxt)
             runs[native] = (_lin_model(lr), prog, bool(lr.psx._nat))
     (mn, pn, isn), (mp_, pp, isp) = runs["1"], runs["0"]
     assert isn and not isp

@@ -1,5 +1,5 @@
 """The multi-rank exchange of the native parameter-server step (csrc/bind/
-rccl_comm.h, csrc/bind/psx_native.inl) with more than one rank.
+rccl_comm.h, csrc/bind/psx_ops.cc) with more than one rank.
 
 * ``a2a_plan`` -- the per-peer plan every transport executes -- composes to
   the exact all-to-all-v over P ranks for uneven, empty and one-sided

@@ -278,7 +278,7 @@ class Psx:
         # the owner-side update of the linear wire format: (algo, alpha,
         # beta, l1, l2) -- the linear model's, or DiFacto's FTRL on w (algo 4)
         self.lin_hp = lrn.psx_linear_hp() if self.linear else None
-        # the native driver of train() (csrc/bind/psx_native.inl PsxStep):
+        # the native driver of train() (csrc/bind/psx_ops.cc PsxStep):
         # decided at the first training call; False = this Python step
         self._nat = None
         self._kmod_cache = None  # (keys, keys % max_key) of the last reduced tensor
@@ -703,7 +703,7 @@ class Psx:
 
     # ------------------------------------------------------------ native
     def _native(self):
-        """The C++ driver of :meth:`train` (csrc/bind/psx_native.inl
+        """The C++ driver of :meth:`train` (csrc/bind/psx_ops.cc
         PsxStep) -- the default for every GPU configuration: RCCL ranks (its
         own communicator, grouped send / recv per peer), gloo-staged ranks
         sharing one GPU, the loopback identity and the 1-rank RCCL loopback.

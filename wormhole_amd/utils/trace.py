@@ -26,7 +26,7 @@ import time
 
 def timing_on(what):
     """True when ``what`` is listed in WH_TIMING (the C++ side reads the same
-    variable: csrc/bind/hip_ops.cc timing_on)."""
+    variable: csrc/bind/bind_common.h timing_on)."""
     return what in os.environ.get("WH_TIMING", "").split(",")
 
 
