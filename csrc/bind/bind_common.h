@@ -3,7 +3,8 @@
 // stateless helpers, the process-wide switches (deterministic, timing) and
 // one registration function per op family. State lives with its owner: the
 // localize workspace in localize_ops.cc, every other device workspace in
-// hip_ops.cc; the KVStore is kv_store.h.
+// hip_ops.cc (DevWs, declared in ps_ops.h for fm_ops.cc); the KVStore is
+// kv_store.h.
 #pragma once
 #include <torch/extension.h>
 #include <pybind11/stl.h>
@@ -48,10 +49,14 @@ inline hipStream_t cur_stream(const Tensor& t) {
 template <typename T>
 T* ptr(const Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
 
+// an optional tensor that is really there: given, defined and non-empty
+inline bool present(const c10::optional<Tensor>& t) {
+  return t.has_value() && t->defined() && t->numel() > 0;
+}
+
 template <typename T>
 const T* optptr(const c10::optional<Tensor>& t) {
-  return (t.has_value() && t->defined() && t->numel() > 0) ? reinterpret_cast<const T*>(t->data_ptr())
-                                                           : nullptr;
+  return present(t) ? reinterpret_cast<const T*>(t->data_ptr()) : nullptr;
 }
 
 inline int64_t next_pow2(int64_t x) {
@@ -197,6 +202,7 @@ void bind_kmeans(py::module_& m);
 void bind_bsp(py::module_& m);
 void bind_ingest(py::module_& m);
 void bind_localize(py::module_& m);
+void bind_fm(py::module_& m);
 void bind_psx(py::module_& m);
 
 }  // namespace wh_bind

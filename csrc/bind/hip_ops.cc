@@ -1,18 +1,17 @@
 // torch / pybind11 binding layer for the gfx950 HIP kernels (module
 // wormhole_amd._hip): the module itself and everything that shares the
-// parameter-server state -- KVStore's bindings (the class is kv_store.h), FM,
-// the single-shard native steps, the AUC chain, quantisation. The multi-shard
-// step and RCCL (psx_ops.cc; what it calls here is declared in ps_ops.h),
-// localize (localize_ops.cc; the steps use its job through localize_job.h)
-// and the stateless BSP families (gbdt_ops.cc, kmeans_ops.cc, bsp_ops.cc,
-// ingest_ops.cc) have translation units of their own, registered from
-// PYBIND11_MODULE below. Host-only: validates tensors, sizes outputs and
-// launches on the current PyTorch HIP stream.
+// parameter-server state -- the device workspaces, KVStore's bindings (the
+// class is kv_store.h), the ps_* ops of the multi-shard exchange, the native
+// layer's streams and host timers, the AUC chain, quantisation. FM and the
+// single-shard native steps (fm_ops.cc), the multi-shard step and RCCL
+// (psx_ops.cc), localize (localize_ops.cc) and the stateless BSP families
+// (gbdt_ops.cc, kmeans_ops.cc, bsp_ops.cc, ingest_ops.cc) have translation
+// units of their own, registered from PYBIND11_MODULE below; what those call
+// here is declared in ps_ops.h. Host-only: validates tensors, sizes outputs
+// and launches on the current PyTorch HIP stream.
 #include "bind_common.h"
 #include "kv_store.h"
-#include "localize_job.h"
 #include "ps_ops.h"
-#include "store_guard.h"
 
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPCachingAllocator.h>
@@ -21,18 +20,12 @@
 #include <array>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <chrono>
-#include <cmath>
-#include <functional>
 #include <deque>
 #include <map>
 #include <mutex>
 #include <condition_variable>
 #include <thread>
-#include <memory>
-#include <numeric>
-#include <tuple>
 #include <string>
 #include <vector>
 
@@ -40,23 +33,9 @@
 
 using namespace wh_bind;
 
-// (in wh_bind, not an anonymous namespace: psx_ops.cc calls some of these)
+// (in wh_bind, not an anonymous namespace: fm_ops.cc and psx_ops.cc call some
+// of these)
 namespace wh_bind {
-
-// Per-device persistent workspaces (allocated once, zero-initialised; the
-// kernels that use them leave them in that state). Intentionally leaked: they
-// must outlive every stream-ordered use and the process exit order. (Localize
-// keeps a workspace of its own in localize_ops.cc.)
-struct DevWs {
-  Tensor lb;          // look-back scan granules + ticket (wh_lookback.h)
-  Tensor auc;         // AUC bucket counters / min-max / area / ticket
-  Tensor fwd_ticket;  // arrival counter of the forward's last-block reduction
-  // the backward's scratch (wh::fm_bwd_layout bytes) per stream, grow-only:
-  // reused in stream order by the next backward on the same stream (eight
-  // allocations per call were ~20 us of host time, the bound of the
-  // small-minibatch multi-shard step)
-  std::map<hipStream_t, Tensor> bwd_scratch;
-};
 
 DevWs& dev_ws(const torch::Device& d) {
   static std::vector<DevWs*> ws(64, nullptr);
@@ -92,302 +71,6 @@ Tensor scan_excl(const Tensor& in) {
     wh::scan_i64(ptr<int64_t>(in), ptr<int64_t>(o), n, ptr<int64_t>(tmp), cur_stream(in));
   }
   return o;
-}
-
-// --------------------------------------------------------------------- FM
-// The row strides fm.hip has kernels for: 0 (linear) or 4 * 2^k <= 256 floats
-// (a lane group of 1..64 lanes, a float4 each). Checked before anything
-// else, so no tensor of a call with another stride is ever looked at.
-static void check_vstride(int64_t vstride) {
-  TORCH_CHECK(vstride == 0 || (vstride >= 4 && vstride <= 256 && (vstride & (vstride - 1)) == 0),
-              "vstride must be 0 or 4 * 2^k <= 256, got ", vstride);
-}
-
-// difacto: w_or_hdr = hdr [U,2], vc = [m, vstride]; linear: w_or_hdr = w [U]
-std::vector<Tensor> fm_forward(const Tensor& offset, const Tensor& lid,
-                               const c10::optional<Tensor>& val, const Tensor& w_or_hdr,
-                               const c10::optional<Tensor>& vc, int64_t vstride,
-                               const Tensor& label, int64_t loss, const Tensor& met) {
-  check_vstride(vstride);
-  CHECK_IN(offset, torch::kInt64);
-  CHECK_IN(lid, torch::kInt32);
-  CHECK_IN(w_or_hdr, torch::kFloat32);
-  CHECK_IN(label, torch::kFloat32);
-  CHECK_IN(met, torch::kFloat64);
-  TORCH_CHECK(met.numel() >= 4, "met needs 4 doubles");
-  const int64_t nrows = offset.numel() - 1;
-  TORCH_CHECK(label.numel() == nrows, "label size mismatch");
-  const float* vcp = nullptr;
-  if (vstride > 0) {
-    TORCH_CHECK(w_or_hdr.dim() == 2 && w_or_hdr.size(1) == 2, "hdr must be [U, 2]");
-    TORCH_CHECK(vc.has_value() && vc->defined(), "vc required");
-    CHECK_IN((*vc), torch::kFloat32);
-    TORCH_CHECK(vc->numel() == 0 || (vc->dim() == 2 && vc->size(1) == vstride), "vc must be [m, vstride]");
-    vcp = vc->numel() ? ptr<float>(*vc) : nullptr;
-  }
-  const float* vp = optptr<float>(val);
-  c10::DeviceGuard g(offset.device());
-  // py, dual, xv and the metric partials from ONE allocation (the views keep
-  // it alive; four allocations were host time of the small-minibatch step)
-  Carve c;
-  const int64_t nxv = vstride > 0 ? nrows * vstride : 0;
-  const int64_t o_py = c.add(nrows * 4), o_du = c.add(nrows * 4), o_xv = c.add(nxv * 4),
-                o_pt = c.add(wh::fm_fwd_partials() * 8);
-  c.alloc(offset.options());
-  auto py = c.view(o_py, nrows, torch::kFloat32);
-  auto dual = c.view(o_du, nrows, torch::kFloat32);
-  auto xv = c.view(o_xv, nxv, torch::kFloat32);
-  auto part = c.view(o_pt, wh::fm_fwd_partials(), torch::kFloat64);
-  // a 5th metric slot asks for the per-minibatch flipped accuracy (linear)
-  const int lossf = (int)loss | (met.numel() >= 5 ? 256 : 0);
-  wh::fm_forward(nrows, ptr<int64_t>(offset), ptr<int32_t>(lid), vp, ptr<float>(w_or_hdr), vcp,
-                 (int)vstride, ptr<float>(label), lossf, ptr<float>(py), ptr<float>(dual),
-                 vstride > 0 ? ptr<float>(xv) : nullptr, ptr<double>(met), ptr<double>(part),
-                 ptr<unsigned int>(dev_ws(offset.device()).fwd_ticket), cur_stream(offset));
-  return {py, dual, xv};
-}
-
-// The backward's outputs and scratch: {gw [U], gvc [vc_rows, vstride] (linear:
-// empty), scratch [wh::fm_bwd_layout bytes]}. from_ws: the scratch is the
-// current stream's grow-only workspace, good until the next backward on that
-// stream; otherwise fresh memory (a plan outlives the call, and L-BFGS's
-// spmv_t must not pin a data-set-sized buffer).
-static std::vector<Tensor> fm_bwd_alloc(const Tensor& csc_off, int64_t nnz, int64_t vc_rows,
-                                        int64_t vstride, bool from_ws) {
-  auto f32 = csc_off.options().dtype(torch::kFloat32);
-  auto u8 = csc_off.options().dtype(torch::kUInt8);
-  const int64_t U = csc_off.numel() - 1;
-  const int64_t need = wh::fm_bwd_layout(U, nnz, (int)vstride, deterministic());
-  Tensor fresh;
-  Tensor& scratch = from_ws ? dev_ws(csc_off.device()).bwd_scratch[cur_stream(csc_off)] : fresh;
-  if (!scratch.defined() || scratch.numel() < need)
-    scratch = torch::empty({from_ws ? need + need / 4 : need}, u8);
-  return {torch::empty({U}, f32),
-          vstride > 0 ? torch::empty({vc_rows, vstride}, f32) : torch::empty({0}, f32), scratch};
-}
-
-// The fused update of a backward (wh::FmBwdProblem::fuse_v): the table's V
-// and VG slabs and the store's hyper-parameters.
-struct FmFuse {
-  float *v, *vg;
-  wh::DifactoHP hp;
-};
-
-// two_pass: plan without the look-back scan (count -> scan -> fill), the
-// path of more keys than the scan has tiles
-static void fm_bwd_launch(const std::vector<Tensor>& pl, const Tensor& csc_off,
-                          const Tensor& csc_row, const float* csc_val, const float* dual,
-                          const float* xv, const float* hdr, const float* vc, int64_t vstride,
-                          int64_t nrows, wh::FmBwdPhase phase, bool two_pass = false,
-                          const FmFuse* fuse = nullptr) {
-  wh::FmBwdProblem p;
-  p.nuniq = csc_off.numel() - 1;
-  p.nnz = csc_row.numel();
-  p.nrows = nrows;
-  p.csc_off = ptr<int64_t>(csc_off);
-  p.csc_row = ptr<int32_t>(csc_row);
-  p.csc_val = csc_val;
-  p.dual = dual;
-  p.xv = xv;
-  p.hdr = hdr;
-  p.vc = vc;
-  p.vstride = (int)vstride;
-  p.gw = ptr<float>(pl[0]);
-  p.gvc = pl[1].numel() ? ptr<float>(pl[1]) : nullptr;
-  p.deterministic = deterministic();
-  if (fuse) {
-    p.fuse_v = fuse->v;
-    p.fuse_vg = fuse->vg;
-    p.fuse_hp = fuse->hp;
-  }
-  const wh::Lookback lb = lookback(csc_off.device());
-  wh::fm_backward(p, pl[2].data_ptr(), two_pass ? nullptr : &lb, cur_stream(csc_off), phase);
-}
-
-static void fm_bwd_check(const Tensor& csc_off, const Tensor& csc_row, const Tensor& w_or_hdr,
-                         int64_t vstride) {
-  check_vstride(vstride);
-  CHECK_IN(csc_off, torch::kInt64);
-  CHECK_IN(csc_row, torch::kInt32);
-  CHECK_IN(w_or_hdr, torch::kFloat32);
-  TORCH_CHECK(w_or_hdr.numel() == (csc_off.numel() - 1) * (vstride > 0 ? 2 : 1),
-              "w/hdr must have U rows");
-}
-
-// the dual / xv dependent inputs of fm_backward and fm_backward_run; returns
-// the rows of vc
-static int64_t fm_bwd_check_run(const Tensor& dual, const c10::optional<Tensor>& xv,
-                                const c10::optional<Tensor>& vc, int64_t vstride) {
-  CHECK_IN(dual, torch::kFloat32);
-  if (vstride == 0) return 0;
-  TORCH_CHECK(vc.has_value() && vc->defined() && xv.has_value() && xv->defined(), "vc/xv required");
-  CHECK_IN((*vc), torch::kFloat32);
-  CHECK_IN((*xv), torch::kFloat32);
-  return vc->numel() ? vc->size(0) : 0;
-}
-
-// Where a kernel outside fm.hip (the single-shard open) writes the chunk plan
-// of a backward whose buffers `pl` (fm_bwd_alloc) exist already.
-static wh::FmBwdPlanDst fm_bwd_plan_dst(const std::vector<Tensor>& pl, const Tensor& csc_off,
-                                        int64_t nnz, int64_t nrows, int64_t vstride) {
-  wh::FmBwdProblem p = {};
-  p.nuniq = csc_off.numel() - 1;
-  p.nnz = nnz;
-  p.nrows = nrows;
-  p.csc_off = ptr<int64_t>(csc_off);
-  p.vstride = (int)vstride;
-  p.gw = ptr<float>(pl[0]);
-  p.gvc = pl[1].numel() ? ptr<float>(pl[1]) : nullptr;
-  p.deterministic = deterministic();
-  return wh::fm_bwd_plan_dst(p, pl[2].data_ptr());
-}
-
-// returns (gw [U], gvc [like vc]) (linear: gvc is empty); fuse (the native
-// step only): single-chunk keys' gvc rows are not written, see FmBwdProblem;
-// planned (the native step only): fm_bwd_alloc's buffers of this call, into
-// which the open has written the chunk plan
-static std::vector<Tensor> fm_backward_impl(const Tensor& csc_off, const Tensor& csc_row,
-                                            const c10::optional<Tensor>& csc_val,
-                                            const Tensor& dual, const c10::optional<Tensor>& xv,
-                                            const Tensor& w_or_hdr,
-                                            const c10::optional<Tensor>& vc, int64_t vstride,
-                                            const FmFuse* fuse,
-                                            const std::vector<Tensor>* planned = nullptr) {
-  fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
-  const int64_t vrows = fm_bwd_check_run(dual, xv, vc, vstride);
-  c10::DeviceGuard g(csc_off.device());
-  if (planned) {
-    TORCH_CHECK((*planned)[1].numel() == vrows * vstride, "backward: gvc rows differ from vc's");
-    fm_bwd_launch(*planned, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
-                  optptr<float>(xv), ptr<float>(w_or_hdr), optptr<float>(vc), vstride,
-                  dual.numel(), wh::FmBwdPhase::kBucketRun, false, fuse);
-    return {(*planned)[0], (*planned)[1]};
-  }
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vrows, vstride, true);
-  fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
-                vstride > 0 ? optptr<float>(xv) : nullptr, ptr<float>(w_or_hdr),
-                vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
-                wh::FmBwdPhase::kAll, false, fuse);
-  return {pl[0], pl[1]};
-}
-
-std::vector<Tensor> fm_backward(const Tensor& csc_off, const Tensor& csc_row,
-                                const c10::optional<Tensor>& csc_val, const Tensor& dual,
-                                const c10::optional<Tensor>& xv, const Tensor& w_or_hdr,
-                                const c10::optional<Tensor>& vc, int64_t vstride) {
-  return fm_backward_impl(csc_off, csc_row, csc_val, dual, xv, w_or_hdr, vc, vstride, nullptr);
-}
-
-// Phase 1 of the backward on the CURRENT stream (the planning that needs no
-// dual: chunk lists, zeroed multi-chunk gradients, V-chunk bucketing); the
-// returned plan is finished by fm_backward_run (same CSC / header / vc).
-// two_pass (tests): see fm_bwd_launch.
-std::vector<Tensor> fm_backward_plan(const Tensor& csc_off, const Tensor& csc_row,
-                                     const Tensor& w_or_hdr, int64_t vc_rows, int64_t nrows,
-                                     int64_t vstride, bool two_pass) {
-  fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
-  TORCH_CHECK(vc_rows >= 0 && nrows >= 0, "bad sizes");
-  c10::DeviceGuard g(csc_off.device());
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vc_rows, vstride, false);
-  fm_bwd_launch(pl, csc_off, csc_row, nullptr, nullptr, nullptr, ptr<float>(w_or_hdr), nullptr,
-                vstride, nrows, wh::FmBwdPhase::kPlan, two_pass);
-  return pl;
-}
-
-std::vector<Tensor> fm_backward_run(const std::vector<Tensor>& plan, const Tensor& csc_off,
-                                    const Tensor& csc_row, const c10::optional<Tensor>& csc_val,
-                                    const Tensor& dual, const c10::optional<Tensor>& xv,
-                                    const Tensor& w_or_hdr, const c10::optional<Tensor>& vc,
-                                    int64_t vstride) {
-  fm_bwd_check(csc_off, csc_row, w_or_hdr, vstride);
-  const int64_t vrows = fm_bwd_check_run(dual, xv, vc, vstride);
-  // the plan is fm_bwd_alloc's fresh triple for this call's sizes. The
-  // scratch must have exactly the layout's bytes: with U and vstride fixed
-  // by gw / gvc, every region grows with nnz, so equal totals mean equal
-  // region offsets, and the kernels find the lists where the plan wrote them
-  TORCH_CHECK(plan.size() == 3, "fm_backward_run: not a backward plan");
-  const Tensor &gw = plan[0], &gvc = plan[1], &scratch = plan[2];
-  CHECK_IN(gw, torch::kFloat32);
-  CHECK_IN(gvc, torch::kFloat32);
-  CHECK_IN(scratch, torch::kUInt8);
-  const int64_t U = csc_off.numel() - 1;
-  TORCH_CHECK(gw.numel() == U, "fm_backward_run: U differs from the plan's");
-  TORCH_CHECK(vstride > 0 ? gvc.dim() == 2 && gvc.size(0) == vrows && gvc.size(1) == vstride
-                          : gvc.numel() == 0,
-              "fm_backward_run: vc rows or vstride differ from the plan's");
-  TORCH_CHECK(scratch.numel() == wh::fm_bwd_layout(U, csc_row.numel(), (int)vstride, deterministic()),
-              "fm_backward_run: the plan was made for a CSC of another size");
-  c10::DeviceGuard g(csc_off.device());
-  // a plan allocated on a side stream is finished on this one, and the
-  // caller may drop it as soon as the call returns
-  for (const Tensor& t : plan)
-    if (t.numel())
-      c10::hip::HIPCachingAllocator::recordStream(
-          t.storage().data_ptr(), c10::hip::getCurrentHIPStream(csc_off.device().index()));
-  fm_bwd_launch(plan, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(dual),
-                vstride > 0 ? optptr<float>(xv) : nullptr, ptr<float>(w_or_hdr),
-                vstride > 0 ? optptr<float>(vc) : nullptr, vstride, dual.numel(),
-                wh::FmBwdPhase::kRun);
-  return {gw, gvc};
-}
-
-// (tests) KVStore::difacto_open_pull with the backward's chunk plan emitted by
-// the open, then the V-chunk bucketing: returns (slot, hdr, vc, vpos, plan),
-// plan as fm_backward_plan returns it, for fm_backward_run. The plan is
-// empty where the open fell back (DifactoStep then plans in the backward).
-py::tuple difacto_open_pull_plan(KVStore& store, const Tensor& keys, bool insert,
-                                 const c10::optional<Tensor>& cnt, const std::vector<double>& h,
-                                 int64_t threshold, bool l1_shrk, int64_t seed, bool direct,
-                                 const Tensor& csc_off, const Tensor& csc_row, int64_t nrows) {
-  CHECK_IN(csc_off, torch::kInt64);
-  CHECK_IN(csc_row, torch::kInt32);
-  TORCH_CHECK(csc_off.numel() == keys.numel() + 1, "open_pull_plan: csc_off must have U + 1");
-  c10::DeviceGuard g(keys.device());
-  const int64_t vstride = store.vstride();
-  check_vstride(vstride);
-  TORCH_CHECK(vstride > 0, "open_pull_plan: an embedding store");
-  const int64_t vrows = direct ? store.V_.size(0) : keys.numel();
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), vrows, vstride, false);
-  const wh::FmBwdPlanDst dst = fm_bwd_plan_dst(pl, csc_off, csc_row.numel(), nrows, vstride);
-  bool planned = false;
-  auto o = store.difacto_open_pull(keys, insert, cnt, h, threshold, l1_shrk, seed, direct, &dst,
-                                   &planned);
-  if (!planned) return py::make_tuple(o[0], o[1], o[2], o[3], std::vector<Tensor>());
-  fm_bwd_launch(pl, csc_off, csc_row, nullptr, nullptr, nullptr, ptr<float>(o[1]), nullptr,
-                vstride, nrows, wh::FmBwdPhase::kBucket);
-  return py::make_tuple(o[0], o[1], o[2], o[3], pl);
-}
-
-// (tests) the chunk totals {scalar, V} of a backward plan, a device int64 [2]
-Tensor fm_backward_plan_totals(const std::vector<Tensor>& plan, const Tensor& csc_off,
-                               int64_t nnz, int64_t vstride) {
-  TORCH_CHECK(plan.size() == 3, "not a backward plan");
-  const wh::FmBwdPlanDst d = fm_bwd_plan_dst(plan, csc_off, nnz, 0, vstride);
-  const int64_t base = reinterpret_cast<int64_t>(plan[2].data_ptr());
-  const int64_t a = reinterpret_cast<int64_t>(d.tot_s) - base;
-  const int64_t b = reinterpret_cast<int64_t>(d.tot_v) - base;
-  auto i64 = plan[2].view(torch::kInt64);
-  return torch::stack({i64[a / 8], i64[b / 8]});
-}
-
-// gvc [mcap, vstride]; m: device int64 tensor holding the live row count
-void fm_grad_post(const Tensor& gvc, const Tensor& m, int64_t dim, double clip, double dropout,
-                  int64_t seed, bool normalize) {
-  CHECK_IN(gvc, torch::kFloat32);
-  CHECK_IN(m, torch::kInt64);
-  if (gvc.numel() == 0) return;
-  TORCH_CHECK(gvc.dim() == 2, "gvc must be [m, vstride]");
-  const int64_t vstride = gvc.size(1);
-  c10::DeviceGuard g(gvc.device());
-  auto s = cur_stream(gvc);
-  Tensor sumsq;
-  if (normalize) sumsq = torch::zeros({1}, gvc.options().dtype(torch::kFloat64));
-  wh::fm_grad_post(ptr<int64_t>(m), gvc.size(0), ptr<float>(gvc), (int)vstride, (int)dim,
-                   (float)clip, (float)dropout, (uint64_t)seed,
-                   normalize ? ptr<double>(sumsq) : nullptr, s);
-  if (normalize)
-    wh::fm_grad_scale(ptr<int64_t>(m), gvc.size(0), ptr<float>(gvc), (int)vstride, (int)dim,
-                      ptr<double>(sumsq), s);
 }
 
 // worker side of the multi-shard exchange (psx.hip). rbuf: the received pull
@@ -567,21 +250,28 @@ HostSplit* host_split(const char* name) {
 
 // -------------------------------------------------------------- metrics
 void auc_after_side(c10::DeviceIndex d, hipStream_t s);
-// auc_sum[0] += exact AUC of (py, label) (sort-free bucketed rank sum)
-void auc_acc(const Tensor& py, const Tensor& label, const Tensor& auc_sum) {
+static void auc_check(const Tensor& py, const Tensor& label, const Tensor& auc_sum) {
   CHECK_IN(py, torch::kFloat32);
   CHECK_IN(label, torch::kFloat32);
   CHECK_IN(auc_sum, torch::kFloat64);
   TORCH_CHECK(py.numel() == label.numel(), "auc: py/label size mismatch");
   TORCH_CHECK(py.numel() < (int64_t)1 << 30, "auc: at most 2^30 examples per call");
-  c10::DeviceGuard g(py.device());
-  auc_after_side(py.device().index(), cur_stream(py));  // (the workspace is shared)
+}
+// the AUC chain on stream s, which is the current stream (the scratch is its)
+static void auc_run(const Tensor& py, const Tensor& label, const Tensor& auc_sum, hipStream_t s) {
   const int64_t n = py.numel();
   const int64_t wsb = wh::auc_ws_bytes(n);
   Tensor scratch;
   if (wsb) scratch = torch::empty({wsb}, py.options().dtype(torch::kUInt8));
   wh::auc_accumulate(ptr<float>(py), ptr<float>(label), n, dev_ws(py.device()).auc.data_ptr(),
-                     wsb ? scratch.data_ptr() : nullptr, ptr<double>(auc_sum), cur_stream(py));
+                     wsb ? scratch.data_ptr() : nullptr, ptr<double>(auc_sum), s);
+}
+// auc_sum[0] += exact AUC of (py, label) (sort-free bucketed rank sum)
+void auc_acc(const Tensor& py, const Tensor& label, const Tensor& auc_sum) {
+  auc_check(py, label, auc_sum);
+  c10::DeviceGuard g(py.device());
+  auc_after_side(py.device().index(), cur_stream(py));  // (the workspace is shared)
+  auc_run(py, label, auc_sum, cur_stream(py));
 }
 
 // The same on a per-device side stream owned here (it waits for the current
@@ -796,11 +486,7 @@ class HostAuc {
 };
 
 void auc_acc_side(const Tensor& py, const Tensor& label, const Tensor& auc_sum) {
-  CHECK_IN(py, torch::kFloat32);
-  CHECK_IN(label, torch::kFloat32);
-  CHECK_IN(auc_sum, torch::kFloat64);
-  TORCH_CHECK(py.numel() == label.numel(), "auc: py/label size mismatch");
-  TORCH_CHECK(py.numel() < (int64_t)1 << 30, "auc: at most 2^30 examples per call");
+  auc_check(py, label, auc_sum);
   // a small minibatch's AUC is ONE launch of a few microseconds (the
   // pairwise k_auc_small): it runs in order on the current stream, without
   // the side stream's event pair (~4 us of host time in a launch-bound
@@ -818,12 +504,7 @@ void auc_acc_side(const Tensor& py, const Tensor& label, const Tensor& auc_sum) 
   }
   a->dirty = true;
   c10::hip::HIPStreamGuard sg(a->s);  // the scratch is the side stream's
-  const int64_t n = py.numel();
-  const int64_t wsb = wh::auc_ws_bytes(n);
-  Tensor scratch;
-  if (wsb) scratch = torch::empty({wsb}, py.options().dtype(torch::kUInt8));
-  wh::auc_accumulate(ptr<float>(py), ptr<float>(label), n, dev_ws(py.device()).auc.data_ptr(),
-                     wsb ? scratch.data_ptr() : nullptr, ptr<double>(auc_sum), a->s.stream());
+  auc_run(py, label, auc_sum, a->s.stream());
 }
 
 void auc_join(const Tensor& auc_sum) {
@@ -962,86 +643,14 @@ Tensor gather_rows(const Tensor& in, const Tensor& idx) {
   return in.dim() > 1 ? out : out.view({idx.numel()});
 }
 
-int64_t vstride_for(int64_t dim) { return dim == 0 ? 0 : 4 * next_pow2((dim + 3) / 4); }
-
-Tensor spmv_t(const Tensor& csc_off, const Tensor& csc_row, const c10::optional<Tensor>& csc_val,
-              const Tensor& p) {
-  CHECK_IN(csc_off, torch::kInt64);
-  CHECK_IN(csc_row, torch::kInt32);
-  CHECK_IN(p, torch::kFloat32);
-  c10::DeviceGuard g(p.device());
-  // the linear backward's chunked segmented sums (fm.hip k_chunk_plan /
-  // k_bwd_scalar): a column is cut into chunks of at most a wave's width
-  // and multi-chunk columns are summed across chunks, so a power-law head
-  // (one Criteo value in a third of all rows) costs what its chunk count
-  // costs -- one lane per column serialised such a column (298 ms per
-  // L-BFGS gradient pass at 4M Criteo rows)
-  auto pl = fm_bwd_alloc(csc_off, csc_row.numel(), 0, 0, false);
-  fm_bwd_launch(pl, csc_off, csc_row, optptr<float>(csc_val), ptr<float>(p), nullptr, nullptr,
-                nullptr, 0, p.numel(), wh::FmBwdPhase::kAll);
-  return pl[0];
-}
-
 }  // namespace wh_bind
-
-#include "localize_ahead.inl"
-#include "linear_step.inl"
-#include "difacto_step.inl"
 
 PYBIND11_MODULE(_hip, m) {
   m.doc() = "wormhole_amd gfx950 HIP kernels";
   m.def("scan_excl", &scan_excl);
   bind_localize(m);
-  py::class_<LinearStep>(m, "LinearStep")
-      .def(py::init<KVStore*, int64_t, double, double, double, double, int64_t, double, bool>(),
-           py::arg("store"), py::arg("algo"), py::arg("alpha"), py::arg("beta"), py::arg("l1"),
-           py::arg("l2"), py::arg("loss"), py::arg("max_load") = 0.7, py::arg("direct") = true,
-           py::keep_alive<1, 2>())
-      .def("step", &LinearStep::step, py::arg("keys"), py::arg("offset"), py::arg("val"),
-           py::arg("label"), py::arg("train"), py::arg("met"), py::arg("auc_sum"),
-           py::arg("next_keys") = py::none(), py::arg("next_offset") = py::none(),
-           py::arg("next_val") = py::none(), py::arg("ready") = 0)
-      .def("reset", &LinearStep::reset)
-      .def("guard_sync", &LinearStep::guard_sync)
-      .def_property_readonly("grows", &LinearStep::grows)
-      .def_property_readonly("direct", [](const LinearStep& l) { return l.direct(); })
-      .def_property("pushes", &LinearStep::pushes, &LinearStep::set_pushes);
+  bind_fm(m);  // LinearStep, DifactoStep, fm_*, spmv_t (before KVStore: their signatures)
   bind_psx(m);  // RcclComm, PSX_TX_*, PsxStep, a2a_plan, c10d_a2a_rows
-  py::class_<DifactoStep>(m, "DifactoStep")
-      .def(py::init<KVStore*, std::vector<double>, int64_t, bool, int64_t, int64_t,
-                    std::vector<double>, double, bool, bool>(),
-           py::arg("store"), py::arg("hp"), py::arg("threshold"), py::arg("l1_shrk"),
-           py::arg("seed"), py::arg("loss"), py::arg("post"), py::arg("max_load"),
-           py::arg("direct"), py::arg("fused_v") = true, py::keep_alive<1, 2>())
-      .def("step", &DifactoStep::step, py::arg("keys"), py::arg("offset"), py::arg("val"),
-           py::arg("label"), py::arg("train"), py::arg("data_pass"), py::arg("met"),
-           py::arg("auc_sum"), py::arg("step"), py::arg("next_keys") = py::none(),
-           py::arg("next_offset") = py::none(), py::arg("next_val") = py::none(),
-           py::arg("ready") = 0)
-      .def("reset", &DifactoStep::reset)
-      .def("guard_sync", &DifactoStep::guard_sync)
-      .def_property_readonly("direct", &DifactoStep::direct)
-      .def_property_readonly("fused_v", &DifactoStep::fused_v)
-      .def_property_readonly("grows", &DifactoStep::grows)
-      .def_property_readonly("vgrows", &DifactoStep::vgrows);
-  m.def("fm_forward", &fm_forward);
-  m.def("set_cu_reserve", [](int64_t n) { wh::fm_set_cu_reserve((int)n); },
-        "CUs the persistent FM kernels leave free for concurrent collectives");
-  m.def("cu_reserve", []() { return (int64_t)wh::fm_cu_reserve(); });
-  m.def("fm_backward", &fm_backward);
-  m.def("fm_backward_plan", &fm_backward_plan, py::arg("csc_off"), py::arg("csc_row"),
-        py::arg("hdr"), py::arg("vc_rows"), py::arg("nrows"), py::arg("vstride"),
-        py::arg("two_pass") = false);
-  m.def("fm_backward_run", &fm_backward_run);
-  m.def("difacto_open_pull_plan", &difacto_open_pull_plan, py::arg("store"), py::arg("keys"),
-        py::arg("insert"), py::arg("cnt"), py::arg("h"), py::arg("threshold"),
-        py::arg("l1_shrk"), py::arg("seed"), py::arg("direct"), py::arg("csc_off"),
-        py::arg("csc_row"), py::arg("nrows"),
-        "(tests) the open with the backward's chunk plan: (slot, hdr, vc, vpos, plan)");
-  m.def("fm_backward_plan_totals", &fm_backward_plan_totals, py::arg("plan"),
-        py::arg("csc_off"), py::arg("nnz"), py::arg("vstride"),
-        "(tests) a backward plan's chunk totals {scalar, V}");
-  m.def("fm_grad_post", &fm_grad_post);
   m.def("vidx_renumber", &vidx_renumber);
   m.def("ps_unpack", &ps_unpack);
   m.def("ps_pack_gw", &ps_pack_gw);
@@ -1066,14 +675,11 @@ PYBIND11_MODULE(_hip, m) {
   m.def("auc_sorted", &auc_sorted);
   m.def("synth_criteo", &synth_criteo);
   m.def("gather_rows", &gather_rows);
-  m.def("vstride_for", &vstride_for);
   // the stateless families, each from its own translation unit
   bind_bsp(m);
   bind_gbdt(m);
   bind_kmeans(m);
   bind_ingest(m);
-  m.def("spmv_t", &spmv_t, py::arg("csc_off"), py::arg("csc_row"), py::arg("csc_val"),
-        py::arg("p"));
   py::class_<KVStore>(m, "KVStore")
       .def(py::init<int64_t, int64_t, int64_t, int64_t>(), py::arg("cap"), py::arg("vcap"),
            py::arg("dim"), py::arg("device"))

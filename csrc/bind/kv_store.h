@@ -1,6 +1,6 @@
 // The parameter store of one shard (module class _hip.KVStore): the slot
 // table, the V slabs and every op on them. Shared by hip_ops.cc, which binds
-// it to Python, and the native steps (hip_ops.cc, psx_ops.cc).
+// it to Python, and the native steps (fm_ops.cc, psx_ops.cc).
 #pragma once
 #include "bind_common.h"
 

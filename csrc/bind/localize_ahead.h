@@ -1,10 +1,20 @@
-// The localize look-ahead of LinearStep and DifactoStep (included by
-// hip_ops.cc before linear_step.inl and difacto_step.inl): the NEXT
-// minibatch's localize begins on the localize stream while this one trains
-// on the compute stream S; the next call takes its outputs, or localizes on
-// S when no job was begun for its minibatch. Both streams use the device's
-// localize workspace (localize_ops.cc; the job's interface is
-// localize_job.h).
+// The localize look-ahead of the single-shard steps (LinearStep and
+// DifactoStep, fm_ops.cc): the NEXT minibatch's localize begins on the
+// localize stream while this one trains on the compute stream S; the next
+// call takes its outputs, or localizes on S when no job was begun for its
+// minibatch. Both streams use the device's localize workspace
+// (localize_ops.cc; the job's interface is localize_job.h).
+#pragma once
+#include "localize_job.h"
+#include "ps_ops.h"
+
+#include <c10/hip/HIPCachingAllocator.h>
+#include <c10/hip/HIPGuard.h>
+
+#include <memory>
+
+namespace wh_bind {
+
 class LocalizeAhead {
  public:
   explicit LocalizeAhead(const c10::Device& device) : dev_(device.index()) {
@@ -64,11 +74,8 @@ class LocalizeAhead {
     // read on the localize stream now and on the current one by the next step
     record(nk, true);
     record(no, true);
-    c10::optional<Tensor> nv;
-    if (nval.has_value() && nval->defined() && nval->numel()) {
-      nv = *nval;
-      record(*nval, true);
-    }
+    const c10::optional<Tensor> nv = present(nval) ? nval : c10::nullopt;
+    if (nv) record(*nv, true);
     c10::hip::HIPStreamGuard sg(ls_);
     job_ = std::make_unique<LocalizeJob>(nk, no, nv, 1, hint_, py::none());
     job_keys_ = nk;
@@ -97,3 +104,5 @@ class LocalizeAhead {
   bool s_job_ = false;  // a localize used the workspace on S since the last begin
   int64_t hint_ = 0;    // the last minibatch's unique keys (the job's table size)
 };
+
+}  // namespace wh_bind

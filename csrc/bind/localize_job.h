@@ -1,7 +1,8 @@
 // The localize job: a minibatch's global keys -> (unique keys, local ids,
 // CSC) on the device, with one host read. Defined in localize_ops.cc; used by
-// the native steps (LocalizeAhead in hip_ops.cc, PsxStep in psx_ops.cc) and
-// bound to Python as _hip.LocalizeJob / _hip.localize.
+// the native steps (LocalizeAhead, localize_ahead.h, of the single-shard
+// steps in fm_ops.cc; PsxStep in psx_ops.cc) and bound to Python as
+// _hip.LocalizeJob / _hip.localize.
 #pragma once
 #include "bind_common.h"
 

@@ -1,4 +1,4 @@
-// The store guard of the native steps DifactoStep (hip_ops.cc) and PsxStep
+// The store guard of the native steps DifactoStep (fm_ops.cc) and PsxStep
 // (psx_ops.cc).
 #pragma once
 #include "kv_store.h"

@@ -1,8 +1,8 @@
 // The store guard's arithmetic (kv/__init__.py StoreGuard.before_open is the
 // Python twin): how many keys / embedding rows the coming open may need, and
 // the capacity that holds them. Free of HIP and torch: the native steps
-// (csrc/bind/store_guard.h, LinearStep for the table rule) and the host
-// self-test compile the same code.
+// (csrc/bind/store_guard.h; LinearStep's guard, linear_guard_plan.h, shares
+// the table rule) and the host self-test compile the same code.
 #pragma once
 
 #include <algorithm>

@@ -7,7 +7,7 @@
 // and RecordIO), the multi-threaded ordered ThreadedReader / MinibatchIter,
 // the conf parser, the WorkloadPool under concurrent workers and the
 // control-plane transport (Van) with live reader threads; and the pure
-// arithmetic of the exact AUC, of the store guard's growth plan, of the
+// arithmetic of the exact AUC, of the two store guards' plans, of the
 // localize job's bookkeeping and of the GBDT histogram task lists.
 #include <atomic>
 #include <cstdio>
@@ -22,6 +22,7 @@
 #include "host/gbdt_hist_plan.h"
 #include "host/io.h"
 #include "host/json.h"
+#include "host/linear_guard_plan.h"
 #include "host/localize_plan.h"
 #include "host/parsers.h"
 #include "host/psx_plan.h"
@@ -337,6 +338,80 @@ static void test_store_guard_plan() {
   EXPECT(wh::grown_vcap(1, 0) == 1 && wh::grown_vcap(64, 64) == 64 && wh::grown_vcap(65, 64) == 128);
 }
 
+// LinearStep's guard plan as the step drives it (guard_before: grow_target;
+// guard_after: due; guard_read: summarised), at cap = 4096 and max_load 0.7.
+// This guard has no Python twin: the expected values are worked out here from
+// the rule "no summary when unforced, not the 8th unforced call, and
+// bound + 8 n < 0.9 * max_load * cap", with max_load * cap = 2867.2 and
+// 0.9 * 2867.2 = 2580.48, and bound = base_keys + (issued - base_issued).
+static void test_linear_guard_plan() {
+  const int64_t cap = 4096;
+  const double ml = 0.7;
+  EXPECT(wh::LinearGuardPlan::kGuardEvery == 8);
+  {
+    // steady cadence: opens of 10 ids from an empty table. After call k the
+    // bound is 10 k, and 10 k + 80 <= 240 is far below 2580.48: only the
+    // counter makes a summary due, at calls 8 and 16
+    wh::LinearGuardPlan p;
+    for (int k = 1; k <= 16; ++k) EXPECT(p.due(10, cap, ml, false) == (k == 8 || k == 16));
+    EXPECT(p.issued == 160 && p.bound() == 160 && p.step == 16);
+    // a summary applied: 50 keys when 80 ids had been issued (ids repeat
+    // across minibatches, so 50 < 80); 80 more were issued since
+    p.summarised(50, 80);
+    EXPECT(p.base_keys == 50 && p.base_issued == 80 && p.bound() == 50 + 80);
+    // a stale summary (stamped 40, read after the one stamped 80) is dropped
+    p.summarised(45, 40);
+    EXPECT(p.base_keys == 50 && p.base_issued == 80 && p.bound() == 130);
+    // one with the same stamp (guard_sync's forced summary of 0 ids) counts
+    p.summarised(48, 80);
+    EXPECT(p.base_keys == 48 && p.bound() == 128);
+  }
+  {
+    // near the load limit: a base of 2500 keys. Call k: bound = 2500 + 10 k,
+    // and 2500 + 10 + 80 = 2590 >= 2580.48 already at k = 1: every call is due
+    wh::LinearGuardPlan p;
+    p.summarised(2500, 0);
+    for (int k = 1; k <= 7; ++k) EXPECT(p.due(10, cap, ml, false));
+    EXPECT(p.bound() == 2570);
+    // both sides of 0.9 * lim on a first call (the counter says no): with
+    // n = 10 the sum is base + 10 + 80; 2490 + 90 = 2580 < 2580.48 is not
+    // due, 2491 + 90 = 2581 is
+    wh::LinearGuardPlan lo, hi;
+    lo.summarised(2490, 0);
+    hi.summarised(2491, 0);
+    EXPECT(!lo.due(10, cap, ml, false));
+    EXPECT(hi.due(10, cap, ml, false));
+  }
+  {
+    // a forced call (guard_sync: n = 0) is due and leaves the cadence alone:
+    // three unforced calls, the forced one, then calls 4..7 are not due and
+    // the 8th unforced call is
+    wh::LinearGuardPlan p;
+    for (int k = 1; k <= 3; ++k) EXPECT(!p.due(10, cap, ml, false));
+    EXPECT(p.due(0, cap, ml, true));
+    EXPECT(p.step == 3 && p.issued == 30);
+    for (int k = 4; k <= 7; ++k) EXPECT(!p.due(10, cap, ml, false));
+    EXPECT(p.due(10, cap, ml, false));
+    EXPECT(p.step == 8 && p.issued == 80);
+  }
+  {
+    // grow target = grown_cap(bound + n): 2867 <= 2867.2 stays, 2868 doubles
+    // until the need fills at most half (2868 <= 4096 = 8192 / 2)
+    wh::LinearGuardPlan p;
+    p.due(2800, cap, ml, false);  // bound 2800
+    EXPECT(p.grow_target(67, cap, ml) == 4096);
+    EXPECT(p.grow_target(68, cap, ml) == 8192);
+    // "the exact count before growing": 2800 + 100 asks for 8192; the newest
+    // summary then says that the 2800 ids were 900 keys, and 900 + 100 fits
+    EXPECT(p.grow_target(100, cap, ml) == 8192);
+    p.summarised(900, 2800);
+    EXPECT(p.bound() == 900 && p.grow_target(100, cap, ml) == 4096);
+    // and one that confirms the need keeps the target: 2790 + 100 > 2867.2
+    p.summarised(2790, 2800);
+    EXPECT(p.grow_target(100, cap, ml) == 8192);
+  }
+}
+
 // the growers' histogram task lists (tasks x 5, red x 6) on literal vectors
 static void test_gbdt_hist_plan() {
   using V = std::vector<int32_t>;
@@ -595,6 +670,7 @@ static void test_psx_plan() {
 int main() {
   test_auc();
   test_store_guard_plan();
+  test_linear_guard_plan();
   test_localize_plan();
   test_psx_plan();
   test_gbdt_hist_plan();

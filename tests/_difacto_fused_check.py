@@ -2,7 +2,7 @@
 tests, the by-key model dump, and, run as a script in a fresh process started
 with WH_DETERMINISTIC=1 (the mode is read once per process), the bit-for-bit
 comparison of the native DiFacto step with and without the fused V update
-(csrc/bind/difacto_step.inl fused_v; fm.hip k_bwd_v<G, true>). Hash localize
+(csrc/bind/fm_ops.cc fused_v; fm.hip k_bwd_v<G, true>). Hash localize
 and ordered partials make the whole step repeatable there, and both variants
 call the same kv_device.h adagrad4 with fixed roundings, so every key's cnt,
 w, z, sq, V row and VG row must be the same bits. Prints OK.

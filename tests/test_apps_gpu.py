@@ -358,6 +358,50 @@ def test_native_linear_step_matches_python_step(algo):
         assert abs(x - y) <= 1e-4 * max(1.0, abs(y)), (pa, pb)
 
 
+def test_native_linear_localize_step_grows_the_table(monkeypatch):
+    """LinearStep's localize path (the one minibatches above 600 000
+    non-zeros take, forced here) with a table that has to grow: the same
+    model as the Python step, as in the direct-path test above (FTRL)."""
+    import torch
+    from wormhole_amd.config.schema import LinearConfig
+    from wormhole_amd.data.synthetic import criteo_batch
+    from wormhole_amd.models.linear import LinearLearner
+    from wormhole_amd.parallel.comm import Comm
+    from wormhole_amd.models import linear as L
+    monkeypatch.setattr(L, "DIRECT_STEP", False)
+    dev = torch.device("cuda", 0)
+    card = [50, 400, 3000, 20, 7, 900, 100000]
+    batches = [criteo_batch(3000, 5, s, dev, card) for s in range(8)]
+
+    def run(native):
+        conf = LinearConfig(algo=3, lambda_l1=0.1, lr_eta=0.1)
+        lr = LinearLearner(conf, Comm(dev, init=False), dev, cap=1 << 12, seed=1)
+        assert lr._native is not None and not lr._native.direct
+        if not native:
+            lr._native = None
+        for s, (keys, label, off) in enumerate(batches):
+            nb = (batches[s + 1][0], batches[s + 1][2], None) if s + 1 < len(batches) else None
+            lr.process(keys, off, None, label, 0, 0, next_batch=nb)
+        lr.flush()
+        prog = lr.take_progress()
+        st = lr.store
+        occ = st.occupied().long()
+        m = dict(zip(st.keys[occ].cpu().tolist(), st.w[occ].cpu().tolist()))
+        keys, label, off = criteo_batch(2000, 6, 0, dev, card)  # unseen ids too
+        py = lr.process(keys, off, None, label, 2, 0)  # PRED: no insert, no push
+        return m, prog, lr, py
+    a, pa, la, ya = run(True)
+    assert la._native.grows >= 1 and la.kv.guard.grows >= 1  # the 4096-slot table had to grow
+    b, pb, lb, yb = run(False)
+    assert lb.kv.guard.grows >= 1
+    assert torch.allclose(ya, yb, atol=1e-4, rtol=1e-4)
+    assert a.keys() == b.keys()
+    bad = sum(1 for k, w in b.items() if abs(w - a[k]) > 1e-5 * max(1.0, abs(w)))
+    assert bad <= len(b) // 1000, bad
+    for x, y in zip(pa, pb):
+        assert abs(x - y) <= 1e-4 * max(1.0, abs(y)), (pa, pb)
+
+
 def test_native_linear_lookahead_made_on_the_compute_stream(monkeypatch):
     """The file worker hands the look-ahead minibatch over without a producer
     event (slices and offset rebasing queued on the compute stream just

@@ -1,4 +1,4 @@
-"""The two fusions of the native DiFacto step (csrc/bind/difacto_step.inl).
+"""The two fusions of the native DiFacto step (csrc/bind/fm_ops.cc).
 
 The backward's chunk plan emitted by the open (kvstore.hip
 k_difacto_open_pull with a plan argument, wh_chunk_plan.h emit_key) against

@@ -1,5 +1,5 @@
 """The single-shard DiFacto step in one native call (csrc/bind/
-difacto_step.inl DifactoStep) against the op-by-op Python step it replaces
+fm_ops.cc DifactoStep) against the op-by-op Python step it replaces
 (models/difacto.py, WH_DIFACTO_NATIVE=0): the same model -- keys, feature
 counts and embedding allocation exactly, w and V to float tolerance -- the
 same progress, with and without the look-ahead localize, with the gradient

@@ -1,5 +1,5 @@
 // Host cost of the torch-side calls around a small-minibatch native step
-// (csrc/bind/difacto_step.inl): caching-allocator allocations, recordStream,
+// (csrc/bind/fm_ops.cc): caching-allocator allocations, recordStream,
 // stream / device guards, views, next to a plain kernel launch.
 // Built by tools/microbench/build_torch_host_cost.sh (g++ against libtorch,
 // no Python); run on the GPU box: ./bin/torch_host_cost

@@ -86,7 +86,7 @@ class DifactoLearner:
             from ..kv.psx import Psx
             self.psx = Psx(self)
         # one shard on the GPU: the whole minibatch in one native call
-        # (csrc/bind/difacto_step.inl; WH_DIFACTO_NATIVE=0 keeps this
+        # (csrc/bind/fm_ops.cc; WH_DIFACTO_NATIVE=0 keeps this
         # module's op-by-op step, the test oracle)
         self._nat = None
         if (self.psx is None and self.device.type == "cuda" and self.vstride > 0

@@ -16,7 +16,7 @@ from ..utils import trace
 
 TRAIN, VAL, PRED = 0, 1, 2
 # one GPU, one shard: the localize-free native step (per-tile de-duplication,
-# csrc/bind/hip_ops.cc LinearStep) up to ~15k Criteo rows; False keeps the
+# csrc/bind/fm_ops.cc LinearStep) up to ~15k Criteo rows; False keeps the
 # localize path at every size (the tests' cross-check of the two)
 DIRECT_STEP = True
 
@@ -63,7 +63,7 @@ class LinearLearner:
             from ..kv.psx import Psx
             self.psx = Psx(self)
         # one GPU, one shard: the whole step is one native call
-        # (csrc/bind/hip_ops.cc LinearStep) -- at the reference's minibatch
+        # (csrc/bind/fm_ops.cc LinearStep) -- at the reference's minibatch
         # of 10000 rows the Python glue of the step cost more host time than
         # the GPU work it launches
         self._native = None
