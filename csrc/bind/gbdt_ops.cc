@@ -11,6 +11,7 @@
 #include <utility>
 
 #include "host/gbdt_hist_plan.h"
+#include "host/gbdt_level_plan.h"
 
 namespace wh_bind {
 namespace {
@@ -98,6 +99,16 @@ void gbdt_hist(const Tensor& B, int64_t nbin, const Tensor& ridx, const Tensor& 
          cx.part(tasks.size(0)), hist, nullptr);
 }
 
+// The best split of each of S slots into out [S, 6] {gain, feature, bin, dir,
+// GL, HL}: hist [S, F, nbin, 2], totals [S x 2] and the [F x nbin] candidate
+// mask on hist's device. False: the kernel refused (nbin > 1024 or no input).
+bool split_search(const Tensor& hist, const double* totals, const uint8_t* valid, int S,
+                  double alpha, double lambda, double mcw, const Tensor& out, hipStream_t s) {
+  auto cand = torch::empty({std::max<int64_t>(S * hist.size(1) * 4, 1)}, hist.options());
+  return wh::gbdt_split(ptr<double>(hist), totals, valid, S, (int)hist.size(1), (int)hist.size(2),
+                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s);
+}
+
 Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid, double alpha,
                   double lambda, double min_child_weight) {
   CHECK_IN(hist, torch::kFloat64);
@@ -109,11 +120,8 @@ Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid,
   TORCH_CHECK(totals.numel() == 2 * (int64_t)S, "totals must be [S, 2]");
   TORCH_CHECK(valid.numel() == (int64_t)F * nbin, "valid must be [F, nbin]");
   auto out = torch::empty({S, 6}, hist.options());
-  auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 4, 1)}, hist.options());
-  TORCH_CHECK(wh::gbdt_split(ptr<double>(hist), ptr<double>(totals),
-                             reinterpret_cast<const uint8_t*>(valid.data_ptr()), S, F, nbin,
-                             alpha, lambda, min_child_weight, ptr<double>(cand), ptr<double>(out),
-                             cur_stream(hist)),
+  TORCH_CHECK(split_search(hist, ptr<double>(totals), ptr<uint8_t>(valid), S, alpha, lambda,
+                           min_child_weight, out, cur_stream(hist)),
               "gbdt_split: nbin > 1024 or empty input");
   return out;
 }
@@ -126,6 +134,28 @@ Tensor gbdt_seg_fill(const Tensor& beg, const Tensor& node, int64_t n) {
   auto out = torch::empty({n}, beg.options());
   wh::gbdt_seg_fill(ptr<int32_t>(beg), ptr<int32_t>(node), (int)beg.numel(), n, ptr<int32_t>(out),
                     cur_stream(beg));
+  return out;
+}
+
+// The stable partition of the split nodes' rows from their go-left flags
+// (left [n], one per ridx position): scan of the flags, per-node left counts
+// nleft[node] = lscan[seg_end] - lscan[seg_beg], scatter. The counts are
+// copied into *nleft when it is defined, else *nleft becomes them; the new
+// ridx is written to out (allocated here unless the caller did) and returned.
+Tensor partition_by_flags(const Tensor& ridx, const Tensor& pos_node, const Tensor& left,
+                          const int32_t* node_feat, const Tensor& seg_beg, const Tensor& seg_end,
+                          Tensor* nleft, Tensor out, hipStream_t s) {
+  const int64_t n = ridx.numel();
+  auto lscan = torch::empty({n + 1}, ridx.options().dtype(torch::kInt64));
+  auto tmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
+  wh::scan_i32(ptr<int32_t>(left), ptr<int64_t>(lscan), n, ptr<int64_t>(tmp), s);
+  auto nl = (lscan.index_select(0, seg_end.to(torch::kInt64)) -
+             lscan.index_select(0, seg_beg.to(torch::kInt64))).to(torch::kInt32);
+  *nleft = nleft->defined() ? nleft->copy_(nl) : nl;
+  if (!out.defined()) out = torch::empty_like(ridx);
+  wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), node_feat,
+                   ptr<int32_t>(seg_beg), ptr<int32_t>(*nleft), ptr<int32_t>(left),
+                   ptr<int64_t>(lscan), ptr<int32_t>(out), s);
   return out;
 }
 
@@ -151,18 +181,8 @@ Tensor gbdt_partition(const Tensor& B, const Tensor& ridx, const Tensor& pos_nod
   wh::gbdt_goleft(ptr<uint8_t>(B), bc, B.size(0), (int)B.size(1), ptr<int32_t>(ridx), n,
                   ptr<int32_t>(pos_node), ptr<int32_t>(node_feat), ptr<int32_t>(node_bin),
                   ptr<uint8_t>(node_defl), ptr<int32_t>(left), s);
-  auto lscan = torch::empty({n + 1}, ridx.options().dtype(torch::kInt64));
-  auto tmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-  wh::scan_i32(ptr<int32_t>(left), ptr<int64_t>(lscan), n, ptr<int64_t>(tmp), s);
-  // nleft[node] = lscan[end] - lscan[beg]
-  auto nl = (lscan.index_select(0, seg_end.to(torch::kInt64)) -
-             lscan.index_select(0, seg_beg.to(torch::kInt64))).to(torch::kInt32);
-  nleft_out.copy_(nl);
-  auto out = torch::empty_like(ridx);
-  wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), ptr<int32_t>(node_feat),
-                   ptr<int32_t>(seg_beg), ptr<int32_t>(nleft_out), ptr<int32_t>(left),
-                   ptr<int64_t>(lscan), ptr<int32_t>(out), s);
-  return out;
+  return partition_by_flags(ridx, pos_node, left, ptr<int32_t>(node_feat), seg_beg, seg_end,
+                            &nleft_out, Tensor(), s);
 }
 
 void gbdt_leaf_add(const Tensor& ridx, const Tensor& pos_node, const Tensor& leaf,
@@ -382,17 +402,8 @@ Tensor gbdt_partition_csr(const Tensor& row_off, const Tensor& fid, const Tensor
                       ptr<int32_t>(cut_off), ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node),
                       ptr<int32_t>(node_feat), ptr<int32_t>(node_bin), ptr<uint8_t>(node_defl),
                       ptr<int32_t>(left), s);
-  auto lscan = torch::empty({n + 1}, ridx.options().dtype(torch::kInt64));
-  auto tmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-  wh::scan_i32(ptr<int32_t>(left), ptr<int64_t>(lscan), n, ptr<int64_t>(tmp), s);
-  auto nl = (lscan.index_select(0, seg_end.to(torch::kInt64)) -
-             lscan.index_select(0, seg_beg.to(torch::kInt64))).to(torch::kInt32);
-  nleft_out.copy_(nl);
-  auto out = torch::empty_like(ridx);
-  wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), ptr<int32_t>(node_feat),
-                   ptr<int32_t>(seg_beg), ptr<int32_t>(nleft_out), ptr<int32_t>(left),
-                   ptr<int64_t>(lscan), ptr<int32_t>(out), s);
-  return out;
+  return partition_by_flags(ridx, pos_node, left, ptr<int32_t>(node_feat), seg_beg, seg_end,
+                            &nleft_out, Tensor(), s);
 }
 
 void gbdt_predict_csr(const Tensor& row_off, const Tensor& fid, const c10::optional<Tensor>& val,
@@ -446,17 +457,28 @@ struct GrowCtx : HistCtx {
   }
 };
 
-// The host grower's one upload per level, as int32 word offsets (the same in
-// the pinned staging copy and on the device): node feat / bin / seg_beg /
-// seg_end [nnode], defl (bytes) [nnode], tiles beg / node [nt], split table
-// [nsplit x 4], parent slots [nsplit], the partition's left / right cursors
-// [nnode] (device-updated)
-struct NodeTables {
-  int64_t feat, bin, sb, se, defl, tb, tn, sp, par, lc, rc, nwords;
-  NodeTables(int64_t nnode, int64_t nt, int64_t nsplit)
-      : feat(0), bin(nnode), sb(2 * nnode), se(3 * nnode), defl(4 * nnode),
-        tb(defl + (nnode + 3) / 4), tn(tb + nt), sp(tn + nt), par(sp + 4 * nsplit),
-        lc(par + nsplit), rc(lc + nnode), nwords(rc + nnode) {}
+// A grown tree on the host, nodes in breadth-first creation order, and the
+// tuple both growers hand to Python (models/gbdt_tree.py RegTree.from_lists):
+// (feat, bin, cond, defl, left, right, parent, gain, cover, base weight, leaf,
+// [(leaf id, begin, end)])
+struct TreeLists {
+  std::vector<int> feat, bin, defl, left, right, parent;
+  std::vector<double> gain, cover, bw, leaf;
+
+  int add(int par) {  // a new leaf
+    feat.push_back(-1), bin.push_back(0), defl.push_back(0), left.push_back(-1),
+        right.push_back(-1), parent.push_back(par), gain.push_back(0), cover.push_back(0),
+        bw.push_back(0), leaf.push_back(0);
+    return (int)feat.size() - 1;
+  }
+
+  py::tuple pack(const std::vector<float>& cut_vals, const std::vector<int64_t>& cut_off,
+                 const py::list& segs) const {
+    std::vector<float> cond(feat.size(), 0.f);
+    for (size_t i = 0; i < feat.size(); ++i)
+      if (feat[i] >= 0) cond[i] = cut_vals[cut_off[feat[i]] + bin[i]];
+    return py::make_tuple(feat, bin, cond, defl, left, right, parent, gain, cover, bw, leaf, segs);
+  }
 };
 
 py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, const Tensor& gpair,
@@ -474,24 +496,17 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   const int64_t per = (int64_t)F * nbin * 2;
   const bool reduce = !allreduce.is_none();
   // host tree
-  std::vector<int> feat, bin, defl, left, right, parent;
-  std::vector<double> gain, cover, bw, leaf;
+  TreeLists t;
   std::vector<std::array<double, 2>> tot;
-  auto add = [&](int par) {
-    feat.push_back(-1), bin.push_back(0), defl.push_back(0), left.push_back(-1),
-        right.push_back(-1), parent.push_back(par), gain.push_back(0), cover.push_back(0),
-        bw.push_back(0), leaf.push_back(0), tot.push_back({0, 0});
-    return (int)feat.size() - 1;
-  };
+  auto add = [&](int par) { return tot.push_back({0, 0}), t.add(par); };
   auto weight = [&](double G_, double H_) {
-    if (H_ < mcw) return 0.0;
-    return -l1_threshold(G_, alpha) / (H_ + lambda);
+    return H_ < mcw ? 0.0 : -l1_threshold(G_, alpha) / (H_ + lambda);
   };
   const int root = add(-1);
   tot[root] = {root_tot[0], root_tot[1]};
   std::map<int, std::pair<int, int>> seg;  // live frontier segments (node -> [b, e))
   seg[root] = {0, (int)n};
-  std::vector<std::array<int, 3>> done;    // finished leaves: node, b, e
+  py::list segs;  // finished leaves: (node, b, e)
   // staging rings for the uploads (node tables, task lists), a plain buffer
   // for the one download per level (read right after its synchronisation)
   PinnedRing<4> up, up_tasks;
@@ -556,11 +571,8 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       auto T = up.tensor().narrow(0, 0, 16 * S).to(B.device(), true).view(torch::kFloat64);
       up.mark(s);
       split_out = torch::empty({S, 6}, f64);
-      auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 4, 1)}, f64);
-      TORCH_CHECK(wh::gbdt_split(ptr<double>(H_front), ptr<double>(T),
-                                 reinterpret_cast<const uint8_t*>(valid.data_ptr()), S, F,
-                                 (int)nbin, alpha, lambda, mcw, ptr<double>(cand),
-                                 ptr<double>(split_out), s),
+      TORCH_CHECK(split_search(H_front, ptr<double>(T), ptr<uint8_t>(valid), S, alpha, lambda, mcw,
+                               split_out, s),
                   "gbdt_split failed");
     }
     // the level's one synchronisation: split results + previous partition counts
@@ -574,9 +586,9 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     WH_HIP_CHECK_HOST(hipStreamSynchronize(s));
     resolve_pending(nl_h);
     for (int nd : frontier) {
-      cover[nd] = tot[nd][1];
-      bw[nd] = weight(tot[nd][0], tot[nd][1]);
-      leaf[nd] = eta * bw[nd];
+      t.cover[nd] = tot[nd][1];
+      t.bw[nd] = weight(tot[nd][0], tot[nd][1]);
+      t.leaf[nd] = eta * t.bw[nd];
     }
     if (last) break;
     std::vector<int> split_k;
@@ -585,33 +597,23 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       if (!(o[0] > rt_eps)) continue;
       const int nd = frontier[k];
       const int f = (int)o[1], b = (int)o[2];
-      feat[nd] = f, bin[nd] = b, defl[nd] = (int)o[3], gain[nd] = o[0];
+      t.feat[nd] = f, t.bin[nd] = b, t.defl[nd] = (int)o[3], t.gain[nd] = o[0];
       const int l = add(nd), r = add(nd);
-      left[nd] = l, right[nd] = r;
+      t.left[nd] = l, t.right[nd] = r;
       tot[l] = {o[4], o[5]};
       tot[r] = {tot[nd][0] - o[4], tot[nd][1] - o[5]};
       split_k.push_back(k);
     }
     if (split_k.empty()) break;
-    const int nnode = (int)feat.size();
+    const int nnode = (int)t.feat.size();
     const int nsplit = (int)split_k.size();
     // segment tiling of [0, n) for the position -> node map (gaps: -1)
-    std::vector<std::pair<int, int>> tiles;  // (begin, node)
-    {
-      std::vector<std::array<int, 3>> all;
-      for (auto& kv : seg) all.push_back({kv.second.first, kv.second.second, kv.first});
-      std::sort(all.begin(), all.end());
-      int cur = 0;
-      for (auto& a : all) {
-        if (a[0] > cur) tiles.push_back({cur, -1});
-        tiles.push_back({a[0], a[2]});
-        cur = a[1];
-      }
-      if (cur < n) tiles.push_back({cur, -1});
-    }
+    std::vector<std::array<int, 3>> live;
+    for (auto& kv : seg) live.push_back({kv.second.first, kv.second.second, kv.first});
+    const auto tiles = wh::gbdt_level_tiles(live, n);  // (begin, node)
     const int nt = (int)tiles.size();
     // one pinned upload of the level's tables
-    const NodeTables at(nnode, nt, nsplit);
+    const wh::GbdtNodeTables at(nnode, nt, nsplit);
     int32_t* hw = up.get<int32_t>(at.nwords);
     std::memset(hw, 0, at.nwords * 4);
     uint8_t* h_defl = reinterpret_cast<uint8_t*>(hw + at.defl);
@@ -619,19 +621,19 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     std::vector<int64_t> small_len(nsplit);
     for (int q = 0; q < nsplit; ++q) {
       const int k = split_k[q], nd = frontier[k];
-      hw[at.feat + nd] = feat[nd], hw[at.bin + nd] = bin[nd], h_defl[nd] = (uint8_t)defl[nd];
+      hw[at.feat + nd] = t.feat[nd], hw[at.bin + nd] = t.bin[nd], h_defl[nd] = (uint8_t)t.defl[nd];
       const auto sg = seg[nd];
       hw[at.sb + nd] = sg.first, hw[at.se + nd] = sg.second;
       hw[at.lc + nd] = sg.first, hw[at.rc + nd] = sg.second;
       // build the child with the smaller GLOBAL hessian, derive the other
-      const int l = left[nd], r = right[nd];
+      const int l = t.left[nd], r = t.right[nd];
       const int build_left = tot[l][1] <= tot[r][1] ? 1 : 0;
       int32_t* h_sp = hw + at.sp + 4 * q;
       h_sp[0] = nd, h_sp[1] = sg.first, h_sp[2] = sg.second, h_sp[3] = build_left;
       hw[at.par + q] = k;
       small_len[q] = sg.second - sg.first;  // upper bound of the built child's rows
     }
-    for (int i = 0; i < nt; ++i) hw[at.tb + i] = tiles[i].first, hw[at.tn + i] = tiles[i].second;
+    for (int i = 0; i < nt; ++i) hw[at.tb + i] = tiles[i][0], hw[at.tn + i] = tiles[i][1];
     auto dw32 = up.tensor().narrow(0, 0, at.nwords * 4).to(B.device(), true).view(torch::kInt32);
     up.mark(s);
     int32_t* d = ptr<int32_t>(dw32);
@@ -649,18 +651,12 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       // position -> node map, flags, scan, per-node left counts, stable scatter
       auto pos_node = torch::empty({n}, i32);
       wh::gbdt_seg_fill(d_tb, d_tn, nt, n, ptr<int32_t>(pos_node), s);
-      auto sb64 = dw32.narrow(0, at.sb, nnode).to(torch::kInt64);
-      auto se64 = dw32.narrow(0, at.se, nnode).to(torch::kInt64);
       auto leftf = torch::empty({n}, i32);
       wh::gbdt_goleft(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F, ptr<int32_t>(ridx), n,
                       ptr<int32_t>(pos_node), d_feat, d_bin, d_defl, ptr<int32_t>(leftf), s);
-      auto lscan = torch::empty({n + 1}, B.options().dtype(torch::kInt64));
-      auto stmp = torch::empty({wh::scan_tmp_elems(n)}, lscan.options());
-      wh::scan_i32(ptr<int32_t>(leftf), ptr<int64_t>(lscan), n, ptr<int64_t>(stmp), s);
-      nleft_dev = (lscan.index_select(0, se64) - lscan.index_select(0, sb64)).to(torch::kInt32);
-      wh::gbdt_scatter(ptr<int32_t>(ridx), n, ptr<int32_t>(pos_node), d_feat, d_sb,
-                       ptr<int32_t>(nleft_dev), ptr<int32_t>(leftf), ptr<int64_t>(lscan),
-                       ptr<int32_t>(ridx_new), s);
+      nleft_dev = Tensor();  // (the counts themselves: no copy)
+      partition_by_flags(ridx, pos_node, leftf, d_feat, dw32.narrow(0, at.sb, nnode),
+                         dw32.narrow(0, at.se, nnode), &nleft_dev, ridx_new, s);
     }
     ridx = ridx_new;
     // built children's rows, from the device counts
@@ -677,16 +673,16 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       const int k = split_k[q], nd = frontier[k];
       was_split[k] = true;
       const auto sg = seg[nd];
-      pending.push_back({nd, left[nd], right[nd], sg.first, sg.second});
+      pending.push_back({nd, t.left[nd], t.right[nd], sg.first, sg.second});
       seg.erase(nd);
-      nf.push_back(left[nd]), nf.push_back(right[nd]);
+      nf.push_back(t.left[nd]), nf.push_back(t.right[nd]);
     }
     for (int k = 0; k < S; ++k)
       if (!was_split[k]) {
         const int nd = frontier[k];
         auto it = seg.find(nd);
         if (it != seg.end()) {
-          done.push_back({nd, it->second.first, it->second.second});
+          segs.append(py::make_tuple(nd, it->second.first, it->second.second));
           seg.erase(it);
         }
       }
@@ -695,14 +691,8 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   }
   if (!pending.empty())  // (a loop that ended right after a partition)
     resolve_pending(nleft_dev.cpu().data_ptr<int32_t>());
-  for (auto& kv : seg) done.push_back({kv.first, kv.second.first, kv.second.second});
-  std::vector<float> cond(feat.size(), 0.f);
-  for (size_t i = 0; i < feat.size(); ++i)
-    if (feat[i] >= 0) cond[i] = cut_vals[cut_off[feat[i]] + bin[i]];
-  py::list segs;
-  for (auto& dn : done) segs.append(py::make_tuple(dn[0], dn[1], dn[2]));
-  return py::make_tuple(feat, bin, cond, defl, left, right, parent, gain, cover, bw, leaf, segs,
-                        ridx);
+  for (auto& kv : seg) segs.append(py::make_tuple(kv.first, kv.second.first, kv.second.second));
+  return py::make_tuple(t.pack(cut_vals, cut_off, segs), ridx);
 }
 
 // The same tree as gbdt_grow with the level loop on the device: heap-numbered
@@ -730,27 +720,24 @@ py::tuple gbdt_tree_from_nodes(const Tensor& hn, const std::vector<float>& cut_v
       id_of[h] = (int)order.size();
       order.push_back(h);
     }
-  const size_t M = order.size();
-  std::vector<int> feat(M), bin(M), defl(M), left(M, -1), right(M, -1), parent(M, -1);
-  std::vector<double> gain(M), cover(M), bw(M), leaf(M);
-  std::vector<float> cond(M, 0.f);
+  TreeLists t;
   py::list segs;
-  for (size_t i = 0; i < M; ++i) {
+  for (size_t i = 0; i < order.size(); ++i) t.add(-1);
+  for (size_t i = 0; i < order.size(); ++i) {
     const int h = order[i];
     const double* q = r + (int64_t)h * REC;
-    feat[i] = (int)q[1], bin[i] = (int)q[2], defl[i] = (int)q[3];
-    gain[i] = q[4], cover[i] = q[5], bw[i] = q[6], leaf[i] = q[7];
-    if (feat[i] >= 0) {
+    t.feat[i] = (int)q[1], t.bin[i] = (int)q[2], t.defl[i] = (int)q[3];
+    t.gain[i] = q[4], t.cover[i] = q[5], t.bw[i] = q[6], t.leaf[i] = q[7];
+    if (t.feat[i] >= 0) {
       TORCH_CHECK(2 * h + 2 < NN, "gbdt_tree_from_nodes: a split at the last depth");
-      left[i] = id_of[2 * h + 1], right[i] = id_of[2 * h + 2];
-      TORCH_CHECK(left[i] >= 0 && right[i] >= 0, "gbdt_tree_from_nodes: a split node lost a child");
-      parent[left[i]] = (int)i, parent[right[i]] = (int)i;
-      cond[i] = cut_vals[cut_off[feat[i]] + bin[i]];
+      const int l = t.left[i] = id_of[2 * h + 1], rt = t.right[i] = id_of[2 * h + 2];
+      TORCH_CHECK(l >= 0 && rt >= 0, "gbdt_tree_from_nodes: a split node lost a child");
+      t.parent[l] = (int)i, t.parent[rt] = (int)i;
     } else {
       segs.append(py::make_tuple((int)i, (int)q[8], (int)q[9]));
     }
   }
-  return py::make_tuple(feat, bin, cond, defl, left, right, parent, gain, cover, bw, leaf, segs);
+  return t.pack(cut_vals, cut_off, segs);
 }
 
 // margin += the leaf value each row reaches in a device grower's heap node
@@ -872,10 +859,8 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     if (!last) {
       so = torch::empty({S, 6}, f64);
       if (Fl > 0) {
-        auto cand = torch::empty({(int64_t)S * Fl * 4}, f64);
-        TORCH_CHECK(wh::gbdt_split(ptr<double>(H_front), ptr<double>(tot_cur),
-                                   vp + (int64_t)f_lo * nbin, S, Fl, (int)nbin, alpha, lambda, mcw,
-                                   ptr<double>(cand), ptr<double>(so), s),
+        TORCH_CHECK(split_search(H_front, ptr<double>(tot_cur), vp + (int64_t)f_lo * nbin, S, alpha,
+                                 lambda, mcw, so, s),
                     "gbdt_split failed");
       } else {  // (more ranks than features: this rank owns none)
         so.zero_();
@@ -962,9 +947,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
   // (gbdt_tree_from_nodes), so the host's tree bookkeeping overlaps the next
   // tree instead of idling the GPU between trees
   if (defer) return py::make_tuple(nodes, ridx);
-  py::tuple t = gbdt_tree_from_nodes(nodes.cpu(), cut_vals, cut_off);
-  return py::make_tuple(t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11],
-                        ridx);
+  return py::make_tuple(gbdt_tree_from_nodes(nodes.cpu(), cut_vals, cut_off), ridx);
 }
 
 }  // namespace

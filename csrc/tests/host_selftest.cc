@@ -8,7 +8,8 @@
 // the conf parser, the WorkloadPool under concurrent workers and the
 // control-plane transport (Van) with live reader threads; and the pure
 // arithmetic of the exact AUC, of the two store guards' plans, of the
-// localize job's bookkeeping and of the GBDT histogram task lists.
+// localize job's bookkeeping and of the GBDT histogram task lists and level
+// tables.
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -20,6 +21,7 @@
 #include "host/auc_host.h"
 #include "host/common.h"
 #include "host/gbdt_hist_plan.h"
+#include "host/gbdt_level_plan.h"
 #include "host/io.h"
 #include "host/json.h"
 #include "host/linear_guard_plan.h"
@@ -455,6 +457,38 @@ static void test_gbdt_hist_plan() {
   }
 }
 
+// the host grower's level tables: the segment tiling of [0, n) (expected
+// values: the runs of models/gbdt.py _pos_node for the same segments) and the
+// upload's word offsets
+static void test_gbdt_level_plan() {
+  using Tiles = std::vector<std::array<int, 2>>;  // {begin, node}
+  using Segs = std::vector<std::array<int, 3>>;    // {begin, end, node}
+  // no live segment: one gap over everything
+  EXPECT((wh::gbdt_level_tiles(Segs{}, 10) == Tiles{{0, -1}}));
+  // one segment covering [0, n)
+  EXPECT((wh::gbdt_level_tiles(Segs{{0, 10, 0}}, 10) == Tiles{{0, 0}}));
+  // gaps at the front, in the middle and at the end
+  EXPECT((wh::gbdt_level_tiles(Segs{{2, 5, 3}, {7, 9, 4}}, 12) ==
+          Tiles{{0, -1}, {2, 3}, {5, -1}, {7, 4}, {9, -1}}));
+  EXPECT((wh::gbdt_level_tiles(Segs{{3, 10, 7}}, 10) == Tiles{{0, -1}, {3, 7}}));
+  EXPECT((wh::gbdt_level_tiles(Segs{{0, 3, 7}}, 10) == Tiles{{0, 7}, {3, -1}}));
+  // adjacent segments: no gap tile between them, in position order whatever
+  // order they come in
+  EXPECT((wh::gbdt_level_tiles(Segs{{0, 4, 1}, {4, 10, 2}}, 10) == Tiles{{0, 1}, {4, 2}}));
+  EXPECT((wh::gbdt_level_tiles(Segs{{6, 10, 5}, {0, 6, 2}}, 10) == Tiles{{0, 2}, {6, 5}}));
+  // word offsets: five nodes' defl bytes take two words
+  {
+    const wh::GbdtNodeTables at(/*nnode=*/5, /*nt=*/3, /*nsplit=*/2);
+    EXPECT(at.feat == 0 && at.bin == 5 && at.sb == 10 && at.se == 15 && at.defl == 20);
+    EXPECT(at.tb == 22 && at.tn == 25 && at.sp == 28 && at.par == 36);
+    EXPECT(at.lc == 38 && at.rc == 43 && at.nwords == 48);
+  }
+  // a multiple of four leaves no padding; one node still takes a whole word
+  EXPECT(wh::GbdtNodeTables(8, 1, 1).tb == 32 + 2);
+  EXPECT(wh::GbdtNodeTables(1, 1, 0).tb == 4 + 1);
+  EXPECT(wh::GbdtNodeTables(1, 1, 0).nwords == 5 + 1 + 1 + 0 + 0 + 1 + 1);
+}
+
 // the localize job's bookkeeping (host/localize_plan.h) through the job
 // sequences the GPU tests rely on. A Job mirrors what LocalizeJob holds.
 static void test_localize_plan() {
@@ -674,6 +708,7 @@ int main() {
   test_localize_plan();
   test_psx_plan();
   test_gbdt_hist_plan();
+  test_gbdt_level_plan();
   test_lz4();
   test_crb();
   test_parsers();

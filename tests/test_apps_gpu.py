@@ -226,6 +226,55 @@ def test_gbdt_native_grower_matches_python_loop(gamma, colsample, hist, monkeypa
     assert torch.allclose(res[0][1], res[1][1], atol=1e-6)
 
 
+def test_gbdt_host_grower_partition_fallback_matches_python_loop(monkeypatch):
+    """A tree deeper than 11 levels: the host grower's one-pass partition
+    refuses a level of more than 2048 segment tiles and the level is
+    partitioned by flags, scan and stable scatter instead. The tree and the
+    margins must still be the Python level loop's."""
+    from collections import Counter
+    from wormhole_amd import _native
+    from wormhole_amd.models import gbdt as G
+    from wormhole_amd.parallel.bsp import BSP
+    g = torch.Generator().manual_seed(7)
+    n, f = 32768, 3
+    X = torch.randn(n, f, generator=g)
+    X[torch.rand(n, f, generator=g) < 0.05] = float("nan")
+    x = torch.nan_to_num(X)
+    y = 4 * x[:, 0] + 3 * x[:, 1] + x[:, 2]
+    bsp = BSP(torch.device("cpu"))
+    p = G.GBDTParam()
+    p.objective, p.reg_lambda, p.max_depth = "reg:linear", 0.0, 13
+    dev = torch.device("cuda", 0)
+    dm = G.DMatrix.from_dense(X, y, dev)
+    cuts = G.Cuts.build(dm, 255, bsp)
+    B = cuts.bin(dm)
+    obj = G.Objective(p.objective)
+    hip = _native.hip()
+    calls = []
+    for name in ("gbdt_grow", "gbdt_grow_dev"):
+        def counted(*a, _name=name, _fn=getattr(hip, name), **kw):
+            calls.append(_name)
+            return _fn(*a, **kw)
+        monkeypatch.setattr(hip, name, counted)
+    res = []
+    for native in (True, False):
+        margin = torch.zeros(n, device=dev)
+        tb = G.TreeBuilder(p, bsp, dm, cuts, B)
+        gp = obj.gpair(margin, dm.label, None)
+        res.append((tb._build_native(gp, margin) if native else tb._build_py(gp, margin),
+                    margin.cpu()))
+    assert calls == ["gbdt_grow"]  # deeper than the device loop's heap numbering
+    (a, ma), (b, mb) = res
+    # the fallback was reached: the level that split the depth-12 nodes held a
+    # tile for each of them, more than the one-pass partition takes
+    depths = Counter(a.depth(i) for i in range(len(a.feat)))
+    assert depths[12] > 2048 and depths[13] >= 1, sorted(depths.items())
+    assert a.feat == b.feat and a.cond == b.cond and a.defl == b.defl
+    assert a.left == b.left and a.right == b.right
+    assert all(abs(u - v) < 1e-6 for u, v in zip(a.leaf, b.leaf))
+    assert torch.allclose(ma, mb, atol=1e-6)
+
+
 @pytest.mark.parametrize("gamma,colsample,depth", [(0.0, 1.0, 6), (2.0, 0.6, 8)])
 def test_gbdt_device_level_loop_matches_host_grower(gamma, colsample, depth, monkeypatch):
     """The level loop on the device (heap-numbered nodes, device split
@@ -303,7 +352,7 @@ def test_gbdt_csr_gpu_matches_dense_and_trains_wide_data():
     y = ((k[:, 0] % 2) == 0).float()
     offs = torch.arange(n + 1, dtype=torch.int64) * per
     dm = G.make_dmatrix(k.reshape(-1), offs, None, y, None, F, dev)
-    assert getattr(dm, "sparse", False)
+    assert dm.sparse
     margin = torch.zeros(n, device=dev)
     cuts = G.Cuts.build(dm, 64, bsp)
     tb = G.make_builder(p, bsp, dm, cuts, cuts.bin(dm))

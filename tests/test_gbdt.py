@@ -164,7 +164,7 @@ def test_csr_matrix_grows_the_dense_trees():
     res = []
     for sparse in (False, True):
         dm = G.make_dmatrix(keys, off, val, lab, None, ncol, torch.device("cpu"), sparse=sparse)
-        assert getattr(dm, "sparse", False) == sparse
+        assert dm.sparse == sparse
         res.append(_train(G, bsp, dm, p, 2))
     for a, b in zip(res[0][0], res[1][0]):
         assert a.feat == b.feat and a.cond == b.cond and a.defl == b.defl

@@ -732,7 +732,7 @@ def test_async_saver_snapshot(hip, tmp_path):
 @pytest.mark.parametrize("S,F,nbin,alpha,mcw", [(5, 7, 33, 0.0, 1.0), (3, 28, 256, 0.5, 0.1),
                                                 (2, 4, 1000, 0.0, 5.0)])
 def test_gbdt_split_kernel(hip, S, F, nbin, alpha, mcw):
-    """Fused split search vs the torch reference (_find_splits_ref): same
+    """Fused split search vs the torch reference (find_splits_ref): same
     feature / bin / direction, gains and left sums to fp64 rounding; a node
     with no valid candidate reports -inf."""
     from wormhole_amd.models import gbdt as G
@@ -745,16 +745,13 @@ def test_gbdt_split_kernel(hip, S, F, nbin, alpha, mcw):
     totals[:, 0] = present[:, :, 0].mean(1)  # rows missing a feature move the totals
     valid = torch.rand(F, nbin, generator=g) < 0.8
     valid[0] = False
-    tb = G.TreeBuilder.__new__(G.TreeBuilder)
-    tb.p = G.GBDTParam()
-    tb.p.alpha, tb.p.min_child_weight = alpha, mcw
-    tb.nbin, tb.valid_mask, tb._valid_dev = nbin, valid, None
-    ref = tb._find_splits_ref(hist, totals)
+    p = G.GBDTParam()
+    p.alpha, p.min_child_weight = alpha, mcw
     if S > 2:
         hist[2].zero_()  # no candidate passes min_child_weight on either side
         totals[2] = 0.0
-        ref = tb._find_splits_ref(hist, totals)
-    got = tb._find_splits(hist.to(DEV), totals.to(DEV))
+    ref = G.split_fields(G.find_splits_ref(p, hist, totals, valid))
+    got = G.split_fields(G.find_splits(p, hist.to(DEV), totals.to(DEV), valid))
     ok = torch.isfinite(ref[0])
     assert torch.equal(torch.isfinite(got[0]), ok)
     assert torch.allclose(got[0][ok], ref[0][ok], rtol=1e-9, atol=1e-9)

@@ -1,0 +1,265 @@
+"""GBDT trees and the model (models/gbdt.py grows the trees): a tree's node
+lists, the device-grown tree that builds them on first use, dump, model file."""
+import math
+import struct
+
+import numpy as np
+import torch
+
+from .. import _native
+from ..utils.fs import open_uri  # noqa: E402
+from .gbdt_objective import Objective
+
+
+# ------------------------------------------------------------------- tree
+class RegTree:
+    def __init__(self):
+        self.feat, self.bin, self.cond, self.defl = [], [], [], []
+        self.left, self.right, self.parent = [], [], []
+        self.leaf, self.gain, self.cover, self.base_weight = [], [], [], []
+
+    @staticmethod
+    def from_lists(t):
+        """The tree of a native grower's lists (``_hip.gbdt_tree_from_nodes``):
+        feat, bin, cond, defl, left, right, parent, gain, cover, base weight, leaf."""
+        tree = RegTree()
+        (tree.feat, tree.bin, tree.cond, tree.defl, tree.left, tree.right, tree.parent,
+         tree.gain, tree.cover, tree.base_weight, tree.leaf) = (list(v) for v in t[:11])
+        return tree
+
+    def compact(self):
+        """Renumber reachable nodes in BFS order (like xgboost's node ids)."""
+        order = [0]
+        k = 0
+        while k < len(order):
+            i = order[k]
+            if not self.is_leaf(i):
+                order += [self.left[i], self.right[i]]
+            k += 1
+        remap = {old: new for new, old in enumerate(order)}
+        t = RegTree()
+        for old in order:
+            t.add(remap.get(self.parent[old], -1) if self.parent[old] >= 0 else -1)
+        for old in order:
+            i = remap[old]
+            t.feat[i] = self.feat[old]
+            t.bin[i], t.cond[i], t.defl[i] = self.bin[old], self.cond[old], self.defl[old]
+            t.leaf[i], t.gain[i], t.cover[i] = self.leaf[old], self.gain[old], self.cover[old]
+            t.base_weight[i] = self.base_weight[old]
+            if not self.is_leaf(old):
+                t.left[i], t.right[i] = remap[self.left[old]], remap[self.right[old]]
+        self.__dict__.update(t.__dict__)
+        return self
+
+    def add(self, parent):
+        i = len(self.feat)
+        self.feat.append(-1), self.bin.append(0), self.cond.append(0.0), self.defl.append(0)
+        self.left.append(-1), self.right.append(-1), self.parent.append(parent)
+        self.leaf.append(0.0), self.gain.append(0.0), self.cover.append(0.0)
+        self.base_weight.append(0.0)
+        return i
+
+    def is_leaf(self, i):
+        return self.feat[i] < 0
+
+    def depth(self, i):
+        d = 0
+        while self.parent[i] >= 0:
+            i = self.parent[i]
+            d += 1
+        return d
+
+    def device_arrays(self, device):
+        f = torch.tensor(self.feat, dtype=torch.int32, device=device)
+        return (f, torch.tensor(self.cond, dtype=torch.float32, device=device),
+                torch.tensor(self.left, dtype=torch.int32, device=device),
+                torch.tensor(self.right, dtype=torch.int32, device=device),
+                torch.tensor(self.defl, dtype=torch.uint8, device=device),
+                torch.tensor(self.leaf, dtype=torch.float32, device=device))
+
+    def predict_margin(self, X, margin):
+        if X.is_cuda:
+            _native.hip().gbdt_predict(X, *self.device_arrays(X.device), margin)
+            return margin
+        node = torch.zeros(X.shape[0], dtype=torch.long)
+        feat = torch.tensor(self.feat)
+        cond = torch.tensor(self.cond)
+        left, right = torch.tensor(self.left), torch.tensor(self.right)
+        defl = torch.tensor(self.defl, dtype=torch.bool)
+        leaf = torch.tensor(self.leaf)
+        for _ in range(64):
+            f = feat[node]
+            active = f >= 0
+            if not bool(active.any()):
+                break
+            v = X[torch.arange(X.shape[0]), f.clamp(min=0)]
+            go_left = torch.where(torch.isnan(v), defl[node], v < cond[node])
+            nxt = torch.where(go_left, left[node], right[node])
+            node = torch.where(active, nxt, node)
+        margin += leaf[node]
+        return margin
+
+    # -------------------------------------------------------------- dump
+    def dump(self, fmap=None, with_stats=False):
+        out = []
+
+        def rec(i, depth):
+            pad = "\t" * depth
+            if self.is_leaf(i):
+                s = "%s%d:leaf=%s" % (pad, i, _fmt(self.leaf[i]))
+                if with_stats:
+                    s += ",cover=%s" % _fmt(self.cover[i])
+                out.append(s)
+                return
+            f = self.feat[i]
+            name, typ = (fmap[f] if fmap and f < len(fmap) else ("f%d" % f, "q"))
+            if typ == "i":
+                # indicator: "yes" is the branch a present feature (value 1) takes
+                yes, no = (self.left[i], self.right[i]) if 1.0 < self.cond[i] else (
+                    self.right[i], self.left[i])
+                s = "%s%d:[%s] yes=%d,no=%d" % (pad, i, name, yes, no)
+            elif typ == "int":
+                s = "%s%d:[%s<%d] yes=%d,no=%d" % (pad, i, name, int(math.ceil(self.cond[i])),
+                                                   self.left[i], self.right[i])
+            else:
+                s = "%s%d:[%s<%s] yes=%d,no=%d" % (pad, i, name, _fmt(self.cond[i]),
+                                                   self.left[i], self.right[i])
+            if typ != "i":
+                s += ",missing=%d" % (self.left[i] if self.defl[i] else self.right[i])
+            if with_stats:
+                s += ",gain=%s,cover=%s" % (_fmt(self.gain[i]), _fmt(self.cover[i]))
+            out.append(s)
+            rec(self.left[i], depth + 1)
+            rec(self.right[i], depth + 1)
+        rec(0, 0)
+        return "\n".join(out) + "\n"
+
+
+class _DeviceTree(RegTree):
+    """A tree grown by the device level loop whose host lists are built on
+    first use (models/gbdt.py TreeBuilder._build_native, defer): the node
+    table is copied to pinned host memory right away, behind the tree's
+    kernels, and renumbered breadth-first (``gbdt_tree_from_nodes``) when an
+    attribute is first read -- by the builder one tree later, or by whoever
+    reads the model first. Until then it holds no lists."""
+
+    def __init__(self, nodes, cut_lists):  # noqa: D401 (no RegTree lists yet)
+        host = torch.empty(nodes.shape, dtype=nodes.dtype, pin_memory=True)
+        host.copy_(nodes, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.__dict__["_pend"] = (host, ev, cut_lists, nodes)
+
+    def materialize(self):
+        pend = self.__dict__.pop("_pend", None)
+        if pend is None:
+            return self
+        host, ev, (cut_vals, cut_off), _ = pend
+        ev.synchronize()
+        lists = _native.hip().gbdt_tree_from_nodes(host, cut_vals, cut_off)
+        self.__dict__.update(RegTree.from_lists(lists).compact().__dict__)
+        return self
+
+    def __getattr__(self, name):  # only for attributes not set yet
+        if name.startswith("__") or "_pend" not in self.__dict__:
+            raise AttributeError(name)
+        self.materialize()
+        return object.__getattribute__(self, name)
+
+    def __getstate__(self):
+        self.materialize()
+        return self.__dict__
+
+
+def _fmt(x):
+    return "%g" % x
+
+
+def load_fmap(path):
+    names = []
+    for line in open_uri(path):
+        parts = line.rstrip("\n").split("\t")
+        if len(parts) < 3:
+            continue
+        fid = int(parts[0])
+        while len(names) <= fid:
+            names.append(("f%d" % len(names), "q"))
+        names[fid] = (parts[1], parts[2])
+    return names
+
+
+# ---------------------------------------------------------------- booster
+class Booster:
+    MAGIC = b"WHGB"
+
+    def __init__(self, param, num_feature):
+        self.param = param
+        self.num_feature = int(num_feature)
+        self.trees = []
+        self.obj = Objective(param.objective, param.num_class)
+        self.base_margin = self.obj.prob_to_margin(param.base_score)
+
+    def predict_margin(self, dm, ntree_limit=0):
+        """[n] margins, or [K, n] for K classes (tree t adds to row t % K)."""
+        K = self.obj.n_group
+        margin = torch.full((dm.n,) if K == 1 else (K, dm.n), self.base_margin,
+                            dtype=torch.float32, device=dm.device)
+        trees = self.trees[:ntree_limit] if ntree_limit else self.trees
+        for i, t in enumerate(trees):
+            dm.predict_tree(t, margin if K == 1 else margin[i % K])
+        return margin
+
+    def save(self, path):
+        p = self.param
+        with open_uri(path, "wb") as f:
+            f.write(self.MAGIC)
+            hdr = "%s|%g|%d|%d" % (p.objective, p.base_score, self.num_feature, len(self.trees))
+            if self.obj.n_group > 1:  # (single-output files keep their four fields)
+                hdr += "|%d" % self.obj.n_group
+            hdr = hdr.encode()
+            f.write(struct.pack("<I", len(hdr)) + hdr)
+            for t in self.trees:
+                n = len(t.feat)
+                f.write(struct.pack("<I", n))
+                arr = np.zeros(n, dtype=[("feat", "<i4"), ("cond", "<f4"), ("left", "<i4"),
+                                         ("right", "<i4"), ("defl", "<i4"), ("leaf", "<f4"),
+                                         ("gain", "<f4"), ("cover", "<f4")])
+                for k in ("feat", "cond", "left", "right", "defl", "leaf", "gain", "cover"):
+                    arr[k] = getattr(t, k)
+                f.write(arr.tobytes())
+
+    @staticmethod
+    def load(path, param):
+        with open_uri(path, "rb") as f:
+            if f.read(4) != Booster.MAGIC:
+                raise ValueError("invalid model file " + path)
+            (ln,) = struct.unpack("<I", f.read(4))
+            fields = f.read(ln).decode().split("|")
+            if len(fields) not in (4, 5):
+                raise ValueError("invalid model header in " + path)
+            objective, base, nf, ntree = fields[:4]
+            param.objective = objective
+            param.base_score = float(base)
+            param.num_class = int(fields[4]) if len(fields) == 5 else 0
+            b = Booster(param, int(nf))
+            for _ in range(int(ntree)):
+                (n,) = struct.unpack("<I", f.read(4))
+                arr = np.frombuffer(f.read(32 * n), dtype=[
+                    ("feat", "<i4"), ("cond", "<f4"), ("left", "<i4"), ("right", "<i4"),
+                    ("defl", "<i4"), ("leaf", "<f4"), ("gain", "<f4"), ("cover", "<f4")])
+                t = RegTree()
+                for k in ("feat", "cond", "left", "right", "defl", "leaf", "gain", "cover"):
+                    setattr(t, k, [x.item() for x in arr[k]])
+                t.parent = [-1] * n
+                for i in range(n):
+                    if t.feat[i] >= 0:
+                        t.parent[t.left[i]] = i
+                        t.parent[t.right[i]] = i
+                t.bin = [0] * n
+                t.base_weight = [0.0] * n
+                b.trees.append(t)
+        return b
+
+    def dump(self, fmap=None, with_stats=False):
+        return "".join("booster[%d]:\n%s" % (i, t.dump(fmap, with_stats))
+                       for i, t in enumerate(self.trees))
