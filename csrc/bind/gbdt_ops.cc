@@ -1,6 +1,7 @@
 // Bindings of the GBDT family (module wormhole_amd._hip): binning, histograms,
-// split search, partition, objectives, prediction (dense and CSR) and the two
-// tree growers. Stateless: tensors are validated, outputs sized and kernels
+// split search, partition, objectives, prediction (dense and CSR; per tree,
+// and the packed forest in one pass per chunk) and the two tree growers.
+// Stateless: tensors are validated, outputs sized and kernels
 // launched on the current PyTorch HIP stream.
 #include "bind_common.h"
 
@@ -8,8 +9,10 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <tuple>
 #include <utility>
 
+#include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
 
@@ -418,6 +421,118 @@ void gbdt_predict_csr(const Tensor& row_off, const Tensor& fid, const c10::optio
                        row_off.numel() - 1, ptr<int32_t>(feat), ptr<float>(thr),
                        ptr<int32_t>(left), ptr<int32_t>(right), ptr<uint8_t>(defl),
                        ptr<float>(leaf), ptr<float>(margin), cur_stream(fid));
+}
+
+// ------------------------------------------------------ forest prediction
+// The packed forest of the trees' lists (host/gbdt_forest_plan.h): (nodes
+// int32 [N, 4], tree_off int32 [T + 1], largest feature id or -1), on the
+// host. A tree a walk could leave or spin in raises ValueError.
+py::tuple gbdt_forest_pack(std::vector<std::vector<int64_t>> feat,
+                           std::vector<std::vector<double>> cond,
+                           std::vector<std::vector<int64_t>> left,
+                           std::vector<std::vector<int64_t>> right,
+                           std::vector<std::vector<int64_t>> defl,
+                           std::vector<std::vector<double>> leaf) {
+  wh::GbdtForestTrees tr{std::move(feat), std::move(left), std::move(right), std::move(defl),
+                         std::move(cond), std::move(leaf)};
+  std::vector<wh::GbdtForestNode> nodes;
+  std::vector<int32_t> off;
+  wh::gbdt_forest_pack(tr, &nodes, &off);  // (std::invalid_argument -> ValueError)
+  int64_t max_feat = -1;
+  for (auto& nd : nodes)
+    if (nd.fd >= 0) max_feat = std::max<int64_t>(max_feat, nd.fd >> 1);
+  auto tn = torch::empty({(int64_t)nodes.size(), 4}, torch::kInt32);
+  if (!nodes.empty()) std::memcpy(tn.data_ptr(), nodes.data(), nodes.size() * sizeof(nodes[0]));
+  auto to = torch::empty({(int64_t)off.size()}, torch::kInt32);
+  std::memcpy(to.data_ptr(), off.data(), off.size() * 4);
+  return py::make_tuple(tn, to, max_feat);
+}
+
+// (first_tree, ntree, node_begin, nnode, in_lds) per chunk
+using ForestChunks = std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, bool>>;
+
+ForestChunks gbdt_forest_plan(const std::vector<int64_t>& tree_sizes, int64_t lds_nodes) {
+  TORCH_CHECK(lds_nodes >= 1, "gbdt_forest_plan: lds_nodes must be positive");
+  for (int64_t sz : tree_sizes) TORCH_CHECK(sz >= 1, "gbdt_forest_plan: an empty tree");
+  ForestChunks out;
+  for (auto& c : wh::gbdt_forest_plan(tree_sizes, lds_nodes))
+    out.emplace_back(c.first_tree, c.ntree, c.node_begin, c.nnode, c.in_lds);
+  return out;
+}
+
+// The checks both forest predictions share, then one launch per chunk.
+// out: float32 margins [n] or [K, n] (rows may be views into a larger
+// buffer), or, leaf, int32 leaf ids [n, T].
+template <class Launch>
+void forest_run(const Tensor& nodes, const Tensor& tree_off, const ForestChunks& chunks,
+                const Tensor& out, bool leaf, int64_t n, Launch launch) {
+  CHECK_IN(nodes, torch::kInt32);
+  CHECK_IN(tree_off, torch::kInt32);
+  CHECK_DEV(out);
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 4, "forest nodes must be int32 [N, 4]");
+  const int64_t T = tree_off.numel() - 1;
+  TORCH_CHECK(T >= 0 && T <= INT32_MAX, "forest tree_off must be [T + 1]");
+  wh::ForestOut o{nullptr, 0, 1, nullptr, (int)T};
+  if (leaf) {
+    CHECK_CONT(out);
+    CHECK_DT(out, torch::kInt32);
+    TORCH_CHECK(out.dim() == 2 && out.size(0) == n && out.size(1) == T, "leaf ids must be [n, T]");
+    o.leaf = ptr<int32_t>(out);
+  } else {
+    CHECK_DT(out, torch::kFloat32);
+    TORCH_CHECK((out.dim() == 1 || out.dim() == 2) && out.size(-1) == n &&
+                    (n <= 1 || out.stride(-1) == 1) && (out.dim() == 1 || out.size(0) >= 1),
+                "margins must be [n] or [K, n] with unit stride along n");
+    o.margin = ptr<float>(out);
+    if (out.dim() == 2) o.K = (int)out.size(0), o.stride = out.stride(0);
+  }
+  if (n == 0 || T == 0) return;
+  int64_t tree = 0, node = 0;
+  for (auto& [first_tree, ntree, node_begin, nnode, in_lds] : chunks) {
+    TORCH_CHECK(first_tree == tree && node_begin == node && ntree >= 1 && nnode >= ntree &&
+                    (!in_lds || nnode <= wh::gbdt_forest_lds_nodes()),
+                "forest chunks must be consecutive whole trees that fit the LDS");
+    tree += ntree, node += nnode;
+  }
+  TORCH_CHECK(tree == T && node == nodes.size(0), "forest chunks must cover the forest");
+  for (auto& [first_tree, ntree, node_begin, nnode, in_lds] : chunks)
+    launch(wh::ForestChunk{nodes.data_ptr(), ptr<int32_t>(tree_off), (int)first_tree, (int)ntree,
+                           (int)node_begin, (int)nnode, in_lds},
+           o);
+}
+
+void gbdt_predict_forest(const Tensor& X, const Tensor& nodes, const Tensor& tree_off,
+                         const ForestChunks& chunks, int64_t max_feat, const Tensor& out,
+                         bool leaf) {
+  CHECK_IN(X, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && max_feat < X.size(1), "forest splits on a feature X does not have");
+  c10::DeviceGuard g(X.device());
+  auto s = cur_stream(X);
+  forest_run(nodes, tree_off, chunks, out, leaf, X.size(0),
+             [&](const wh::ForestChunk& c, const wh::ForestOut& o) {
+               wh::gbdt_predict_forest(ptr<float>(X), X.size(0), (int)X.size(1), c, o, s);
+             });
+}
+
+void gbdt_predict_forest_csr(const Tensor& row_off, const Tensor& fid,
+                             const c10::optional<Tensor>& val, const Tensor& nodes,
+                             const Tensor& tree_off, const ForestChunks& chunks, const Tensor& out,
+                             bool leaf) {
+  CHECK_IN(row_off, torch::kInt64);
+  CHECK_IN(fid, torch::kInt32);
+  TORCH_CHECK(row_off.numel() >= 1, "row_off must be [n + 1]");
+  if (present(val)) {
+    CHECK_IN((*val), torch::kFloat32);
+    TORCH_CHECK(val->numel() == fid.numel(), "val and fid sizes differ");
+  }
+  c10::DeviceGuard g(row_off.device());
+  auto s = cur_stream(row_off);
+  const int64_t n = row_off.numel() - 1;
+  forest_run(nodes, tree_off, chunks, out, leaf, n,
+             [&](const wh::ForestChunk& c, const wh::ForestOut& o) {
+               wh::gbdt_predict_forest_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid),
+                                           optptr<float>(val), n, c, o, s);
+             });
 }
 
 // ------------------------------------------------------------ gbdt grower
@@ -993,6 +1108,17 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_split_csr", &gbdt_split_csr);
   m.def("gbdt_partition_csr", &gbdt_partition_csr);
   m.def("gbdt_predict_csr", &gbdt_predict_csr);
+  // forest prediction: pack, plan and the capacity need no GPU
+  m.def("gbdt_forest_pack", &gbdt_forest_pack, py::arg("feat"), py::arg("cond"), py::arg("left"),
+        py::arg("right"), py::arg("defl"), py::arg("leaf"));
+  m.def("gbdt_forest_plan", &gbdt_forest_plan, py::arg("tree_sizes"), py::arg("lds_nodes"));
+  m.def("gbdt_forest_lds_nodes", &wh::gbdt_forest_lds_nodes);
+  m.def("gbdt_predict_forest", &gbdt_predict_forest, py::arg("X"), py::arg("nodes"),
+        py::arg("tree_off"), py::arg("chunks"), py::arg("max_feat"), py::arg("out"),
+        py::arg("leaf") = false);
+  m.def("gbdt_predict_forest_csr", &gbdt_predict_forest_csr, py::arg("row_off"), py::arg("fid"),
+        py::arg("val"), py::arg("nodes"), py::arg("tree_off"), py::arg("chunks"), py::arg("out"),
+        py::arg("leaf") = false);
 }
 
 }  // namespace wh_bind

@@ -645,6 +645,34 @@ void gbdt_predict(const float* X, int64_t n, int f, const int32_t* feat, const f
                   const int32_t* left, const int32_t* right, const uint8_t* defl,
                   const float* leaf, float* margin, hipStream_t s);
 
+// -------------------------------------------------------- gbdt_forest.hip
+// One chunk of a packed forest (host/gbdt_forest_plan.h: 16-byte nodes, whole
+// table `nodes`, tree_off [T + 1], both on the device) walked by every row in
+// one launch: the chunk's nodes from LDS (in_lds, nnode <=
+// gbdt_forest_lds_nodes()) or from global memory. Margins: tree t adds its
+// leaf to margin[(t % K) * stride + row], starting from what is there, in
+// tree order; or, leaf != null, leaf[row * T + t] = the leaf's node id within
+// tree t. Dense rows are raw fp32 X [n, f] with NaN = missing (every feature
+// id of the forest must be < f); CSR rows as gbdt_predict_csr. Nothing runs
+// for n <= 0 or an empty chunk.
+struct ForestChunk {
+  const void* nodes;
+  const int32_t* tree_off;
+  int first_tree, ntree, node_begin, nnode;
+  bool in_lds;
+};
+struct ForestOut {
+  float* margin;
+  int64_t stride;
+  int K;
+  int32_t* leaf;
+  int T;
+};
+void gbdt_predict_forest(const float* X, int64_t n, int f, const ForestChunk& c,
+                         const ForestOut& o, hipStream_t s);
+void gbdt_predict_forest_csr(const int64_t* row_off, const int32_t* fid, const float* val,
+                             int64_t n, const ForestChunk& c, const ForestOut& o, hipStream_t s);
+
 // ------------------------------------------------------------- ingest.hip
 // Criteo / libsvm text -> CSR minibatch on the device (keys bit-identical to
 // the host parsers'). text_lines: start [nlines + 1] of the lines of

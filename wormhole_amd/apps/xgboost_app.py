@@ -13,7 +13,12 @@ subsample, colsample_bytree, seed, eval_metric, num_round, save_period,
 eval_train, eval[name]=path, data, test:data, model_in, model_out, model_dir,
 fmap, name_dump, name_pred, dump_stats, dsplit=row, dsparse (keep the rows CSR:
 wide libsvm data; default when num_feature > 4096), nthread (ignored),
-num_feature.  Output: ``[r]\\t<set>-<metric>:<value>`` lines per round.
+num_feature; for task=pred and task=eval ntree_limit (use the first N
+boosting rounds, N x num_class trees; 0 or more than the model has: all), for
+task=pred pred_margin (write the untransformed margins: n lines, or n x K
+row-major for a multi: objective) and pred_leaf (write n x T row-major leaf
+node ids, numbered as in task=dump; not together with pred_margin).
+Output: ``[r]\\t<set>-<metric>:<value>`` lines per round.
 """
 import os
 import sys
@@ -65,6 +70,7 @@ def main(argv):
     fmap, name_dump, name_pred, dump_stats = None, "dump.txt", "pred.txt", 0
     num_feature = 0
     dsparse = None  # dsparse=1|0: keep the data CSR / dense (default: by width)
+    ntree_limit, pred_margin, pred_leaf = 0, False, False
     evals = []
     for k, v in parse_args(argv):
         if param.set(k, v):
@@ -103,6 +109,12 @@ def main(argv):
             num_feature = int(v)
         elif k == "dsparse":
             dsparse = bool(int(v))
+        elif k == "ntree_limit":
+            ntree_limit = int(v)
+        elif k == "pred_margin":
+            pred_margin = bool(int(v))
+        elif k == "pred_leaf":
+            pred_leaf = bool(int(v))
         elif k in ("dsplit",):
             if v not in ("row", "auto"):
                 raise SystemExit("only dsplit=row is supported")
@@ -112,6 +124,10 @@ def main(argv):
             bsp.tracker_print("Warning: unknown parameter %s=%s ignored" % (k, v))
     if param.booster != "gbtree":
         raise SystemExit("only booster=gbtree is supported")
+    if ntree_limit < 0:
+        raise SystemExit("ntree_limit must not be negative")
+    if pred_leaf and pred_margin:
+        raise SystemExit("pred_leaf=1 and pred_margin=1 exclude each other")
     host = _native.host()
 
     def load(path):
@@ -157,8 +173,11 @@ def main(argv):
         path = test_data or data
         raw = load(path)
         dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse)
-        margin = b.predict_margin(dm)
+        # ntree_limit counts boosting rounds (K trees each); 0 or more than
+        # the model has: every tree
+        limit = ntree_limit * b.obj.n_group
         if task == "eval":
+            margin = b.predict_margin(dm, limit)
             metrics = param.eval_metric or [b.obj.default_metric()]
             b.obj.check_metrics(metrics)
             b.obj.check_labels(dm.label, bsp)
@@ -167,13 +186,23 @@ def main(argv):
             bsp.tracker_print(s.lstrip("\t"))
         else:
             # one value per line: n class ids (multi:softmax), n x K row-major
-            # probabilities (multi:softprob), else n predictions
-            pred = b.obj.pred(margin)
-            parts = bsp.comm.allgather_object(pred.float().cpu().reshape(-1).tolist())
+            # probabilities (multi:softprob), else n predictions; pred_margin:
+            # the untransformed margins, n or n x K row-major; pred_leaf: the
+            # n x T row-major node ids (the dump's numbering) of the leaves
+            fmt = "%d\n" if pred_leaf else "%g\n"
+            if pred_leaf:
+                pred = b.predict_leaf(dm, limit)
+            else:
+                margin = b.predict_margin(dm, limit)
+                if pred_margin:
+                    pred = margin if margin.dim() == 1 else margin.t()
+                else:
+                    pred = b.obj.pred(margin).float()
+            parts = bsp.comm.allgather_object(pred.cpu().reshape(-1).tolist())
             if bsp.rank == 0:
                 with open_uri(name_pred, "w") as f:
                     for part in parts:
-                        f.write("".join("%g\n" % p for p in part))
+                        f.write("".join(fmt % p for p in part))
         bsp.finalize()
         return 0
 

@@ -45,6 +45,15 @@ class DMatrix:
     def predict_tree(self, tree, margin):
         return tree.predict_margin(self.X, margin)
 
+    def predict_forest(self, forest, out, leaf=False):
+        """All trees of a packed forest (gbdt_tree.py Forest) in one pass over
+        the rows, on the GPU: margins [n] or [K, n] added to ``out`` exactly
+        as one predict_tree per tree would, or, leaf, leaf ids [n, T]."""
+        _native.hip().gbdt_predict_forest(X=self.X, nodes=forest.nodes, tree_off=forest.tree_off,
+                                          chunks=forest.chunks, max_feat=forest.max_feat,
+                                          out=out, leaf=leaf)
+        return out
+
 
 class CSRMatrix:
     """A rank's rows kept sparse (libsvm data with a wide feature space:
@@ -84,6 +93,13 @@ class CSRMatrix:
                                            *tree.device_arrays(self.device), margin)
             return margin
         return tree.predict_margin(self.dense_cpu(), margin)
+
+    def predict_forest(self, forest, out, leaf=False):
+        """As DMatrix.predict_forest, an absent feature standing for NaN."""
+        _native.hip().gbdt_predict_forest_csr(row_off=self.row_off, fid=self.fid, val=self.val,
+                                              nodes=forest.nodes, tree_off=forest.tree_off,
+                                              chunks=forest.chunks, out=out, leaf=leaf)
+        return out
 
     def dense_cpu(self):
         """(CPU reference path only: small matrices)"""

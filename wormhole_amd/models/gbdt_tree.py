@@ -81,12 +81,17 @@ class RegTree:
         if X.is_cuda:
             _native.hip().gbdt_predict(X, *self.device_arrays(X.device), margin)
             return margin
+        margin += torch.tensor(self.leaf)[self.leaf_index(X)]
+        return margin
+
+    def leaf_index(self, X):
+        """The node id of the leaf each row of a CPU matrix ends in (NaN takes
+        the default direction, a value equal to the threshold goes right)."""
         node = torch.zeros(X.shape[0], dtype=torch.long)
         feat = torch.tensor(self.feat)
         cond = torch.tensor(self.cond)
         left, right = torch.tensor(self.left), torch.tensor(self.right)
         defl = torch.tensor(self.defl, dtype=torch.bool)
-        leaf = torch.tensor(self.leaf)
         for _ in range(64):
             f = feat[node]
             active = f >= 0
@@ -96,8 +101,7 @@ class RegTree:
             go_left = torch.where(torch.isnan(v), defl[node], v < cond[node])
             nxt = torch.where(go_left, left[node], right[node])
             node = torch.where(active, nxt, node)
-        margin += leaf[node]
-        return margin
+        return node
 
     # -------------------------------------------------------------- dump
     def dump(self, fmap=None, with_stats=False):
@@ -188,6 +192,25 @@ def load_fmap(path):
     return names
 
 
+# ----------------------------------------------------------------- forest
+class Forest:
+    """Trees packed for the forest prediction kernels (csrc/host/
+    gbdt_forest_plan.h): one node table and the trees' offsets on the device,
+    and the chunks of whole trees, each walked by every row in one launch."""
+
+    def __init__(self, trees, device):
+        hip = _native.hip()
+        # (a tree a walk could leave or spin in: ValueError "malformed tree t")
+        nodes, tree_off, self.max_feat = hip.gbdt_forest_pack(
+            feat=[t.feat for t in trees], cond=[t.cond for t in trees],
+            left=[t.left for t in trees], right=[t.right for t in trees],
+            defl=[t.defl for t in trees], leaf=[t.leaf for t in trees])
+        self.ntree = len(trees)
+        self.chunks = hip.gbdt_forest_plan(tree_sizes=[len(t.feat) for t in trees],
+                                           lds_nodes=hip.gbdt_forest_lds_nodes())
+        self.nodes, self.tree_off = nodes.to(device), tree_off.to(device)
+
+
 # ---------------------------------------------------------------- booster
 class Booster:
     MAGIC = b"WHGB"
@@ -199,15 +222,55 @@ class Booster:
         self.obj = Objective(param.objective, param.num_class)
         self.base_margin = self.obj.prob_to_margin(param.base_score)
 
+    # Trees from which a GPU matrix is predicted by the forest kernels (one
+    # launch per chunk of trees) instead of one predict_tree per tree: the
+    # forest path was never the slower one, at one tree included
+    # (profiles/gbdt_forest_predict.txt)
+    FOREST_MIN_TREES = 1
+
+    def _ntree(self, ntree_limit):
+        """How many of the model's trees a limit means (0: all of them)."""
+        if ntree_limit < 0:
+            raise ValueError("ntree_limit must not be negative")
+        return min(ntree_limit, len(self.trees)) if ntree_limit else len(self.trees)
+
+    def forest(self, device, ntree=0):
+        """The first ``ntree`` trees (0: all) packed for the forest kernels on
+        ``device``; kept until the model's tree count or the limit changes.
+        Packing reads the trees' lists (a pending device tree is built here);
+        a tree that a walk could leave raises ValueError."""
+        ntree = self._ntree(ntree)
+        key = (torch.device(device), len(self.trees), ntree)
+        if self.__dict__.get("_forest_key") != key:
+            self._forest = Forest(self.trees[:ntree], device)
+            self._forest_key = key
+        return self._forest
+
     def predict_margin(self, dm, ntree_limit=0):
         """[n] margins, or [K, n] for K classes (tree t adds to row t % K)."""
         K = self.obj.n_group
         margin = torch.full((dm.n,) if K == 1 else (K, dm.n), self.base_margin,
                             dtype=torch.float32, device=dm.device)
-        trees = self.trees[:ntree_limit] if ntree_limit else self.trees
-        for i, t in enumerate(trees):
+        ntree = self._ntree(ntree_limit)
+        if torch.device(dm.device).type == "cuda" and ntree >= self.FOREST_MIN_TREES:
+            dm.predict_forest(self.forest(dm.device, ntree), margin)
+            return margin
+        for i, t in enumerate(self.trees[:ntree]):
             dm.predict_tree(t, margin if K == 1 else margin[i % K])
         return margin
+
+    def predict_leaf(self, dm, ntree_limit=0):
+        """int32 [n, T]: the node id (the dump's numbering) of the leaf each
+        row ends in, per tree."""
+        ntree = self._ntree(ntree_limit)
+        if torch.device(dm.device).type == "cuda" and ntree:
+            out = torch.empty((dm.n, ntree), dtype=torch.int32, device=dm.device)
+            dm.predict_forest(self.forest(dm.device, ntree), out, leaf=True)
+            return out
+        X = (dm.dense_cpu() if dm.sparse else dm.X).cpu()
+        cols = [t.leaf_index(X).to(torch.int32) for t in self.trees[:ntree]]
+        out = torch.stack(cols, 1) if cols else torch.empty((dm.n, 0), dtype=torch.int32)
+        return out.to(dm.device)
 
     def save(self, path):
         p = self.param
