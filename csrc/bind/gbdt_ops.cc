@@ -15,6 +15,7 @@
 #include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
+#include "host/gbdt_rank_plan.h"
 
 namespace wh_bind {
 namespace {
@@ -533,6 +534,103 @@ void gbdt_predict_forest_csr(const Tensor& row_off, const Tensor& fid,
                wh::gbdt_predict_forest_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid),
                                            optptr<float>(val), n, c, o, s);
              });
+}
+
+// ----------------------------------------------------- learning to rank
+// The task plan of a matrix's query groups (host/gbdt_rank_plan.h), on the
+// host: group_off, a CPU integer tensor [Q + 1] -> (small, block, tiled: int32
+// group ids, larger groups first; the rows of the largest block group and of
+// the largest tiled group). Malformed offsets raise ValueError.
+py::tuple gbdt_rank_plan(const Tensor& group_off, int64_t n, int64_t lds_rows) {
+  TORCH_CHECK(!group_off.is_cuda() && group_off.dim() == 1 &&
+                  at::isIntegralType(group_off.scalar_type(), false),
+              "gbdt_rank_plan: group_off must be a CPU integer vector");
+  const auto off = group_off.to(torch::kInt64).contiguous();
+  // (std::invalid_argument -> ValueError)
+  const auto p = wh::gbdt_rank_plan(off.data_ptr<int64_t>(), (size_t)off.numel(), n, lds_rows);
+  const auto ids = [](const std::vector<int32_t>& v) {
+    auto t = torch::empty({(int64_t)v.size()}, torch::kInt32);
+    if (!v.empty()) std::memcpy(t.data_ptr(), v.data(), v.size() * 4);
+    return t;
+  };
+  return py::make_tuple(ids(p.small), ids(p.block), ids(p.tiled), p.max_block_rows,
+                        p.max_tiled_rows);
+}
+
+namespace {
+// The checked inputs both ranking ops share -> the kernels' task lists.
+wh::RankTasks rank_args(const char* op, const Tensor& margin, const Tensor& label,
+                        const Tensor& group_off, const Tensor& small, const Tensor& block,
+                        const Tensor& tiled, int64_t block_rows, int64_t tiled_rows,
+                        int64_t tile_rows) {
+  CHECK_IN(margin, torch::kFloat32);
+  CHECK_IN(label, torch::kFloat32);
+  CHECK_IN(group_off, torch::kInt32);
+  CHECK_IN(small, torch::kInt32);
+  CHECK_IN(block, torch::kInt32);
+  CHECK_IN(tiled, torch::kInt32);
+  const int64_t n = margin.numel();
+  TORCH_CHECK(label.numel() == n && n <= INT32_MAX, op, ": label size mismatch");
+  TORCH_CHECK(group_off.numel() >= 1 && group_off.numel() - 1 <= INT32_MAX, op,
+              ": group_off must be [Q + 1]");
+  const int64_t cap = wh::gbdt_rank_lds_rows();
+  if (tile_rows <= 0) tile_rows = cap;
+  TORCH_CHECK(block_rows >= 0 && block_rows <= cap && tile_rows <= cap, op,
+              ": at most gbdt_rank_lds_rows() rows fit the LDS");
+  TORCH_CHECK(tiled_rows >= 0 && tiled_rows <= INT32_MAX, op, ": tiled_rows out of range");
+  TORCH_CHECK(std::max({small.numel(), block.numel(), tiled.numel()}) <= INT32_MAX, op,
+              ": too many tasks");
+  return {ptr<int32_t>(small), ptr<int32_t>(block), ptr<int32_t>(tiled),
+          (int)small.numel(), (int)block.numel(), (int)tiled.numel(),
+          (int)block_rows, (int)tiled_rows, (int)tile_rows};
+}
+}  // namespace
+
+// (gpair f32 [n, 2], stats f64 [4] = {sum g, sum h, max|g|, max|h|}) of
+// rank:pairwise, or, ndcg, rank:ndcg
+std::vector<Tensor> gbdt_gpair_rank(const Tensor& margin, const Tensor& label,
+                                    const Tensor& group_off, const Tensor& small,
+                                    const Tensor& block, const Tensor& tiled, int64_t block_rows,
+                                    int64_t tiled_rows, bool ndcg, int64_t tile_rows) {
+  const auto tk = rank_args("gbdt_gpair_rank", margin, label, group_off, small, block, tiled,
+                            block_rows, tiled_rows, tile_rows);
+  const int64_t n = margin.numel();
+  c10::DeviceGuard g(margin.device());
+  const auto f64 = margin.options().dtype(torch::kFloat64);
+  auto gp = torch::zeros({n, 2}, margin.options());
+  auto st = torch::zeros({4}, f64);
+  if (n > 0) {
+    const bool chunks = tk.ntiled > 0 || tk.nblock > 0;
+    auto aux = torch::empty({chunks ? 2 * n : 2}, margin.options());
+    auto idcg = torch::empty({chunks && ndcg ? n : 1}, f64);
+    auto scratch = torch::empty({wh::gbdt_rank_scratch()}, f64);
+    wh::gbdt_gpair_rank(ptr<float>(margin), ptr<float>(label), ptr<int32_t>(group_off),
+                        (int)group_off.numel() - 1, n, tk, ndcg, ptr<float>(aux), ptr<double>(idcg),
+                        ptr<float>(gp),
+                        ptr<double>(scratch), ptr<double>(st), cur_stream(margin));
+  }
+  return {gp, st};
+}
+
+// f64 [Q]: every group's ndcg@k (kind 0) or map@k (kind 1), NaN for an empty
+// group; k <= 0: no cut-off
+Tensor gbdt_rank_eval(const Tensor& margin, const Tensor& label, const Tensor& group_off,
+                      const Tensor& small, const Tensor& block, const Tensor& tiled,
+                      int64_t block_rows, int64_t tiled_rows, int64_t kind, int64_t k, bool minus,
+                      int64_t tile_rows) {
+  const auto tk = rank_args("gbdt_rank_eval", margin, label, group_off, small, block, tiled,
+                            block_rows, tiled_rows, tile_rows);
+  TORCH_CHECK(kind == 0 || kind == 1, "gbdt_rank_eval: kind is 0 (ndcg) or 1 (map)");
+  c10::DeviceGuard g(margin.device());
+  const int64_t Q = group_off.numel() - 1;
+  auto out = torch::full({Q}, std::numeric_limits<double>::quiet_NaN(),
+                         margin.options().dtype(torch::kFloat64));
+  const int kk = k <= 0 || k > INT32_MAX ? INT32_MAX : (int)k;
+  auto part = torch::empty({tk.nblock > 0 || tk.ntiled > 0 ? 2 * margin.numel() : 2}, out.options());
+  wh::gbdt_rank_eval(ptr<float>(margin), ptr<float>(label), ptr<int32_t>(group_off), (int)Q,
+                     margin.numel(), tk, (int)kind, kk, minus, ptr<double>(part), ptr<double>(out),
+                     cur_stream(margin));
+  return out;
 }
 
 // ------------------------------------------------------------ gbdt grower
@@ -1119,6 +1217,17 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_predict_forest_csr", &gbdt_predict_forest_csr, py::arg("row_off"), py::arg("fid"),
         py::arg("val"), py::arg("nodes"), py::arg("tree_off"), py::arg("chunks"), py::arg("out"),
         py::arg("leaf") = false);
+  m.def("gbdt_rank_plan", &gbdt_rank_plan, py::arg("group_off"), py::arg("n"),
+        py::arg("lds_rows") = (int64_t)wh::kRankLdsRows);
+  m.def("gbdt_rank_lds_rows", &wh::gbdt_rank_lds_rows);
+  m.def("gbdt_gpair_rank", &gbdt_gpair_rank, py::arg("margin"), py::arg("label"),
+        py::arg("group_off"), py::arg("small"), py::arg("block"), py::arg("tiled"),
+        py::arg("block_rows"), py::arg("tiled_rows"), py::arg("ndcg"), py::arg("tile_rows") = 0);
+  m.def("gbdt_rank_eval", &gbdt_rank_eval, py::arg("margin"), py::arg("label"),
+        py::arg("group_off"), py::arg("small"), py::arg("block"), py::arg("tiled"),
+        py::arg("block_rows"), py::arg("tiled_rows"), py::arg("kind"), py::arg("k"),
+        py::arg("minus"),
+        py::arg("tile_rows") = 0);
 }
 
 }  // namespace wh_bind

@@ -673,6 +673,37 @@ void gbdt_predict_forest(const float* X, int64_t n, int f, const ForestChunk& c,
 void gbdt_predict_forest_csr(const int64_t* row_off, const int32_t* fid, const float* val,
                              int64_t n, const ForestChunk& c, const ForestOut& o, hipStream_t s);
 
+// ---------------------------------------------------------- gbdt_rank.hip
+// Learning to rank over query groups: rows [group_off[q], group_off[q + 1])
+// are group q (int32 [Q + 1] on the device, n rows in all). The three task
+// lists hold group ids (host/gbdt_rank_plan.h): `small` groups of <= 64 rows
+// take a wavefront each, `block` and `tiled` groups a block per 256 rows
+// that moves the group through block_rows / tile_rows rows of LDS (at most
+// gbdt_rank_lds_rows(); one tile when the group fits). block_rows and
+// tiled_rows are the rows of the largest group of their list (they size the
+// grids; a larger group is still covered). A task whose id or offsets are
+// out of range is skipped. Nothing runs for n <= 0.
+struct RankTasks {
+  const int32_t *small, *block, *tiled;
+  int nsmall, nblock, ntiled;
+  int block_rows, tiled_rows, tile_rows;
+};
+// gpair [n, 2] of rank:pairwise (ndcg: rank:ndcg) and stats [4] = {sum g,
+// sum h, max |g|, max |h|}; aux: 2 n floats and, ndcg, idcg: n doubles of
+// workspace (the larger groups' pass 1 leaves every row's {1 / c, discount}
+// and the chunks' IDCG shares there); scratch: gbdt_rank_scratch() doubles.
+int64_t gbdt_rank_scratch();
+void gbdt_gpair_rank(const float* margin, const float* label, const int32_t* group_off, int Q,
+                     int64_t n, const RankTasks& tk, bool ndcg, float* aux, double* idcg,
+                     float* gpair, double* scratch, double* stats, hipStream_t s);
+// out [Q]: group q's ndcg@k (kind 0) or map@k (kind 1), k = INT32_MAX for no
+// cut-off; a group whose denominator is 0 scores 1, or 0 with `minus`. The
+// entries of empty groups (and of groups in no list) are left as they are.
+// part: 2 n doubles of workspace (the larger groups' partial sums).
+void gbdt_rank_eval(const float* margin, const float* label, const int32_t* group_off, int Q,
+                    int64_t n, const RankTasks& tk, int kind, int k, bool minus, double* part,
+                    double* out, hipStream_t s);
+
 // ------------------------------------------------------------- ingest.hip
 // Criteo / libsvm text -> CSR minibatch on the device (keys bit-identical to
 // the host parsers'). text_lines: start [nlines + 1] of the lines of

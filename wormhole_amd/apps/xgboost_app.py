@@ -4,7 +4,8 @@ learn/xgboost/run_yarn.sh; SURVEY §2.2 "xgboost"):
 
 tasks ``train | pred | dump | eval``; parameters booster, objective
 (binary:logistic, binary:logitraw, reg:logistic, reg:linear,
-reg:squarederror, multi:softmax, multi:softprob), num_class (the multi:
+reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg),
+num_class (the multi:
 objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
@@ -18,6 +19,17 @@ boosting rounds, N x num_class trees; 0 or more than the model has: all), for
 task=pred pred_margin (write the untransformed margins: n lines, or n x K
 row-major for a multi: objective) and pred_leaf (write n x T row-major leaf
 node ids, numbered as in task=dump; not together with pred_margin).
+
+Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
+map@k (each optionally with a trailing ``-``: a group without a relevant row
+scores 0 instead of 1; allowed with any single-output objective) need the
+rows' query groups. They come from ``<path>.group`` beside a data path (for
+``data#cache`` the path before ``#``): one non-negative integer per line, a
+group's row count, in file order; the counts must sum to the rows of the
+data. It is looked for beside data, test:data and every eval[name] path
+(task=pred needs none); the data path must then be a single file. With
+several ranks a group cut by a rank boundary counts as two groups (docs/
+bsp_apps.md "Ranking"). Instance weights are refused with a rank: objective.
 Output: ``[r]\\t<set>-<metric>:<value>`` lines per round.
 """
 import os
@@ -159,6 +171,55 @@ def main(argv):
             w.close()
         return blk
 
+    def load_group(path, nlocal):
+        """The query groups of this rank's nlocal rows of ``path`` from
+        ``<path>.group`` (group sizes, one per line) -> local offsets
+        [Q + 1] (int64), or None when there is no such file. Every rank holds
+        a contiguous range of the file's rows, in rank order: its first
+        global row comes from one allgather of the row counts, and the
+        groups are intersected with its range (a group cut by the boundary
+        becomes two groups, one on each rank)."""
+        base = path.split("#", 1)[0]
+        gpath = base + ".group"
+        if host.file_size(gpath) <= 0:
+            return None
+        # (a data path is one file here: load() reads `path` itself, never a
+        # directory or a pattern, so the sizes describe exactly its rows)
+        try:
+            sizes = torch.tensor([int(t) for t in open_uri(gpath).read().split()],
+                                 dtype=torch.int64)
+        except ValueError as e:
+            raise SystemExit("%s: %s" % (gpath, e))
+        if bool((sizes < 0).any()):
+            raise SystemExit("%s: a negative group size" % gpath)
+        counts = bsp.comm.allgather_object(int(nlocal))
+        first, total = sum(counts[:bsp.rank]), sum(counts)
+        if int(sizes.sum()) != total:
+            raise SystemExit("%s: the group sizes sum to %d, the data has %d rows"
+                             % (gpath, int(sizes.sum()), total))
+        ends = (sizes.cumsum(0) - first).clamp(0, int(nlocal))
+        local = torch.diff(ends, prepend=torch.zeros(1, dtype=torch.int64))
+        local = local[local > 0]
+        return torch.cat([torch.zeros(1, dtype=torch.int64), local.cumsum(0)])
+
+    def check_rank_data(obj, metrics, sets):
+        """What ranking asks of the data: sets = [(name, path, matrix,
+        trains, evaluated)]. A set the rank objective trains on, or a rank
+        metric is evaluated on, needs its group file (the same answer on
+        every rank); a rank objective refuses instance weights (the flag is
+        allreduced before anyone raises, so no rank is left waiting in a
+        collective)."""
+        want = [m for m in metrics if G.parse_rank_metric(m)]
+        for name, path, d, trains, evaluated in sets:
+            for who, needs in (("objective " + obj.name, obj.rank and trains),
+                               ("eval_metric " + (want or [""])[0], bool(want) and evaluated)):
+                if needs and d.group is None:
+                    raise SystemExit("%s needs query groups: there is no %s.group (the %s data)"
+                                     % (who, path.split("#", 1)[0], name))
+            if obj.rank and trains and bsp.allreduce_scalar(
+                    1.0 if d.weight is not None else 0.0, "max") > 0:
+                raise ValueError("instance weights are not defined for objective " + obj.name)
+
     if task == "dump":
         if bsp.rank == 0:
             b = G.Booster.load(model_in, param)
@@ -172,7 +233,8 @@ def main(argv):
         b = G.Booster.load(model_in, param)
         path = test_data or data
         raw = load(path)
-        dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse)
+        group = load_group(path, raw[3].numel()) if task == "eval" else None
+        dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse, group=group)
         # ntree_limit counts boosting rounds (K trees each); 0 or more than
         # the model has: every tree
         limit = ntree_limit * b.obj.n_group
@@ -180,8 +242,9 @@ def main(argv):
             margin = b.predict_margin(dm, limit)
             metrics = param.eval_metric or [b.obj.default_metric()]
             b.obj.check_metrics(metrics)
+            check_rank_data(b.obj, metrics, [("test", path, dm, False, True)])
             b.obj.check_labels(dm.label, bsp)
-            vals = b.obj.metrics(metrics, margin, dm.label, dm.weight, bsp)
+            vals = b.obj.metrics(metrics, margin, dm.label, dm.weight, bsp, dm.rank_groups())
             s = "".join("\ttest-%s:%f" % (m, v) for m, v in zip(metrics, vals))
             bsp.tracker_print(s.lstrip("\t"))
         else:
@@ -215,9 +278,11 @@ def main(argv):
     ncol = max([int(r[0].max().item()) + 1 if r[0].numel() else 0
                 for r in [train_raw] + [e[1] for e in eval_raw]] + [num_feature])
     ncol = int(bsp.allreduce_scalar(ncol, "max", torch.int64))
-    dtrain = G.make_dmatrix(*train_raw, ncol=ncol, device=dev, sparse=dsparse)
-    deval = [(name, G.make_dmatrix(*r, ncol=ncol, device=dev, sparse=dsparse))
-             for name, r in eval_raw]
+    dtrain = G.make_dmatrix(*train_raw, ncol=ncol, device=dev, sparse=dsparse,
+                            group=load_group(data, train_raw[3].numel()))
+    deval = [(name, G.make_dmatrix(*r, ncol=ncol, device=dev, sparse=dsparse,
+                                   group=load_group(path, r[3].numel())))
+             for (name, r), (_, path) in zip(eval_raw, evals)]
     booster = G.Booster.load(model_in, param) if model_in else G.Booster(param, ncol)
     version, gstate, _ = bsp.load_checkpoint()
     if version > 0:
@@ -229,6 +294,8 @@ def main(argv):
         print("restart from version=%d (round %d)" % (version, start), flush=True)
     metrics = param.eval_metric or [obj.default_metric()]
     obj.check_metrics(metrics)
+    check_rank_data(obj, metrics, [("train", data, dtrain, True, bool(eval_train))] + [
+        (name, path, d, False, True) for (name, d), (_, path) in zip(deval, evals)])
     for d in [dtrain] + [d for _, d in deval]:
         obj.check_labels(d.label, bsp)
     margin = booster.predict_margin(dtrain)
@@ -236,7 +303,7 @@ def main(argv):
     # the row's hessians summed over the classes)
     hess = None
     if dtrain.n:
-        hess = obj.gpair(margin, dtrain.label, None)[..., 1]
+        hess = obj.gpair(margin, dtrain.label, None, dtrain.rank_groups())[..., 1]
         hess = hess.sum(0) if K > 1 else hess
     cuts = G.Cuts.build(dtrain, param.max_bin, bsp, hess=hess)
     B = cuts.bin(dtrain)
@@ -251,11 +318,12 @@ def main(argv):
         for (name, d), em in zip(deval, emargins):
             for k, tree in enumerate(new):
                 d.predict_tree(tree, em[k] if K > 1 else em)
-            for m, v in zip(metrics, obj.metrics(metrics, em, d.label, d.weight, bsp)):
+            for m, v in zip(metrics, obj.metrics(metrics, em, d.label, d.weight, bsp,
+                                                 d.rank_groups())):
                 msg += "\t%s-%s:%f" % (name, m, v)
         if eval_train:
             for m, v in zip(metrics, obj.metrics(metrics, margin, dtrain.label, dtrain.weight,
-                                                 bsp)):
+                                                 bsp, dtrain.rank_groups())):
                 msg += "\ttrain-%s:%f" % (m, v)
         bsp.tracker_print(msg)
         if save_period and (r + 1) % save_period == 0 and bsp.rank == 0:

@@ -29,8 +29,10 @@ from .. import _native
 # matrices and cuts, the trees and the model (every public name stays
 # reachable from this module)
 from .gbdt_objective import (GBDTParam, MULTI_METRICS, NLL_MAX, Objective,  # noqa: F401
-                             SINGLE_METRICS, class_gpair, eval_metric, first_argmax,
-                             gpair_stats, multi_eval_sums, softmax_gpair_torch)
+                             RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
+                             eval_metric, first_argmax, gpair_stats, multi_eval_sums,
+                             parse_rank_metric, rank_eval, rank_eval_torch, rank_gpair_torch,
+                             rank_metric, softmax_gpair_torch)
 from .gbdt_data import MISSING_BIN, CSRMatrix, Cuts, DMatrix, make_dmatrix  # noqa: F401
 from .gbdt_tree import Booster, RegTree, _DeviceTree, load_fmap  # noqa: F401
 
@@ -764,10 +766,12 @@ def boost_round(obj, builder, dm, margin, gen=None, fgen=None):
     gradient call, then one tree per class on its own slice of the pairs and
     margins (a single tree for a single-output objective). ``subsample``
     (rows, from ``gen``) and ``colsample_bytree`` (features, from ``fgen``)
-    are drawn per tree. Returns the new trees in class order."""
+    are drawn per tree. A rank objective takes the rows' query groups from
+    ``dm.group``. Returns the new trees in class order."""
     p = builder.p
     K = obj.n_group
-    gp = obj.gpair(margin, dm.label, dm.weight)
+    # (a rank objective's query groups: the matrix's, with their cached task plan)
+    gp = obj.gpair(margin, dm.label, dm.weight, dm.rank_groups())
     new = []
     for k in range(K):
         gk, mk = (class_gpair(gp, k), margin[k]) if K > 1 else (gp, margin)

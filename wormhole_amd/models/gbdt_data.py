@@ -8,13 +8,37 @@ from .. import _native
 MISSING_BIN = 255
 
 
+class _QueryGroups:
+    """What both matrices keep of their rows' query groups (learning to
+    rank): ``group``, the int32 offsets [Q + 1] on the matrix's device (rows
+    [group[q], group[q + 1]) are group q) or None, and the ranking kernels'
+    task plan, built once per matrix on first use."""
+
+    group = None
+    _rank_groups = None
+
+    def set_group(self, group):
+        """group: integer offsets [Q + 1] (any device) or None. Malformed
+        offsets raise ValueError."""
+        from .gbdt_objective import RankGroups
+        self.group = self._rank_groups = None
+        if group is not None:
+            self._rank_groups = RankGroups(group, self.n)
+            self.group = self._rank_groups.device_off(self.device)
+
+    def rank_groups(self):
+        """The groups with their cached task plan (objective and metrics
+        take it as ``group``), or None."""
+        return self._rank_groups
+
+
 # ------------------------------------------------------------------- data
-class DMatrix:
+class DMatrix(_QueryGroups):
     """A rank's rows as a dense device matrix with NaN = missing."""
 
     sparse = False
 
-    def __init__(self, keys, offset, val, label, weight, ncol, device):
+    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None):
         n = offset.numel() - 1
         self.n = n
         self.ncol = int(ncol)
@@ -30,9 +54,10 @@ class DMatrix:
         self.label = label.to(device).float()
         self.weight = weight.to(device).float() if weight is not None else None
         self.B = None
+        self.set_group(group)
 
     @staticmethod
-    def from_dense(X, label, device):
+    def from_dense(X, label, device, group=None):
         d = DMatrix.__new__(DMatrix)
         d.n, d.ncol = X.shape
         d.device = device
@@ -40,6 +65,7 @@ class DMatrix:
         d.label = label.to(device).float()
         d.weight = None
         d.B = None
+        d.set_group(group)
         return d
 
     def predict_tree(self, tree, margin):
@@ -55,7 +81,7 @@ class DMatrix:
         return out
 
 
-class CSRMatrix:
+class CSRMatrix(_QueryGroups):
     """A rank's rows kept sparse (libsvm data with a wide feature space:
     a dense n x ncol matrix would not fit). Row feature ids are sorted
     ascending within each row; a feature a row does not store is missing
@@ -63,7 +89,7 @@ class CSRMatrix:
 
     sparse = True
 
-    def __init__(self, keys, offset, val, label, weight, ncol, device):
+    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None):
         n = offset.numel() - 1
         self.n, self.ncol, self.device = n, int(ncol), device
         off = offset.to(torch.int64)
@@ -80,6 +106,7 @@ class CSRMatrix:
         self.label = label.to(device).float()
         self.weight = weight.to(device).float() if weight is not None else None
         self.gbin = None
+        self.set_group(group)
 
     def entry_rows(self):
         return torch.repeat_interleave(torch.arange(self.n, device=self.device),
@@ -111,16 +138,17 @@ class CSRMatrix:
         return X
 
 
-def make_dmatrix(keys, offset, val, label, weight, ncol, device, sparse=None):
+def make_dmatrix(keys, offset, val, label, weight, ncol, device, sparse=None, group=None):
     """Dense device matrix, or CSR when asked (sparse=True) or when the dense
-    form would be large and mostly missing (auto: sparse=None)."""
+    form would be large and mostly missing (auto: sparse=None). group: the
+    rows' query group offsets [Q + 1] (learning to rank) or None."""
     n = offset.numel() - 1
     if sparse is None:
         cells = n * max(int(ncol), 1)
         sparse = int(ncol) > 4096 or (cells > (1 << 28) and keys.numel() < cells // 8)
     if sparse:
-        return CSRMatrix(keys, offset, val, label, weight, ncol, device)
-    return DMatrix(keys, offset, val, label, weight, ncol, device)
+        return CSRMatrix(keys, offset, val, label, weight, ncol, device, group)
+    return DMatrix(keys, offset, val, label, weight, ncol, device, group)
 
 
 class Cuts:

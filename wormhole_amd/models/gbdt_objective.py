@@ -1,6 +1,8 @@
-"""GBDT parameters, objectives (single-output and multi-class softmax, with
-their gradient pairs) and globally reduced metrics; models/gbdt.py grows the trees."""
+"""GBDT parameters, objectives (single-output, multi-class softmax and
+learning to rank over query groups, with their gradient pairs) and globally
+reduced metrics; models/gbdt.py grows the trees."""
 import math
+import re
 
 import torch
 
@@ -70,7 +72,18 @@ def _threshold_l1(G, alpha):
 # ---------------------------------------------------------------- objective
 MULTI_METRICS = ("merror", "mlogloss")
 SINGLE_METRICS = ("error", "logloss", "rmse", "auc")
+RANK_OBJECTIVES = ("rank:pairwise", "rank:ndcg")
 NLL_MAX = -math.log(1e-16)
+_RANK_METRIC = re.compile(r"^(ndcg|map)(?:@(\d+))?(-)?$")
+
+
+def parse_rank_metric(name):
+    """xgboost's ranking metric names ``ndcg | map`` [``@k``] [``-``] ->
+    (kind, k or 0 for no cut-off, minus), or None for any other name."""
+    m = _RANK_METRIC.match(name)
+    if m is None:
+        return None
+    return m.group(1), int(m.group(2)) if m.group(2) else 0, m.group(3) is not None
 
 
 class Objective:
@@ -78,13 +91,16 @@ class Objective:
     multi:softprob keep ``num_class`` margins per row, class-major
     (margin [K, n], gpair [K, n, 2]), so ``margin[k]`` / ``gpair[k]`` are the
     contiguous tensors a tree builder takes: one round grows K trees, tree t
-    of the flat list belongs to class t % K."""
+    of the flat list belongs to class t % K. rank:pairwise and rank:ndcg keep
+    one margin per row (the prediction is the margin) and need the rows'
+    query groups (``DMatrix.group``) for their gradient pairs."""
 
     def __init__(self, name, num_class=0):
         if name not in ("binary:logistic", "reg:logistic", "reg:linear", "reg:squarederror",
-                        "binary:logitraw", "multi:softmax", "multi:softprob"):
+                        "binary:logitraw", "multi:softmax", "multi:softprob") + RANK_OBJECTIVES:
             raise ValueError("unknown objective " + name)
         self.name = name
+        self.rank = name in RANK_OBJECTIVES
         self.logistic = name in ("binary:logistic", "reg:logistic", "binary:logitraw")
         self.multi = name.startswith("multi:")
         if self.multi and int(num_class) < 2:
@@ -109,6 +125,10 @@ class Objective:
 
     def check_metrics(self, names):
         for m in names:
+            if parse_rank_metric(m) is not None:  # any single-output objective, as in xgboost
+                if self.multi:
+                    raise ValueError("eval_metric %s does not fit objective %s" % (m, self.name))
+                continue
             if m not in MULTI_METRICS + SINGLE_METRICS:
                 raise ValueError("unknown eval_metric " + m)
             if (m in MULTI_METRICS) != self.multi:
@@ -123,7 +143,11 @@ class Objective:
             return -math.log(1.0 / base - 1.0)
         return base
 
-    def gpair(self, margin, label, weight):
+    def gpair(self, margin, label, weight, group=None):
+        """group: the rank objectives' query groups, a :class:`RankGroups`
+        (``DMatrix.group``) or the int32 offsets [Q + 1]."""
+        if self.rank:
+            return self._gpair_rank(margin, label, weight, group)
         if self.multi:
             return self._gpair_softmax(margin, label, weight)
         if margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32:
@@ -143,6 +167,26 @@ class Objective:
         if weight is not None:
             g, h = g * weight, h * weight
         return torch.stack([g, h], 1).float().contiguous()
+
+    def _gpair_rank(self, margin, label, weight, group):
+        """The expectation of xgboost's random partner draw over a row's
+        query group (:func:`rank_gpair_torch` has the formulas). On the GPU
+        one launch per task class plus the root statistics."""
+        if group is None:
+            raise ValueError("objective %s needs query groups (a <data>.group file)" % self.name)
+        if weight is not None:
+            raise ValueError("instance weights are not defined for objective " + self.name)
+        group = RankGroups.of(group)
+        ndcg = self.name == "rank:ndcg"
+        if margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32:
+            small, block, tiled, rows, tiled_rows = group.tasks(margin.device)
+            gp, st = _native.hip().gbdt_gpair_rank(
+                margin=margin.contiguous(), label=label.contiguous(),
+                group_off=group.device_off(margin.device), small=small, block=block, tiled=tiled,
+                block_rows=rows, tiled_rows=tiled_rows, ndcg=ndcg)
+            gp._wh_stats = st
+            return gp
+        return rank_gpair_torch(margin, label, group.off, ndcg).float().contiguous()
 
     def _gpair_softmax(self, margin, label, weight):
         """margin [K, n] -> gpair [K, n, 2]: p = softmax over the classes,
@@ -176,10 +220,16 @@ class Objective:
     def default_metric(self):
         if self.multi:
             return "merror"
+        if self.rank:
+            return "map"
         return "error" if self.name == "binary:logistic" else "rmse"
 
-    def metrics(self, names, margin, label, weight, bsp):
-        """Globally reduced metrics of a set from its margins. Multi-class:
+    def metrics(self, names, margin, label, weight, bsp, group=None):
+        """Globally reduced metrics of a set from its margins. The ranking
+        metrics (ndcg, map, with ``@k`` and ``-``) are the unweighted mean of
+        the per-group values over the non-empty groups of every rank: one
+        evaluation (on the GPU one launch per task class, ``gbdt_rank_eval``)
+        and one allreduce of {sum, count}. Multi-class:
         merror = sum w [arg-max != y] / sum w and mlogloss = sum w (-log
         max(p_y, 1e-16)) / sum w from ONE reduction {sum w err, sum w nll,
         sum w} (on the GPU one launch, ``gbdt_multi_eval``) and one allreduce
@@ -188,7 +238,8 @@ class Objective:
         self.check_metrics(names)
         if not self.multi:
             p = self.pred(margin)
-            return [eval_metric(m, p, label, weight, bsp) for m in names]
+            return [rank_metric(m, margin, label, group, bsp) if parse_rank_metric(m)
+                    else eval_metric(m, p, label, weight, bsp) for m in names]
         v = multi_eval_sums(margin, label, weight)
         bsp.allreduce(v)
         v = v.tolist()
@@ -293,3 +344,248 @@ def eval_metric(name, pred, label, weight, bsp):
     raise ValueError("unknown eval_metric " + name)
 
 
+# ------------------------------------------------------- learning to rank
+class RankGroups:
+    """The query groups of a matrix: rows [off[q], off[q + 1]) are group q
+    (int32 offsets [Q + 1] on the host, the first 0, non-decreasing, the last
+    n; empty groups are legal). The device copy and the kernels' task plan
+    (csrc/host/gbdt_rank_plan.h) are made once per device and kept."""
+
+    def __init__(self, off, n=None):
+        off = torch.as_tensor(off).detach().cpu()
+        if off.dim() != 1 or off.is_floating_point():
+            raise ValueError("group offsets must be an integer vector [Q + 1]")
+        off = off.long()
+        n = int(off[-1]) if n is None and off.numel() else int(n or 0)
+        # (the plan validates: ValueError for malformed offsets)
+        self._plan = _native.hip().gbdt_rank_plan(off, n)
+        self.off = off.to(torch.int32)
+        self.n = n
+        self._dev = {}
+
+    @staticmethod
+    def of(group):
+        return group if isinstance(group, RankGroups) else RankGroups(group)
+
+    @staticmethod
+    def from_sizes(sizes):
+        sizes = torch.as_tensor(sizes, dtype=torch.int64)
+        return RankGroups(torch.cat([torch.zeros(1, dtype=torch.int64), sizes.cumsum(0)]))
+
+    @property
+    def num_group(self):
+        return self.off.numel() - 1
+
+    def _on(self, device):
+        device = torch.device(device)
+        d = self._dev.get(device)
+        if d is None:
+            small, block, tiled, rows, tiled_rows = self._plan
+            d = self._dev[device] = (self.off.to(device), small.to(device), block.to(device),
+                                     tiled.to(device), int(rows), int(tiled_rows))
+        return d
+
+    def device_off(self, device):
+        return self._on(device)[0]
+
+    def tasks(self, device):
+        """(small, block, tiled: int32 group ids on the device; the rows of
+        the largest block group and of the largest tiled group)"""
+        return self._on(device)[1:]
+
+
+def _rank_batches(off, budget):
+    """Non-empty groups, larger first, cut into batches of similar size: each
+    ([group ids], L = its largest size) pads to [G, L] with G L^2 <= budget
+    where it can and sizes of at least L / 2 (any size once L <= 16)."""
+    sizes = (off[1:] - off[:-1]).long()
+    order = torch.argsort(sizes, descending=True, stable=True)
+    order = order[sizes[order] > 0]
+    s, o = sizes[order].tolist(), order.tolist()
+    out, a = [], 0
+    while a < len(o):
+        L = s[a]
+        cap = max(1, budget // (L * L))
+        b = a + 1
+        while b < len(o) and b - a < cap and (2 * s[b] >= L or L <= 16):
+            b += 1
+        out.append((o[a:b], L))
+        a = b
+    return out
+
+
+class _RankBatch:
+    """A padded batch [G, L] of groups: margins M, labels Y, validity, the
+    rows' global indices, and pair masks of a chunk of rows [a, b)."""
+
+    def __init__(self, margin, label, off, gids, L):
+        dev = margin.device
+        g = torch.tensor(gids, dtype=torch.long, device=dev)
+        beg = off[g]
+        self.ar = torch.arange(L, device=dev)
+        self.valid = self.ar[None, :] < (off[g + 1] - beg)[:, None]
+        self.idx = (beg[:, None] + self.ar[None, :]).clamp(max=max(margin.numel() - 1, 0))
+        self.M, self.Y = margin[self.idx], label[self.idx]
+        self.G, self.L = len(gids), L
+
+    def chunks(self, budget):
+        step = max(1, budget // (self.G * self.L))
+        return [(a, min(self.L, a + step)) for a in range(0, self.L, step)]
+
+    def pairs(self, X, a, b):
+        """(X_i [G, b - a, 1], X_j [G, 1, L])"""
+        return X[:, a:b, None], X[:, None, :]
+
+    def ranks(self, X, a, b):
+        """Rows j ahead of row i by X: X_j > X_i, or equal and j before i."""
+        xi, xj = self.pairs(X, a, b)
+        before = self.ar[None, None, :] < self.ar[None, a:b, None]
+        return ((xj > xi) | ((xj == xi) & before)) & self.valid[:, None, :]
+
+    def scatter(self, out, val):
+        out[self.idx[self.valid]] = val[self.valid]
+
+
+def _discount(r):
+    return 1.0 / torch.log2(2.0 + r.double())
+
+
+def rank_gpair_torch(margin, label, group_off, ndcg, mass=False, budget=1 << 22):
+    """Gradient pairs [n, 2] of rank:pairwise / rank:ndcg in plain torch: the
+    CPU path and the reference of ``gbdt_gpair_rank`` (CPU or GPU tensors).
+
+    Within a group, c_i = rows with another label, r_i / lr_i = rows ahead of
+    i by margin / by label (ties: the earlier row is ahead), gain = 2^y - 1,
+    IDCG = sum gain_i / log2(2 + lr_i). Every pair with y_i > y_j weighs
+    W = (1 / c_i + 1 / c_j) * delta, delta = 1 (pairwise) or |gain_i - gain_j|
+    |1 / log2(2 + r_i) - 1 / log2(2 + r_j)| / IDCG (ndcg; 0 when IDCG = 0):
+    the expectation of drawing, for every row, one partner with a different
+    label uniformly. With rho = sigmoid(m_i - m_j), lambda = rho - 1 and eta =
+    max(rho (1 - rho), 1e-16): g_i += W lambda, g_j -= W lambda, h_i and h_j
+    += 2 W eta. Per-pair terms are in the margins' precision (the discounts
+    and IDCG are taken in fp64 and rounded once); a row's sums are fp64,
+    rounded once to the margins' precision. mass: also return the rows' fp64
+    sum of W |lambda| (the scale of g's rounding error)."""
+    T = margin.dtype
+    n, dev = margin.numel(), margin.device
+    off = torch.as_tensor(group_off).to(dev).long()
+    g_out = torch.zeros(n, dtype=torch.float64, device=dev)
+    h_out, m_out = torch.zeros_like(g_out), torch.zeros_like(g_out)
+    label = label.to(T)
+    for gids, L in _rank_batches(off.cpu(), budget):
+        bt = _RankBatch(margin, label, off, gids, L)
+        vj = bt.valid[:, None, :]
+        c = torch.zeros(bt.G, L, dtype=torch.long, device=dev)
+        r, lr = torch.zeros_like(c), torch.zeros_like(c)
+        for a, b in bt.chunks(budget):
+            yi, yj = bt.pairs(bt.Y, a, b)
+            c[:, a:b] = ((yj != yi) & vj).sum(-1)
+            if ndcg:
+                r[:, a:b] = bt.ranks(bt.M, a, b).sum(-1)
+                lr[:, a:b] = bt.ranks(bt.Y, a, b).sum(-1)
+        invc = torch.where(c > 0, 1.0 / c.to(T), torch.zeros((), dtype=T, device=dev))
+        if ndcg:
+            gain = torch.exp2(bt.Y) - 1.0
+            disc = _discount(r).to(T)
+            idcg = (gain.double() * _discount(lr) * bt.valid).sum(-1)
+            inv_idcg = torch.where(idcg > 0, 1.0 / idcg, torch.zeros_like(idcg)).to(T)
+        gs = torch.zeros(bt.G, L, dtype=torch.float64, device=dev)
+        hs, ms = torch.zeros_like(gs), torch.zeros_like(gs)
+        for a, b in bt.chunks(budget):
+            mi, mj = bt.pairs(bt.M, a, b)
+            yi, yj = bt.pairs(bt.Y, a, b)
+            w = invc[:, a:b, None] + invc[:, None, :]
+            if ndcg:
+                gi, gj = bt.pairs(gain, a, b)
+                di, dj = bt.pairs(disc, a, b)
+                w = w * ((gi - gj).abs() * (di - dj).abs() * inv_idcg[:, None, None])
+            part = (yi != yj) & vj
+            hi = yi > yj
+            d = torch.where(hi, mi - mj, mj - mi)  # m_hi - m_lo
+            t = torch.exp(-d.abs())
+            s = 1.0 / (1.0 + t)
+            ts = t * s
+            rho = torch.where(d >= 0, s, ts)
+            q = torch.where(d >= 0, ts, s)  # 1 - rho, without cancellation
+            eta = (rho * q).clamp(min=1e-16)
+            wl = w * -q
+            zero = torch.zeros((), dtype=T, device=dev)
+            gs[:, a:b] = torch.where(part, torch.where(hi, wl, -wl), zero).double().sum(-1)
+            hs[:, a:b] = torch.where(part, 2.0 * w * eta, zero).double().sum(-1)
+            if mass:
+                ms[:, a:b] = torch.where(part, w * q, zero).double().sum(-1)
+        bt.scatter(g_out, gs)
+        bt.scatter(h_out, hs)
+        bt.scatter(m_out, ms)
+    gp = torch.stack([g_out, h_out], 1).to(T).contiguous()
+    return (gp, m_out) if mass else gp
+
+
+def rank_eval_torch(margin, label, group_off, kind, k=0, minus=False, budget=1 << 22):
+    """Per-group ndcg@k (kind "ndcg") or map@k ("map") in plain torch, fp64
+    [Q] with NaN for an empty group (k = 0: no cut-off): the CPU path and the
+    reference of ``gbdt_rank_eval``. ndcg@k = (sum over r_i < k of gain_i /
+    log2(2 + r_i)) / (the same over lr_i < k with lr_i). map@k: a hit is
+    y_i > 0, hits_i = hits j with r_j <= r_i, map = (sum over hits i with
+    r_i < k of hits_i / (r_i + 1)) / (hits of the whole group). A group whose
+    denominator is 0 scores 1, or, minus, 0."""
+    if kind not in ("ndcg", "map"):
+        raise ValueError("unknown ranking metric " + kind)
+    dev = margin.device
+    off = torch.as_tensor(group_off).to(dev).long()
+    Q = off.numel() - 1
+    out = torch.full((Q,), float("nan"), dtype=torch.float64, device=dev)
+    kk = int(k) if k and k > 0 else (1 << 62)
+    label = label.to(margin.dtype)
+    for gids, L in _rank_batches(off.cpu(), budget):
+        bt = _RankBatch(margin, label, off, gids, L)
+        r = torch.zeros(bt.G, L, dtype=torch.long, device=dev)
+        lr, hits = torch.zeros_like(r), torch.zeros_like(r)
+        hit = (bt.Y > 0) & bt.valid
+        for a, b in bt.chunks(budget):
+            ahead = bt.ranks(bt.M, a, b)
+            r[:, a:b] = ahead.sum(-1)
+            if kind == "ndcg":
+                lr[:, a:b] = bt.ranks(bt.Y, a, b).sum(-1)
+            else:
+                me = bt.ar[None, None, :] == bt.ar[None, a:b, None]
+                hits[:, a:b] = ((ahead | me) & hit[:, None, :]).sum(-1)
+        if kind == "ndcg":
+            gain = torch.exp2(bt.Y.double()) - 1.0
+            num = (gain * _discount(r) * (bt.valid & (r < kk))).sum(-1)
+            den = (gain * _discount(lr) * (bt.valid & (lr < kk))).sum(-1)
+        else:
+            num = (hits.double() / (r + 1).double() * (hit & (r < kk))).sum(-1)
+            den = hit.sum(-1).double()
+        val = torch.where(den > 0, num / den.clamp(min=1e-300),
+                          torch.full_like(num, 0.0 if minus else 1.0))
+        out[torch.tensor(gids, dtype=torch.long, device=dev)] = val
+    return out
+
+
+def rank_eval(margin, label, group, kind, k=0, minus=False):
+    """Per-group ranking metric values, fp64 [Q] (NaN: an empty group): on
+    the GPU ``gbdt_rank_eval``, else :func:`rank_eval_torch`."""
+    group = RankGroups.of(group)
+    if margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32:
+        small, block, tiled, rows, tiled_rows = group.tasks(margin.device)
+        return _native.hip().gbdt_rank_eval(
+            margin=margin.contiguous(), label=label.contiguous(),
+            group_off=group.device_off(margin.device), small=small, block=block, tiled=tiled,
+            block_rows=rows, tiled_rows=tiled_rows, kind=0 if kind == "ndcg" else 1, k=int(k), minus=bool(minus))
+    return rank_eval_torch(margin, label, group.off, kind, k, minus)
+
+
+def rank_metric(name, margin, label, group, bsp):
+    """A ranking metric's global value: the mean of the per-group values over
+    the non-empty groups of all ranks (a group cut by a rank boundary counts
+    as two)."""
+    kind, k, minus = parse_rank_metric(name)
+    if group is None:
+        raise ValueError("eval_metric %s needs query groups (a <data>.group file)" % name)
+    v = rank_eval(margin, label, group, kind, k, minus)
+    ok = ~torch.isnan(v)
+    s = torch.stack([torch.where(ok, v, torch.zeros_like(v)).sum(), ok.sum().double()])
+    bsp.allreduce(s)
+    s = s.tolist()
+    return s[0] / s[1] if s[1] > 0 else 0.0
