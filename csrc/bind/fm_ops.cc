@@ -849,6 +849,9 @@ void bind_fm(py::module_& m) {
   m.def("set_cu_reserve", [](int64_t n) { wh::fm_set_cu_reserve((int)n); },
         "CUs the persistent FM kernels leave free for concurrent collectives");
   m.def("cu_reserve", []() { return (int64_t)wh::fm_cu_reserve(); });
+  m.def("set_fm_bwd_pack", [](bool on) { wh::fm_set_bwd_pack(on); },
+        "FM backward: pack small single-chunk keys, one lane group per key (default on)");
+  m.def("fm_bwd_pack", []() { return wh::fm_bwd_pack(); });
   m.def("fm_backward", &fm_backward);
   m.def("fm_backward_plan", &fm_backward_plan, py::arg("csc_off"), py::arg("csc_row"),
         py::arg("hdr"), py::arg("vc_rows"), py::arg("nrows"), py::arg("vstride"),

@@ -37,7 +37,9 @@ namespace wh {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kFwdBlocks = 2048;  // persistent forward grid: 8192 waves = 32 per CU
+// cap of the persistent forward grid; resident_blocks sizes it to what fits
+// (k_fm_fwd<16>: 116 VGPRs, 4 waves per SIMD = 4 blocks per CU)
+constexpr int kFwdBlocks = 2048;
 
 // Memory-level parallelism decides both FM kernels: every V / xv row is a
 // dependent gather (index load -> header -> row), and 256-byte rows only
@@ -364,7 +366,12 @@ __global__ __launch_bounds__(kThreads) void k_chunk_plan(int64_t nuniq,
 // 31% L2 hit rate and 248 us in rocprof, vs 144 us bucketed. A three-kernel
 // counting sort (block histograms -> bucket-major scan -> scatter); rocPRIM's
 // radix_sort_pairs picks a 10-pass merge sort at this size (124 us).
+// The sort digit is row bucket x 2 + class: within each row window the small
+// chunks (a single-chunk key of at most `small_n` occurrences, the ones
+// k_bwd_v packs SUB to a wave iteration) come first and the rest after, so
+// the packed iterations find their SUB small chunks side by side.
 constexpr int kBuckets = 256;
+constexpr int kDigits = 2 * kBuckets;  // with the class bit (histogram scratch is sized for it)
 constexpr int kBucketBlocks = 128;
 constexpr int kBucketU = 8;  // chunks per thread with loads in flight together
 
@@ -373,12 +380,23 @@ __device__ __forceinline__ int row_bucket(int row, int shift) {
   return b < kBuckets ? b : kBuckets - 1;
 }
 
+// meta.z = n | multi << 8: small means 1 <= n <= small_n and one chunk
+__device__ __forceinline__ bool small_chunk(int z, int small_n) { return z >= 1 && z <= small_n; }
+
+// D == kBuckets: the row bucket alone; D == kDigits: row bucket x 2 + class
+template <int D>
+__device__ __forceinline__ int chunk_digit(int row, int shift, int z, int small_n) {
+  const int b = row_bucket(row, shift);
+  return D == kBuckets ? b : b * 2 + (small_chunk(z, small_n) ? 0 : 1);
+}
+
+template <int D>
 __global__ __launch_bounds__(kThreads) void k_vchunk_hist(const int64_t* __restrict__ nchunk_p,
                                                           const int4* __restrict__ meta,
                                                           const int32_t* __restrict__ csc_row,
-                                                          int shift, int32_t* hist) {
-  __shared__ int32_t h[kBuckets];
-  for (int i = threadIdx.x; i < kBuckets; i += kThreads) h[i] = 0;
+                                                          int shift, int small_n, int32_t* hist) {
+  __shared__ int32_t h[D];
+  for (int i = threadIdx.x; i < D; i += kThreads) h[i] = 0;
   __syncthreads();
   const int64_t n = *nchunk_p;
   const int64_t per = (n + gridDim.x - 1) / gridDim.x;
@@ -386,46 +404,55 @@ __global__ __launch_bounds__(kThreads) void k_vchunk_hist(const int64_t* __restr
   // kBucketU independent meta -> row load chains in flight per thread (one
   // chain at a time left this kernel waiting on ~17 round trips)
   for (int64_t cb = c0 + threadIdx.x; cb < c1; cb += kThreads * kBucketU) {
-    int idx[kBucketU], row[kBucketU];
+    int idx[kBucketU], z[kBucketU], row[kBucketU];
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u) {
       const int64_t c = cb + (int64_t)u * kThreads;
       idx[u] = c < c1 ? meta[c].y : -1;
+      z[u] = D != kBuckets && c < c1 ? meta[c].z : 0;
     }
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u) row[u] = idx[u] >= 0 ? csc_row[idx[u]] : -1;
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u)
-      if (row[u] >= 0) atomicAdd(&h[row_bucket(row[u], shift)], 1);
+      if (row[u] >= 0) atomicAdd(&h[chunk_digit<D>(row[u], shift, z[u], small_n)], 1);
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < kBuckets; i += kThreads) hist[blockIdx.x * kBuckets + i] = h[i];
+  for (int i = threadIdx.x; i < D; i += kThreads) hist[blockIdx.x * D + i] = h[i];
 }
 
-// one block of 1024: hist[block][bucket] -> bucket-major exclusive offsets in
-// place. Four threads per bucket each own a quarter of the blocks, so every
-// load is independent (the serial per-bucket walk took ~15-20 us of load
-// latency); the 256 bucket totals are scanned by the first four waves.
-constexpr int kScanParts = 4;
-constexpr int kScanPer = kBucketBlocks / kScanParts;
+// one block of 1024: hist[block][digit] -> digit-major exclusive offsets in
+// place. 1024 / D threads per digit each own a share of the blocks, so every
+// load is independent (the serial per-digit walk took ~15-20 us of load
+// latency); the D digit totals are scanned by the first D / 64 waves. A
+// thread keeps up to 32 counts in registers; with 64 (D = 512: 1024 threads
+// leave 128 VGPRs each, which 64 counts and their addresses exceed) it reads
+// them again from L2 for the second pass.
+constexpr int kScanThreads = 1024;
 
-__global__ __launch_bounds__(kBuckets * kScanParts) void k_vchunk_scan(int32_t* hist) {
-  __shared__ int32_t part[kScanParts][kBuckets];
-  __shared__ int32_t excl[kBuckets];
-  __shared__ int32_t wtot[kBuckets / 64];
-  const int b = threadIdx.x & (kBuckets - 1), q = threadIdx.x / kBuckets;
-  int32_t v[kScanPer];
-#pragma unroll
-  for (int i = 0; i < kScanPer; ++i) v[i] = hist[(q * kScanPer + i) * kBuckets + b];
+template <int D>
+__global__ __launch_bounds__(kScanThreads) void k_vchunk_scan(int32_t* hist) {
+  constexpr int kParts = kScanThreads / D, kPer = kBucketBlocks / kParts;
+  constexpr int kKeep = kPer <= 32 ? kPer : 32;
+  __shared__ int32_t part[kParts][D];
+  __shared__ int32_t excl[D];
+  __shared__ int32_t wtot[D / 64];
+  const int b = threadIdx.x & (D - 1), q = threadIdx.x / D;
+  int32_t v[kKeep];
   int32_t sum = 0;
 #pragma unroll
-  for (int i = 0; i < kScanPer; ++i) sum += v[i];
+  for (int i0 = 0; i0 < kPer; i0 += kKeep) {
+#pragma unroll
+    for (int i = 0; i < kKeep; ++i) v[i] = hist[(q * kPer + i0 + i) * D + b];
+#pragma unroll
+    for (int i = 0; i < kKeep; ++i) sum += v[i];
+  }
   part[q][b] = sum;
   __syncthreads();
-  if (q == 0) {  // bucket totals -> wave-local inclusive scans
+  if (q == 0) {  // digit totals -> wave-local inclusive scans
     int32_t t = 0;
 #pragma unroll
-    for (int r = 0; r < kScanParts; ++r) t += part[r][b];
+    for (int r = 0; r < kParts; ++r) t += part[r][b];
     const int lane = b & 63;
     int32_t x = t;
 #pragma unroll
@@ -441,20 +468,28 @@ __global__ __launch_bounds__(kBuckets * kScanParts) void k_vchunk_scan(int32_t* 
   for (int w = 0; w < (b >> 6); ++w) base += wtot[w];
   for (int r = 0; r < q; ++r) base += part[r][b];
 #pragma unroll
-  for (int i = 0; i < kScanPer; ++i) {
-    hist[(q * kScanPer + i) * kBuckets + b] = base;
-    base += v[i];
+  for (int i0 = 0; i0 < kPer; i0 += kKeep) {
+    if (kPer > kKeep) {
+#pragma unroll
+      for (int i = 0; i < kKeep; ++i) v[i] = hist[(q * kPer + i0 + i) * D + b];
+    }
+#pragma unroll
+    for (int i = 0; i < kKeep; ++i) {
+      hist[(q * kPer + i0 + i) * D + b] = base;
+      base += v[i];
+    }
   }
 }
 
+template <int D>
 __global__ __launch_bounds__(kThreads) void k_vchunk_scatter(const int64_t* __restrict__ nchunk_p,
                                                              const int4* __restrict__ meta,
                                                              const int32_t* __restrict__ csc_row,
-                                                             int shift,
+                                                             int shift, int small_n,
                                                              const int32_t* __restrict__ hist,
                                                              int4* out) {
-  __shared__ int32_t base[kBuckets];
-  for (int i = threadIdx.x; i < kBuckets; i += kThreads) base[i] = hist[blockIdx.x * kBuckets + i];
+  __shared__ int32_t base[D];
+  for (int i = threadIdx.x; i < D; i += kThreads) base[i] = hist[blockIdx.x * D + i];
   __syncthreads();
   const int64_t n = *nchunk_p;
   const int64_t per = (n + gridDim.x - 1) / gridDim.x;
@@ -471,7 +506,8 @@ __global__ __launch_bounds__(kThreads) void k_vchunk_scatter(const int64_t* __re
     for (int u = 0; u < kBucketU; ++u) row[u] = m[u].y >= 0 ? csc_row[m[u].y] : -1;
 #pragma unroll
     for (int u = 0; u < kBucketU; ++u)
-      if (row[u] >= 0) out[atomicAdd(&base[row_bucket(row[u], shift)], 1)] = m[u];
+      if (row[u] >= 0)
+        out[atomicAdd(&base[chunk_digit<D>(row[u], shift, m[u].z, small_n)], 1)] = m[u];
   }
 }
 
@@ -511,9 +547,16 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scalar(const int64_t* __restri
 }
 
 // V chunks: one wave per chunk, persistent over the (device-counted) list,
-// software-pipelined like the forward: while chunk i's xv rows are gathered,
-// the duals of chunk i+1, the CSC rows of chunk i+2 and the description of
-// chunk i+3 are in flight.
+// software-pipelined like the forward: while item i's xv rows are gathered,
+// the duals of item i+1, the CSC rows of item i+2 and the list entries after
+// them are in flight.
+// Packing (fm_bwd_pack): 70 % of the headline's V chunks belong to keys of at
+// most 4 occurrences and would use a quarter of a wave or less for a whole
+// iteration. A wave therefore takes SUB consecutive list entries: when all
+// of them are small (one chunk, n <= TI) they are ONE item, lane group s
+// owning key s -- the same gather shape, SUB x TI rows in flight -- else the
+// entries are items one by one, as without packing. A packed key's sums
+// follow the one-wave tree, so it gets the same bits either way.
 // FUSED (FmBwdProblem::fuse_v): the V rows are read from fv, the table's slab
 // (vc is null), and a single-chunk key's wave, which holds the key's finished
 // gradient row and its V row, applies the AdaGrad step itself (VG row loaded
@@ -540,7 +583,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
                                                     float* __restrict__ gvc,
                                                     float* __restrict__ part_gw,
                                                     float* __restrict__ part_gv, float* fv,
-                                                    float* fvg, DifactoHP hp) {
+                                                    float* fvg, DifactoHP hp, int pack) {
   using S = Shape<G>;
   constexpr bool kSplit = 64 / G >= 4;  // fused update: one element per lane
   const float* vrows = FUSED ? fv : vc;
@@ -548,26 +591,170 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
   int2* st = stage[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63, gl = lane & (G - 1), sub = lane / G;
   const int64_t nch = *nchunk_p, nw = (int64_t)gridDim.x * (kThreads / 64);
-  const int64_t w0 =
-      __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * kThreads + threadIdx.x) >> 6));
-  auto get_meta = [&](int64_t c) {
-    return c < nch ? meta[c] : make_int4(0, 0, 0, -1);
+  // groups of gs list entries: SUB when packing, else one (a wave's chunks
+  // spread over the list as evenly as the waves' one-at-a-time walk)
+  const bool can_pack = pack != 0 && S::SUB > 1;
+  const int gs = can_pack ? S::SUB : 1;
+  const int64_t ngrp = (nch + gs - 1) / gs;
+  // Blocks b and b + 8 share an XCD (and its L2): the waves of one XCD take
+  // nw / 8 consecutive groups of every round of nw, so a row window's xv rows
+  // are fetched into one L2 instead of all eight.
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int64_t w0 = (gridDim.x & 7) == 0
+                         ? (int64_t)(blockIdx.x & 7) * (nw / 8) + (blockIdx.x >> 3) * (kThreads / 64) + wv
+                         : (int64_t)blockIdx.x * (kThreads / 64) + wv;
+  const int4 kNone = make_int4(0, 0, 0, -1);
+  // group g of the list: lane group `sub` holds entry g * SUB + sub (gs == 1:
+  // every lane holds entry g)
+  // (one unconditional load at a clamped index: the list's buffer is never
+  // empty, and a lane past the end drops what it read)
+  const int64_t e_last = nch > 0 ? nch - 1 : 0;
+  auto get_group = [&](int64_t g) {
+    const int64_t e = g * gs + (can_pack ? sub : 0);
+    const int4 m = meta[e < e_last ? e : e_last];
+    return e < nch ? m : kNone;
   };
-  auto load_rows = [&](const int4& mt, int& r, float& x) {
-    const bool ok = lane < (mt.z & 0xff);
-    r = ok ? csc_row[mt.y + lane] : -1;
-    x = ok ? (csc_val ? csc_val[mt.y + lane] : 1.f) : 0.f;
+  // The item generator: walks this wave's groups (gq = w0, w0 + nw, ...) and
+  // hands out one packed item for a group of SUB small chunks, or the group's
+  // chunks one at a time (entry jq). mg: the group's entries, loaded when the
+  // generator moves to it, an iteration before it is read.
+  int64_t gq = w0;
+  int jq = 0;
+  int4 mg = get_group(gq);
+  // The next item, in two halves. plan_item, at the top of an iteration
+  // (every earlier load has landed there; reading mg behind the gathers
+  // would make the wave wait for them): a single chunk's description in im,
+  // the same in every lane (read from the owning lane group into scalar
+  // registers, like the scalar load of a list walked one entry per wave),
+  // occurrence i in lane i; packed, lane group s keeps its key's embedding
+  // row in vid, occurrence i of that key in lane (s, i). e: the (first)
+  // entry's list index; at: the lane's CSC position, -1 without one. Returns
+  // false past the end of the list. issue_item, behind the gathers: the loads.
+  bool load_mg = false;
+  auto plan_item = [&](int4& im, int& vid, bool& pk, int64_t& e, int& at) {
+    const bool ok = gq < ngrp;
+    pk = can_pack && __ballot(small_chunk(mg.z, S::TI)) == ~0ull;
+    e = gq * gs + jq;
+    load_mg = true;
+    int beg, n, i;
+    if (pk) {
+      vid = mg.w;
+      beg = mg.y;
+      n = mg.z;
+      i = gl;
+    } else {
+      const int src = jq * G;
+      im = make_int4(__builtin_amdgcn_readlane(mg.x, src), __builtin_amdgcn_readlane(mg.y, src),
+                     __builtin_amdgcn_readlane(mg.z, src), __builtin_amdgcn_readlane(mg.w, src));
+      beg = im.y;
+      n = im.z & 0xff;
+      i = lane;
+      ++jq;
+      load_mg = jq >= gs || gq * gs + jq >= nch;
+    }
+    at = i < n ? beg + i : -1;
+    if (load_mg) {
+      gq += nw;
+      jq = 0;
+    }
+    return ok;
   };
-  int64_t c = w0;
-  int4 mc = get_meta(c), mn = get_meta(c + nw), m2 = get_meta(c + 2 * nw),
-       m3 = make_int4(0, 0, 0, -1);
-  int rc, rn, r2 = -1;
+  auto issue_item = [&](int at, int& r, float& x) {
+    r = at >= 0 ? csc_row[at] : -1;
+    x = at >= 0 ? (csc_val ? csc_val[at] : 1.f) : 0.f;
+    if (load_mg) mg = get_group(gq);
+  };
+  int4 mc = kNone, mn = kNone, m2 = kNone;
+  int vic = -1, vin = -1, vi2 = -1;
+  bool pc, pn, p2 = false;
+  int64_t ec, en, e2 = 0;
+  int rc, rn, r2 = -1, at2 = -1;
   float xc, xn, x2 = 0.f;
-  load_rows(mc, rc, xc);
-  float dc = rc >= 0 ? dual[rc] * xc : 0.f;
-  load_rows(mn, rn, xn);
+  bool okc = plan_item(mc, vic, pc, ec, at2);
+  issue_item(at2, rc, xc);
+  float dc = (rc >= 0 ? dual[rc] : 0.f) * xc;
+  bool okn = plan_item(mn, vin, pn, en, at2), ok2 = false;
+  issue_item(at2, rn, xn);
   float dn = 0.f;
-  for (; c < nch; c += nw) {
+  // the next stages' loads, issued behind the current item's gathers. dn is
+  // the dual alone: its product with x is taken when the pipeline rotates
+  // (taken here, beside the load, it made the wave wait for the gathers
+  // before it issued the loads that follow)
+  auto prefetch = [&]() {
+    dn = rn >= 0 ? dual[rn] : 0.f;
+    issue_item(at2, r2, x2);
+  };
+  while (okc) {
+    ok2 = plan_item(m2, vi2, p2, e2, at2);
+    if (pc) {
+      // Packed: lane group `sub` owns the small key of entry ec + sub. Its
+      // <= TI pairs (lanes gl < n of the group) are staged as the group's
+      // instructions t = 0.., so instruction t gathers row t of all SUB keys.
+      if (gl < S::TI) st[sub * S::NI + gl] = make_int2(rc, __float_as_int(dc));
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      float4 a[S::TI];
+      float du[S::TI];
+#pragma unroll
+      for (int t = 0; t < S::TI; ++t) {
+        const int2 e = st[sub * S::NI + t];
+        du[t] = __int_as_float(e.y);
+        const float* src = e.x >= 0 ? xv + (uint32_t)e.x * (uint32_t)S::VS : kZeroRow;
+        a[t] = reinterpret_cast<const float4*>(src)[gl];
+      }
+      const uint32_t vat = (uint32_t)vic * (uint32_t)S::VS;
+      float4 v = reinterpret_cast<const float4*>(vrows + vat)[gl];
+      float4 vg = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (FUSED) vg = reinterpret_cast<const float4*>(fvg + vat)[gl];
+      const int key = meta[ec + sub].x;  // (read again, not carried: only the gw store needs it)
+      prefetch();
+      // The same bits as the one-wave-per-chunk path below gives this key:
+      // there occurrence i is accumulated by sub-group i % SUB (in order of
+      // i), the sub-groups are summed by the xor butterfly, and the
+      // sub-groups without an occurrence add +0 at every level they join.
+      constexpr int W = S::SUB < S::TI ? S::SUB : S::TI;
+      float4 q[W];
+#pragma unroll
+      for (int j = 0; j < W; ++j) q[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int t = 0; t < S::TI; ++t) {
+        float4& p = q[t % S::SUB];
+        p.x += du[t] * a[t].x; p.y += du[t] * a[t].y;
+        p.z += du[t] * a[t].z; p.w += du[t] * a[t].w;
+      }
+#pragma unroll
+      for (int o = 1; o < W; o <<= 1) {
+#pragma unroll
+        for (int j = 0; j + o < W; j += 2 * o) {
+          q[j].x += q[j + o].x; q[j].y += q[j + o].y;
+          q[j].z += q[j + o].z; q[j].w += q[j + o].w;
+        }
+      }
+      float4 acc = q[0];
+#pragma unroll
+      for (int o = W; o < S::SUB; o <<= 1) {
+        acc.x += 0.f; acc.y += 0.f; acc.z += 0.f; acc.w += 0.f;
+      }
+      // wave_sum over lanes 0..TI-1 and zeros: (d0 + d2) + (d1 + d3), each
+      // d first + 0 from the upper lanes
+      float gw = dc + 0.f, xx = dc * xc + 0.f;
+#pragma unroll
+      for (int o = S::TI / 2; o > 0; o >>= 1) {
+        gw += __shfl_xor(gw, o, 64);
+        xx += __shfl_xor(xx, o, 64);
+      }
+      const float xxp = __shfl(xx, lane & ~(G - 1), 64);
+      if (gl == 0) gw_out[key] = gw;
+      acc.x -= xxp * v.x; acc.y -= xxp * v.y; acc.z -= xxp * v.z; acc.w -= xxp * v.w;
+      if (FUSED) {
+        kvd::adagrad4(v, vg, acc, hp);
+        reinterpret_cast<float4*>(fv + vat)[gl] = v;
+        reinterpret_cast<float4*>(fvg + vat)[gl] = vg;
+      } else {
+        *reinterpret_cast<float4*>(gvc + (int64_t)vic * vstride + gl * 4) = acc;
+      }
+    } else {
     const int n = mc.z & 0xff;
     const bool multi = (mc.z >> 8) != 0;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -592,10 +779,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
           if (kSplit) vg.x = fvg[(uint32_t)mc.w * (uint32_t)S::VS + gl * 4 + (sub & 3)];
           else vg = reinterpret_cast<const float4*>(fvg + (uint32_t)mc.w * (uint32_t)S::VS)[gl];
         }
-        // prefetch the next stages behind the gathers
-        dn = rn >= 0 ? dual[rn] * xn : 0.f;
-        load_rows(m2, r2, x2);
-        m3 = get_meta(c + 3 * nw);
+        prefetch();
       }
 #pragma unroll
       for (int t = 0; t < TB; ++t) {
@@ -614,11 +798,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
         batch(std::integral_constant<int, S::TI>(), t0);
       }
     }
-    if (n == 0) {  // (chunks are never empty; keep the pipeline consistent anyway)
-      dn = rn >= 0 ? dual[rn] * xn : 0.f;
-      load_rows(m2, r2, x2);
-      m3 = get_meta(c + 3 * nw);
-    }
+    if (n == 0) prefetch();  // (chunks are never empty; keep the pipeline consistent anyway)
     const float gw = wave_sum(dc);
     const float xxp = wave_sum(dc * xc);
 #pragma unroll
@@ -628,7 +808,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
     }
     if (lane == 0) {
       if (!multi) gw_out[mc.x] = gw;
-      else if (part_gw) part_gw[c] = gw;
+      else if (part_gw) part_gw[ec] = gw;
       else atomicAdd(gw_out + mc.x, gw);
     }
     acc.x -= xxp * v.x; acc.y -= xxp * v.y; acc.z -= xxp * v.z; acc.w -= xxp * v.w;
@@ -653,7 +833,7 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
     } else if (!multi || part_gv) {
       // single chunk: the row itself; deterministic mode: this chunk's
       // partial row (the list is key-major, unbucketed), summed in order later
-      float* dst = multi ? part_gv + c * (int64_t)vstride : gvc + (int64_t)mc.w * vstride;
+      float* dst = multi ? part_gv + ec * (int64_t)vstride : gvc + (int64_t)mc.w * vstride;
       if (sub == 0) *reinterpret_cast<float4*>(dst + gl * 4) = acc;
     } else {
       // every sub-group holds the whole row after the butterfly: lane l adds
@@ -672,10 +852,10 @@ __global__ __launch_bounds__(kThreads) void k_bwd_v(const int64_t* __restrict__ 
         if (d < S::VS) atomicAdd(gv + d, a);
       }
     }
+    }
     // rotate the pipeline
-    mc = mn; rc = rn; xc = xn; dc = dn;
-    mn = m2; rn = r2; xn = x2;
-    m2 = m3;
+    mc = mn; vic = vin; pc = pn; okc = okn; ec = en; rc = rn; xc = xn; dc = dn * xn;
+    mn = m2; vin = vi2; pn = p2; okn = ok2; en = e2; rn = r2; xn = x2;
   }
 }
 
@@ -792,6 +972,23 @@ static int g_cu_reserve = 0;
 void fm_set_cu_reserve(int cus) { g_cu_reserve = cus < 0 ? 0 : cus; }
 int fm_cu_reserve() { return g_cu_reserve; }
 
+// k_bwd_v packs SUB small single-chunk keys into one wave iteration and the
+// bucket sort puts them side by side (default). WH_FM_BWD_PACK=0 /
+// fm_set_bwd_pack(false): every chunk gets an iteration of its own, in plain
+// row-bucket order -- the same bits for every single-chunk key; kept for A/B
+// and the tests (profiles/fm_bwd_packed.txt: alone the kernel runs level
+// either way, inside the step the packed one is 10 % of the step faster).
+static int g_bwd_pack = -1;
+
+void fm_set_bwd_pack(bool on) { g_bwd_pack = on ? 1 : 0; }
+bool fm_bwd_pack() {
+  if (g_bwd_pack < 0) {
+    const char* e = std::getenv("WH_FM_BWD_PACK");
+    g_bwd_pack = !(e && std::string(e) == "0");
+  }
+  return g_bwd_pack == 1;
+}
+
 static int device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -874,7 +1071,7 @@ int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministi
   l.key_s = carve(cap_s * 4);
   l.beg_s = carve(cap_s * 4);
   l.meta_v = carve(2 * cap_v * 16);
-  l.hist = carve(vstride > 0 ? (int64_t)kBuckets * kBucketBlocks * 4 : 0);
+  l.hist = carve(vstride > 0 ? (int64_t)kDigits * kBucketBlocks * 4 : 0);
   l.det_s = carve(deterministic ? cap_s * 4 : 0);
   l.det_vw = carve(deterministic ? cap_v * 4 : 0);
   l.det_v = carve(deterministic ? cap_v * vstride * 4 : 0);
@@ -918,6 +1115,7 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
   const bool bucket =
       hdr && !p.deterministic && p.nrows * (int64_t)vstride * 4 > ((int64_t)2 << 20);
   int4* meta_sorted = bucket ? meta_v + cap_v : meta_v;
+  const bool pack = fm_bwd_pack();
   if (phase == FmBwdPhase::kAll || phase == FmBwdPhase::kPlan) {
     const ChunkOut out = {key_s, beg_s, meta_v, p.gw, p.gvc, vstride};
     const int64_t ntiles = (nuniq + kPlanTile - 1) / kPlanTile;
@@ -940,11 +1138,20 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
   if (phase != FmBwdPhase::kRun && bucket) {
     int32_t* hist = reinterpret_cast<int32_t*>(base + l.hist);
     const int shift = bucket_shift(std::max<int64_t>(p.nrows, 1));
-    hipLaunchKernelGGL(k_vchunk_hist, dim3(kBucketBlocks), dim3(kThreads), 0, s, off_v + nuniq,
-                       meta_v, p.csc_row, shift, hist);
-    hipLaunchKernelGGL(k_vchunk_scan, dim3(1), dim3(kBuckets * kScanParts), 0, s, hist);
-    hipLaunchKernelGGL(k_vchunk_scatter, dim3(kBucketBlocks), dim3(kThreads), 0, s,
-                       off_v + nuniq, meta_v, p.csc_row, shift, hist, meta_sorted);
+    // the chunks k_bwd_v packs: <= TI occurrences, where a wave holds 2+ keys
+    const int G = vstride / 4;
+    const int small_n = pack && G < 64 ? std::min(G, WH_FM_TI) : 0;
+    auto sort = [&](auto d) {
+      constexpr int D = decltype(d)::value;
+      hipLaunchKernelGGL(k_vchunk_hist<D>, dim3(kBucketBlocks), dim3(kThreads), 0, s,
+                         off_v + nuniq, meta_v, p.csc_row, shift, small_n, hist);
+      hipLaunchKernelGGL(k_vchunk_scan<D>, dim3(1), dim3(kScanThreads), 0, s, hist);
+      hipLaunchKernelGGL(k_vchunk_scatter<D>, dim3(kBucketBlocks), dim3(kThreads), 0, s,
+                         off_v + nuniq, meta_v, p.csc_row, shift, small_n, hist, meta_sorted);
+    };
+    // the class bit only where there are small chunks to put side by side
+    if (small_n > 0) sort(std::integral_constant<int, kDigits>());
+    else sort(std::integral_constant<int, kBuckets>());
   }
   if (phase == FmBwdPhase::kPlan || phase == FmBwdPhase::kBucket) return;
   // chunk counts are device values (off[nuniq]); the scalar kernel launches
@@ -971,7 +1178,7 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
       const int64_t vblk = std::min<int64_t>((cap_v + 3) / 4, resident_blocks(kernel, 2048));
       hipLaunchKernelGGL(kernel, dim3((unsigned)vblk), dim3(kThreads), 0, s, off_v + nuniq,
                          meta_sorted, p.csc_row, p.csc_val, p.dual, p.xv, vc, vstride, p.gw,
-                         p.gvc, pgv_w, pgv, p.fuse_v, p.fuse_vg, p.fuse_hp);
+                         p.gvc, pgv_w, pgv, p.fuse_v, p.fuse_vg, p.fuse_hp, pack ? 1 : 0);
     };
     if (p.fuse_v && p.fuse_v != p.vc) {
       fprintf(stderr, "fm.hip: the fused update needs vc to be the V slab itself\n");

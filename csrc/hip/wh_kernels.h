@@ -326,6 +326,11 @@ void ld_push(const KVTable& t, int64_t ntiles, int T, const int32_t* tlist,
 // CUs the persistent FM grids leave free for concurrent RCCL kernels
 void fm_set_cu_reserve(int cus);
 int fm_cu_reserve();
+// The backward packs SUB = 256 / vstride small single-chunk keys (at most
+// min(vstride / 4, 4) occurrences) into one wave iteration, one lane group
+// per key (default; WH_FM_BWD_PACK=0 or false here: one iteration per chunk)
+void fm_set_bwd_pack(bool on);
+bool fm_bwd_pack();
 void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const float* val,
                 const float* w_or_hdr, const float* vc, int vstride, const float* label, int loss,
                 float* py, float* dual, float* xv, double* met, double* part,
