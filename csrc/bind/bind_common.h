@@ -3,8 +3,9 @@
 // stateless helpers, the process-wide switches (deterministic, timing) and
 // one registration function per op family. State lives with its owner: the
 // localize workspace in localize_ops.cc, every other device workspace in
-// hip_ops.cc (DevWs, declared in ps_ops.h for fm_ops.cc); the KVStore is
-// kv_store.h.
+// hip_ops.cc (DevWs, declared in ps_ops.h for fm_ops.cc and auc_ops.cc), the
+// AUC side stream and host-thread pool in auc_ops.cc, the native layer's own
+// streams and host timers in step_rt.cc; the KVStore is kv_store.h.
 #pragma once
 #include <torch/extension.h>
 #include <pybind11/stl.h>
@@ -204,5 +205,6 @@ void bind_ingest(py::module_& m);
 void bind_localize(py::module_& m);
 void bind_fm(py::module_& m);
 void bind_psx(py::module_& m);
+void bind_auc(py::module_& m);
 
 }  // namespace wh_bind

@@ -10,6 +10,7 @@
 #include "kv_store.h"
 #include "localize_ahead.h"
 #include "ps_ops.h"
+#include "step_rt.h"
 #include "store_guard.h"
 
 #include <c10/hip/HIPCachingAllocator.h>

@@ -6,7 +6,7 @@
 // (localize_ops.cc; the job's interface is localize_job.h).
 #pragma once
 #include "localize_job.h"
-#include "ps_ops.h"
+#include "step_rt.h"
 
 #include <c10/hip/HIPCachingAllocator.h>
 #include <c10/hip/HIPGuard.h>

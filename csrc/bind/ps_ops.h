@@ -1,10 +1,10 @@
 // What one translation unit of the parameter-server family uses from another
-// (hip_ops.cc, fm_ops.cc, psx_ops.cc): declarations only, grouped by the unit
-// that defines them.
+// (hip_ops.cc, fm_ops.cc, psx_ops.cc, auc_ops.cc): declarations only, grouped
+// by the unit that defines them. (The steps' streams and host timers are
+// step_rt.h.)
 #pragma once
 #include "bind_common.h"
 
-#include <array>
 #include <map>
 
 namespace wh_bind {
@@ -53,40 +53,10 @@ Tensor ps_qpack(const Tensor& x, const Tensor& desc, int64_t rows, int64_t W, in
                 int64_t seed);
 void ps_qunpack(const Tensor& q, const Tensor& desc, int64_t W, int64_t nb, const Tensor& out);
 
-// ---- the AUC chain
+// ============================================================= auc_ops.cc
+// auc_sum[0] += the minibatch's exact AUC: on the current stream, or (large
+// minibatches) on the AUC side stream or host threads, joined by auc_join
 void auc_acc(const Tensor& py, const Tensor& label, const Tensor& auc_sum);
 void auc_acc_side(const Tensor& py, const Tensor& label, const Tensor& auc_sum);
-
-// ---- the native layer's own streams, one per device and role
-enum OwnStream { kStreamLinearLs, kStreamPsxLs, kStreamPsxCs, kStreamPsxXs, kStreamAuc, kOwnStreams };
-hipStream_t own_stream(int dev, int role);
-
-// ---- WH_TIMING=step: host time per section of a native step
-struct HostSplit {
-  const char* name;
-  double us[10] = {};
-  int64_t calls = 0;
-  bool abs = false;
-  std::vector<std::array<int64_t, 11>> marks;
-  explicit HostSplit(const char* n);
-  ~HostSplit();
-  HostSplit(const HostSplit&) = delete;
-  HostSplit& operator=(const HostSplit&) = delete;
-  void print() const;
-};
-class HostTimer {
- public:
-  explicit HostTimer(HostSplit* h);
-  void mark(int i);
-  ~HostTimer();
-
- private:
-  HostSplit* h_;
-  std::chrono::steady_clock::time_point t_;
-  bool rec_ = false;
-  std::array<int64_t, 11> m_{};
-};
-// a split when WH_TIMING asks for one, else nullptr
-HostSplit* host_split(const char* name);
 
 }  // namespace wh_bind

@@ -33,6 +33,7 @@
 #include "localize_job.h"
 #include "ps_ops.h"
 #include "rccl_comm.h"
+#include "step_rt.h"
 #include "store_guard.h"
 
 #include <c10/hip/HIPCachingAllocator.h>

@@ -3,7 +3,7 @@
 // ranges over OpenMP threads).
 //   spmv   : y = X x           G lanes stride over one CSR row, group reduce
 //   spmv_t : y = X^T p         runs on the linear backward's chunked
-//                              segmented sums (fm.hip; csrc/bind/hip_ops.cc
+//                              segmented sums (fm.hip; csrc/bind/fm_ops.cc
 //                              spmv_t): skew-robust over power-law columns
 // Columns are the dense local ids produced by `localize`, so the same
 // kernels serve L-BFGS (whole split resident in HBM) and minibatch apps.

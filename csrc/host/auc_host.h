@@ -8,9 +8,10 @@
 // convention (learn/base/binary_class_evaluation.h:17-38, whose std::sort
 // leaves the order of equal scores unspecified; the index fixes it here).
 //
-// Header-only: the device layer (csrc/bind/hip_ops.cc, which can run it on
+// Header-only: the device layer (csrc/bind/auc_ops.cc, which can run it on
 // host threads from a pinned copy instead of the device chain:
-// WH_AUC_HOST_THREADS) and the host runtime's binding (the CPU test against
+// WH_AUC_HOST_THREADS, with csrc/host/auc_jobs.h as the job ledger) and the
+// host runtime's binding (the CPU test against
 // the plain-PyTorch oracle) compile the same code.
 #pragma once
 

@@ -9,16 +9,21 @@
 // control-plane transport (Van) with live reader threads; and the pure
 // arithmetic of the exact AUC, of the two store guards' plans, of the
 // localize job's bookkeeping and of the GBDT histogram task lists and level
-// tables.
+// tables; and the host-thread AUC's job ledger under test workers.
+#include <algorithm>
 #include <atomic>
+#include <chrono>
+#include <condition_variable>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 #include <random>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "host/auc_host.h"
+#include "host/auc_jobs.h"
 #include "host/common.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
@@ -306,6 +311,135 @@ static void test_auc() {
       }
       EXPECT(wh::auc_exact_host(p.data(), l.data(), n, ws) == want);
     }
+  }
+}
+
+// The host-thread AUC's job ledger (host/auc_jobs.h) as the binding drives
+// it, with the test in the binding's place: it owns what ev and buf point to,
+// gives fresh jobs their cap, and its workers finish jobs with results it
+// supplies. Workers end on sentinel jobs (the product's never end).
+static void test_auc_jobs() {
+  using namespace std::chrono_literals;
+  // Submission-order fold: 40 jobs over two targets, three workers. Each
+  // group of three jobs finishes in reverse (job i waits at the gate until
+  // the later jobs of its group have finished), so every fold happens with
+  // jobs finished out of order; the sums must still be the left-to-right ones.
+  {
+    const int N = 40;
+    const double vals[4] = {1e16, 1.0, -1e16, 3.0};
+    struct Item { double r; int target; };
+    std::vector<Item> items(N);
+    for (int i = 0; i < N; ++i) items[i] = {vals[i / 2 % 4], i % 2};  // each target: vals, 5 times
+    int tgt[2], stop;  // (their addresses name the targets)
+    double fwd[2] = {0, 0}, rev[2] = {0, 0};
+    for (int i = 0; i < N; ++i) fwd[items[i].target] += items[i].r;
+    for (int i = N - 1; i >= 0; --i) rev[items[i].target] += items[i].r;
+    EXPECT(fwd[0] == 19 && rev[0] == 20 && fwd[1] == 19 && rev[1] == 20);  // order shows
+
+    wh::AucJobs jobs(64);
+    std::mutex gm;
+    std::condition_variable gcv;
+    std::vector<char> fin(N, 0);
+    std::vector<int> order;
+    auto worker = [&] {
+      for (;;) {
+        wh::AucJob* j = jobs.take();
+        if (j->target == &stop) {
+          jobs.finish(j, 0);
+          return;
+        }
+        const int i = (int)(static_cast<Item*>(j->ev) - items.data());
+        {
+          std::unique_lock<std::mutex> lk(gm);
+          gcv.wait(lk, [&] {
+            for (int k = i + 1; k < std::min(N, i / 3 * 3 + 3); ++k)
+              if (!fin[k]) return false;
+            return true;
+          });
+        }
+        jobs.finish(j, items[i].r);
+        std::lock_guard<std::mutex> lk(gm);
+        fin[i] = 1;
+        order.push_back(i);
+        gcv.notify_all();
+      }
+    };
+    std::vector<std::thread> th;
+    for (int w = 0; w < 3; ++w) th.emplace_back(worker);
+    for (int i = 0; i < N + 3; ++i) {
+      wh::AucJob* j = jobs.acquire(1);
+      EXPECT(j->n == 1 && !j->done);
+      if (!j->cap) j->cap = 1;
+      j->ev = i < N ? &items[i] : nullptr;
+      jobs.submit(j, i < N ? (const void*)&tgt[items[i].target] : &stop);
+    }
+    for (int t = 0; t < 2; ++t) {  // (blocks until the target's last job folds)
+      double s = -1;
+      EXPECT(jobs.join(&tgt[t], &s) && s == fwd[t]);
+    }
+    for (auto& t : th) t.join();
+    EXPECT((int)order.size() == N && order[0] == 2 && order[1] == 1 && order[2] == 0);
+  }
+  // Back-pressure, recycling and join, single-stepped: no workers, the test
+  // takes and finishes the jobs itself
+  {
+    wh::AucJobs jobs(4);
+    int t, u, never;
+    wh::AucJob* j[4];
+    for (int k = 0; k < 4; ++k) {
+      j[k] = jobs.acquire(10);
+      EXPECT(j[k]->cap == 0);  // fresh
+      j[k]->cap = 100 * (k + 1);
+      jobs.submit(j[k], &t);
+    }
+    for (int k = 0; k < 4; ++k) EXPECT(jobs.take() == j[k]);  // in submission order
+    std::atomic<bool> got{false};
+    wh::AucJob* fifth = nullptr;
+    std::thread sub([&] {
+      fifth = jobs.acquire(150);
+      got = true;
+    });
+    std::this_thread::sleep_for(50ms);
+    EXPECT(!got);  // four unfolded jobs: the fifth acquire waits
+    jobs.finish(j[1], 2.0);
+    std::this_thread::sleep_for(50ms);
+    EXPECT(!got);  // job 2 is finished but not at the head of the line: no space
+    jobs.finish(j[0], 1.0);  // folds jobs 1 and 2
+    sub.join();
+    EXPECT(got && fifth == j[1]);  // free: {100, 200}; the first with cap >= 150
+    jobs.finish(j[3], 4.0);
+    jobs.finish(j[2], 3.0);  // free: caps {100, 300, 400}
+    wh::AucJob* big = jobs.acquire(1000);  // larger than every free job: a fresh one
+    EXPECT(big->cap == 0 && big->n == 1000);
+    for (int k = 0; k < 4; ++k) EXPECT(big != j[k]);
+    EXPECT(jobs.acquire(250) == j[2]);  // skips the smaller free job
+    EXPECT(jobs.acquire(1) == j[0]);
+    for (int k = 0; k < 4; ++k) EXPECT(j[k]->cap == 100 * (k + 1));  // none regrown
+
+    double s = -1;
+    EXPECT(!jobs.join(&never, &s) && s == -1);  // never submitted: at once
+    EXPECT(jobs.join(&t, &s) && s == 10.0);     // all folded
+    EXPECT(!jobs.join(&t, &s));                 // and forgotten
+    // unfolded jobs: join waits for the last fold (submitted: fifth, big, j[2])
+    big->cap = 1000;
+    jobs.submit(fifth, &u);
+    jobs.submit(big, &u);
+    jobs.submit(j[2], &u);
+    std::atomic<bool> joined{false};
+    double su = -1;
+    bool had = false;
+    std::thread joiner([&] {
+      had = jobs.join(&u, &su);
+      joined = true;
+    });
+    EXPECT(jobs.take() == fifth && jobs.take() == big && jobs.take() == j[2]);
+    jobs.finish(j[2], 4.0);
+    jobs.finish(fifth, 1.0);  // folds only itself: big is unfinished
+    std::this_thread::sleep_for(50ms);
+    EXPECT(!joined);
+    jobs.finish(big, 2.0);
+    joiner.join();
+    EXPECT(had && su == 7.0);
   }
 }
 
@@ -703,6 +837,7 @@ static void test_psx_plan() {
 
 int main() {
   test_auc();
+  test_auc_jobs();
   test_store_guard_plan();
   test_linear_guard_plan();
   test_localize_plan();

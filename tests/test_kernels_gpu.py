@@ -981,6 +981,54 @@ def _auc_side_checks(hip):
     assert abs(float(a) - ta) < 1e-9
 
 
+_AUC_EDGE_CASES = []
+
+
+def _auc_edge_cases():
+    """(py, label, exact AUC) at the sizes where auc_acc_side changes path:
+    4096 is the last that runs on the current stream and 4097 the first on the
+    side stream; 24576 is the last the pair kernel takes and 24577 the first
+    bucketed one. Computed once."""
+    if not _AUC_EDGE_CASES:
+        g = torch.Generator().manual_seed(10)
+        for n in (4096, 4097, 24576, 24577):
+            py = torch.round(torch.randn(n, generator=g) * 64) / 64  # with ties
+            lab = (torch.rand(n, generator=g) < torch.sigmoid(py)).float()
+            _AUC_EDGE_CASES.append((py, lab, float(ref.auc(py, lab))))
+    return _AUC_EDGE_CASES
+
+
+def test_auc_side_path_boundaries(hip):
+    """auc_acc_side into one sum at the four boundary sizes, on host threads
+    and on the device chain: auc_join leaves the sum of the exact AUCs."""
+    tot = sum(r for _, _, r in _auc_edge_cases())
+    for threads in (2, 0):
+        acc = torch.zeros(1, dtype=torch.float64, device=DEV)
+        hip.auc_host_threads(threads)
+        try:
+            for py, lab, _ in _auc_edge_cases():
+                hip.auc_acc_side(py.to(DEV), lab.to(DEV), acc)
+            hip.auc_join(acc)
+        finally:
+            hip.auc_host_threads(0)
+        assert abs(float(acc) - tot) < 1e-9, (threads, float(acc), tot)
+
+
+def test_auc_host_jobs_survive_switch_off(hip):
+    """Host-thread jobs still pending when the host path is switched off are
+    joined all the same: the sum holds both AUCs."""
+    py, lab, r = _auc_edge_cases()[1]  # 4097 rows: the side stream's path
+    acc = torch.zeros(1, dtype=torch.float64, device=DEV)
+    hip.auc_host_threads(2)
+    try:
+        hip.auc_acc_side(py.to(DEV), lab.to(DEV), acc)
+        hip.auc_acc_side(py.to(DEV), lab.to(DEV), acc)
+    finally:
+        hip.auc_host_threads(0)
+    hip.auc_join(acc)
+    assert abs(float(acc) - 2 * r) < 1e-9, (float(acc), r)
+
+
 @pytest.mark.parametrize("nshard", [1, 8])
 def test_localize_few_distinct_ids_many_partitions(hip, nshard):
     """~2M non-zeros over 2000 power-law ids (the shape of bench_e2e.py's

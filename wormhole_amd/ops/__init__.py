@@ -171,8 +171,6 @@ def auc(py, label):
 
 
 
-
-
 def auc_acc(py, label, auc_sum):
     """auc_sum (float64 [1]) += exact AUC of the minibatch, on the device.
 
