@@ -10,8 +10,9 @@ Two shared objects are produced next to the Python sources:
   launches on the current HIP stream).
 * ``bin/native/{convert,text2crb}`` -- standalone C++ data conversion tools
   (reference learn/tool/), wrapped by ``bin/convert.dmlc`` / ``bin/text2crb.dmlc``.
-* ``bin/native/{host_selftest,gbdt_rank_plan_test}`` -- stand-alone tests of
-  host code (``--sanitize`` / ``--sanitize-rank-plan`` build them under sanitizers).
+* ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test}`` --
+  stand-alone tests of host code (``--sanitize`` / ``--sanitize-rank-plan`` /
+  ``--sanitize-shap-plan`` build them under sanitizers).
 * ``wormhole_amd/_host.so`` -- the native C++ runtime (``csrc/host/*.cc``):
   proto-text config parser, data parsers (libsvm / criteo / adfea / crb),
   CityHash64, LZ4 block codec, RecordIO, workload pool, control-plane
@@ -138,6 +139,11 @@ def gen_ninja():
     lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, RANK_PLAN_TEST_SRC)))
     lines.append("build %s: link_tool %s" % (
         os.path.join(ROOT, "bin", "native", "gbdt_rank_plan_test"), obj))
+    # contribution tables and plan test (header only): bin/native/gbdt_shap_plan_test
+    obj = os.path.join(BUILD, "tool", "gbdt_shap_plan_test.o")
+    lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, SHAP_PLAN_TEST_SRC)))
+    lines.append("build %s: link_tool %s" % (
+        os.path.join(ROOT, "bin", "native", "gbdt_shap_plan_test"), obj))
     lines.append("build %s: link_hip %s" % (os.path.join(PKG, "_hip.so"), " ".join(hip_objs)))
     lines.append("build %s: link_host %s" % (os.path.join(PKG, "_host.so"), " ".join(host_objs)))
     os.makedirs(BUILD, exist_ok=True)
@@ -146,6 +152,7 @@ def gen_ninja():
 
 
 RANK_PLAN_TEST_SRC = "csrc/tests/gbdt_rank_plan_test.cc"
+SHAP_PLAN_TEST_SRC = "csrc/tests/gbdt_shap_plan_test.cc"
 SELFTEST_SRCS = ("csrc/tests/host_selftest.cc", "csrc/host/parsers.cc", "csrc/host/io.cc",
                  "csrc/host/remote_fs.cc", "csrc/host/lz4.cc", "csrc/host/cityhash.cc", "csrc/host/workload_pool.cc",
                  "csrc/host/conf_parser.cc", "csrc/host/van.cc", "csrc/host/json.cc")
@@ -168,18 +175,32 @@ def build_sanitized(kind, jobs=None):
     return exe
 
 
+def _build_plan_test_sanitized(name, src):
+    """A header-only plan test (its own main) under
+    -fsanitize=address,undefined: build/san-<name>/<test>."""
+    out_dir = os.path.join(BUILD, "san-" + name)
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, os.path.splitext(os.path.basename(src))[0])
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fno-omit-frame-pointer",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-I" + os.path.join(ROOT, "csrc"), os.path.join(ROOT, src),
+                    "-o", exe], check=True)
+    return exe
+
+
 def build_rank_plan_sanitized():
     """The ranking task plan test (csrc/host/gbdt_rank_plan.h, its own main)
     under -fsanitize=address,undefined: build/san-rank-plan/gbdt_rank_plan_test.
     The plain build is bin/native/gbdt_rank_plan_test."""
-    out_dir = os.path.join(BUILD, "san-rank-plan")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "gbdt_rank_plan_test")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fno-omit-frame-pointer",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I" + os.path.join(ROOT, "csrc"), os.path.join(ROOT, RANK_PLAN_TEST_SRC),
-                    "-o", exe], check=True)
-    return exe
+    return _build_plan_test_sanitized("rank-plan", RANK_PLAN_TEST_SRC)
+
+
+def build_shap_plan_sanitized():
+    """The contribution tables and plan test (csrc/host/gbdt_shap_plan.h, its
+    own main) under -fsanitize=address,undefined:
+    build/san-shap-plan/gbdt_shap_plan_test. The plain build is
+    bin/native/gbdt_shap_plan_test."""
+    return _build_plan_test_sanitized("shap-plan", SHAP_PLAN_TEST_SRC)
 
 
 def build(jobs=None, clean=False, verbose=False):
@@ -204,7 +225,12 @@ if __name__ == "__main__":
                     help="build the host self-test under a sanitizer instead")
     ap.add_argument("--sanitize-rank-plan", action="store_true",
                     help="build the ranking task plan test under address,undefined instead")
+    ap.add_argument("--sanitize-shap-plan", action="store_true",
+                    help="build the contribution plan test under address,undefined instead")
     a = ap.parse_args()
+    if a.sanitize_shap_plan:
+        print(build_shap_plan_sanitized())
+        sys.exit(0)
     if a.sanitize_rank_plan:
         print(build_rank_plan_sanitized())
         sys.exit(0)

@@ -16,6 +16,7 @@
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
 #include "host/gbdt_rank_plan.h"
+#include "host/gbdt_shap_plan.h"
 
 namespace wh_bind {
 namespace {
@@ -535,6 +536,232 @@ void gbdt_predict_forest_csr(const Tensor& row_off, const Tensor& fid,
                                            optptr<float>(val), n, c, o, s);
              });
 }
+
+// ------------------------------------------------- feature contributions
+// pred_contribs / approx_contribs (host/gbdt_shap_plan.h, gbdt_shap.hip).
+// Pack, plan and the host references need no GPU.
+using TreeInts = std::vector<std::vector<int64_t>>;
+using TreeReals = std::vector<std::vector<double>>;
+
+Tensor int32_tensor(const std::vector<int32_t>& v, std::vector<int64_t> shape) {
+  auto t = torch::empty(shape, torch::kInt32);
+  TORCH_CHECK(t.numel() == (int64_t)v.size());
+  if (!v.empty()) std::memcpy(t.data_ptr(), v.data(), v.size() * 4);
+  return t;
+}
+
+// (path_begin, npath, elem_begin, nelem, class, width) per chunk
+using ShapChunks = std::vector<std::tuple<int64_t, int64_t, int64_t, int64_t, int64_t, int64_t>>;
+
+ShapChunks shap_chunks(const wh::GbdtShapPlan& plan) {
+  ShapChunks out;
+  for (auto& c : plan.chunks)
+    out.emplace_back(c.path_begin, c.npath, c.elem_begin, c.nelem, c.cls, c.width);
+  return out;
+}
+
+// The kernels' tables of the trees' lists and covers, on the host: (used
+// int32 [U], tree_E float64 [T], paths int32 [P, 4], elems int32 [E, 4], ecol
+// int32 [E], chunks, nodes int32 [N, 4], tree_off int32 [T + 1], node_m
+// float32 [N], node_col int32 [N]). ValueError: a malformed tree, a tree
+// without usable covers, a path of more than 63 distinct features.
+py::tuple gbdt_shap_pack(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
+                         TreeInts defl, TreeReals leaf, const TreeReals& cover, int64_t num_class,
+                         int64_t lds_elems) {
+  wh::GbdtForestTrees tr{std::move(feat), std::move(left), std::move(right), std::move(defl),
+                         std::move(cond), std::move(leaf)};
+  const wh::GbdtShapModel m = wh::gbdt_shap_pack(tr, cover, (int)num_class);
+  const wh::GbdtShapPlan plan = wh::gbdt_shap_plan(m, lds_elems);
+  const wh::GbdtShapTable tab = wh::gbdt_shap_table(m, plan);
+  const int64_t N = (int64_t)m.nodes.size();
+  auto nodes = torch::empty({N, 4}, torch::kInt32);
+  if (N) std::memcpy(nodes.data_ptr(), m.nodes.data(), N * sizeof(m.nodes[0]));
+  auto E = torch::empty({m.ntree()}, torch::kFloat64);
+  if (m.ntree()) std::memcpy(E.data_ptr(), m.tree_E.data(), m.ntree() * 8);
+  auto nm = torch::empty({N}, torch::kFloat32);
+  for (int64_t i = 0; i < N; ++i) nm.data_ptr<float>()[i] = (float)m.node_m[i];
+  return py::make_tuple(int32_tensor(m.used, {(int64_t)m.used.size()}), E,
+                        int32_tensor(tab.paths, {(int64_t)tab.paths.size() / 4, 4}),
+                        int32_tensor(tab.elems, {(int64_t)tab.elems.size() / 4, 4}),
+                        int32_tensor(tab.ecol, {(int64_t)tab.ecol.size()}), shap_chunks(plan), nodes,
+                        int32_tensor(m.tree_off, {(int64_t)m.tree_off.size()}), nm,
+                        int32_tensor(m.node_col, {N}));
+}
+
+// (order, chunks) of paths given by length, class and tree
+py::tuple gbdt_shap_plan(const std::vector<int32_t>& path_len, const std::vector<int32_t>& path_class,
+                         const std::vector<int32_t>& path_tree, int64_t lds_elems) {
+  const wh::GbdtShapPlan plan = wh::gbdt_shap_plan(path_len, path_class, path_tree, lds_elems);
+  return py::make_tuple(plan.order, shap_chunks(plan));
+}
+
+// The host references: (phi float64 [K, n, U + 1] in compact columns, the
+// bias last; used int32 [U]); f32: computed in fp32 throughout.
+template <class Rows>
+py::tuple shap_rows_host(wh::GbdtForestTrees tr, const TreeReals& cover, int64_t num_class,
+                         double base, const Rows& rows, int64_t n, bool approx, bool f32) {
+  const wh::GbdtShapModel m = wh::gbdt_shap_pack(tr, cover, (int)num_class);
+  const int64_t U1 = (int64_t)m.used.size() + 1;
+  auto phi = torch::empty({num_class, n, U1}, torch::kFloat64);
+  if (f32) {
+    auto p32 = torch::empty({num_class, n, U1}, torch::kFloat32);
+    wh::gbdt_shap_rows<float>(m, rows, n, base, approx, p32.data_ptr<float>());
+    phi.copy_(p32);
+  } else {
+    wh::gbdt_shap_rows<double>(m, rows, n, base, approx, phi.data_ptr<double>());
+  }
+  return py::make_tuple(phi, int32_tensor(m.used, {U1 - 1}));
+}
+
+py::tuple gbdt_shap_rows(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
+                         TreeInts defl, TreeReals leaf, const TreeReals& cover, int64_t num_class,
+                         double base, const Tensor& X, bool approx, bool f32) {
+  TORCH_CHECK(!X.is_cuda() && X.dim() == 2 && X.scalar_type() == torch::kFloat32 &&
+                  X.is_contiguous(),
+              "gbdt_shap_rows: X must be a contiguous CPU float32 matrix");
+  return shap_rows_host(wh::GbdtForestTrees{std::move(feat), std::move(left), std::move(right),
+                                            std::move(defl), std::move(cond), std::move(leaf)},
+                        cover, num_class, base, wh::ShapDenseRows{X.data_ptr<float>(), X.size(1)},
+                        X.size(0), approx, f32);
+}
+
+py::tuple gbdt_shap_rows_csr(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
+                             TreeInts defl, TreeReals leaf, const TreeReals& cover,
+                             int64_t num_class, double base, const Tensor& row_off,
+                             const Tensor& fid, const c10::optional<Tensor>& val, bool approx,
+                             bool f32) {
+  TORCH_CHECK(!row_off.is_cuda() && row_off.scalar_type() == torch::kInt64 &&
+                  row_off.is_contiguous() && row_off.numel() >= 1 && !fid.is_cuda() &&
+                  fid.scalar_type() == torch::kInt32 && fid.is_contiguous(),
+              "gbdt_shap_rows_csr: row_off int64 [n + 1] and fid int32 on the CPU");
+  const int64_t n = row_off.numel() - 1;
+  const int64_t* off = row_off.data_ptr<int64_t>();
+  TORCH_CHECK(off[0] >= 0 && off[n] <= fid.numel(), "gbdt_shap_rows_csr: row_off leaves fid");
+  for (int64_t r = 0; r < n; ++r)
+    TORCH_CHECK(off[r] <= off[r + 1], "gbdt_shap_rows_csr: row_off must not decrease");
+  const float* v = nullptr;
+  if (present(val)) {
+    TORCH_CHECK(!val->is_cuda() && val->scalar_type() == torch::kFloat32 && val->is_contiguous() &&
+                    val->numel() == fid.numel(),
+                "gbdt_shap_rows_csr: val must be float32 of fid's size");
+    v = val->data_ptr<float>();
+  }
+  return shap_rows_host(wh::GbdtForestTrees{std::move(feat), std::move(left), std::move(right),
+                                            std::move(defl), std::move(cond), std::move(leaf)},
+                        cover, num_class, base,
+                        wh::ShapCsrRows{off, fid.data_ptr<int32_t>(), v}, n, approx, f32);
+}
+
+// out: float32 [K, n, U + 1], contiguous, the bias column set by the caller.
+void shap_out_check(const Tensor& out, int64_t n, int64_t ncol) {
+  CHECK_IN(out, torch::kFloat32);
+  TORCH_CHECK(out.dim() == 3 && out.size(0) >= 1 && out.size(1) == n && out.size(2) == ncol + 1 &&
+                  out.size(2) <= INT32_MAX,
+              "contributions must be [K, n, U + 1]");
+}
+
+// The checks both exact kernels share, then one launch per chunk.
+template <class Launch>
+void shap_run(const Tensor& paths, const Tensor& elems, const Tensor& ecol,
+              const ShapChunks& chunks, int64_t ncol, const Tensor& out, int64_t n,
+              Launch launch) {
+  CHECK_IN(paths, torch::kInt32);
+  CHECK_IN(elems, torch::kInt32);
+  CHECK_IN(ecol, torch::kInt32);
+  TORCH_CHECK(paths.dim() == 2 && paths.size(1) == 4 && elems.dim() == 2 && elems.size(1) == 4 &&
+                  ecol.dim() == 1 && ecol.numel() == elems.size(0) &&
+                  elems.size(0) <= INT32_MAX,
+              "the path table must be paths [P, 4], elems [E, 4], ecol [E]");
+  shap_out_check(out, n, ncol);
+  const int64_t K = out.size(0), U1 = out.size(2);
+  int64_t path = 0, elem = 0;
+  for (auto& [path_begin, npath, elem_begin, nelem, cls, width] : chunks) {
+    TORCH_CHECK(path_begin == path && elem_begin == elem && npath >= 1 && nelem >= npath &&
+                    nelem <= wh::gbdt_shap_lds_elems() && cls >= 0 && cls < K &&
+                    (width == 16 || width == 32 || width == 64),
+                "contribution chunks must be consecutive whole paths that fit the LDS");
+    path += npath, elem += nelem;
+  }
+  TORCH_CHECK(path == paths.size(0) && elem == elems.size(0),
+              "contribution chunks must cover the path table");
+  if (n == 0) return;
+  for (auto& [path_begin, npath, elem_begin, nelem, cls, width] : chunks)
+    launch(wh::ShapChunk{paths.data_ptr(), elems.data_ptr(), ptr<int32_t>(ecol), (int)path_begin,
+                         (int)npath, (int)elem_begin, (int)nelem, (int)width, (int)U1,
+                         ptr<float>(out) + cls * n * U1});
+}
+
+void gbdt_shap(const Tensor& X, const Tensor& paths, const Tensor& elems, const Tensor& ecol,
+               const ShapChunks& chunks, int64_t ncol, int64_t max_feat, const Tensor& out) {
+  CHECK_IN(X, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && max_feat < X.size(1), "forest splits on a feature X does not have");
+  c10::DeviceGuard g(X.device());
+  auto s = cur_stream(X);
+  shap_run(paths, elems, ecol, chunks, ncol, out, X.size(0), [&](const wh::ShapChunk& c) {
+    wh::gbdt_shap(ptr<float>(X), X.size(0), (int)X.size(1), c, s);
+  });
+}
+
+// the CSR arguments the contribution kernels share; returns n
+int64_t shap_csr_check(const Tensor& row_off, const Tensor& fid, const c10::optional<Tensor>& val) {
+  CHECK_IN(row_off, torch::kInt64);
+  CHECK_IN(fid, torch::kInt32);
+  TORCH_CHECK(row_off.numel() >= 1, "row_off must be [n + 1]");
+  if (present(val)) {
+    CHECK_IN((*val), torch::kFloat32);
+    TORCH_CHECK(val->numel() == fid.numel(), "val and fid sizes differ");
+  }
+  return row_off.numel() - 1;
+}
+
+void gbdt_shap_csr(const Tensor& row_off, const Tensor& fid, const c10::optional<Tensor>& val,
+                   const Tensor& paths, const Tensor& elems, const Tensor& ecol,
+                   const ShapChunks& chunks, int64_t ncol, const Tensor& out) {
+  const int64_t n = shap_csr_check(row_off, fid, val);
+  c10::DeviceGuard g(row_off.device());
+  auto s = cur_stream(row_off);
+  shap_run(paths, elems, ecol, chunks, ncol, out, n, [&](const wh::ShapChunk& c) {
+    wh::gbdt_shap_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val), n, c, s);
+  });
+}
+
+wh::SaabasForest saabas_forest(const Tensor& nodes, const Tensor& tree_off, const Tensor& node_m,
+                               const Tensor& node_col, int64_t ncol, const Tensor& out, int64_t n) {
+  CHECK_IN(nodes, torch::kInt32);
+  CHECK_IN(tree_off, torch::kInt32);
+  CHECK_IN(node_m, torch::kFloat32);
+  CHECK_IN(node_col, torch::kInt32);
+  const int64_t T = tree_off.numel() - 1;
+  TORCH_CHECK(nodes.dim() == 2 && nodes.size(1) == 4 && node_m.numel() == nodes.size(0) &&
+                  node_col.numel() == nodes.size(0) && T >= 0 && T <= INT32_MAX,
+              "the forest must be nodes [N, 4], tree_off [T + 1], node_m [N], node_col [N]");
+  shap_out_check(out, n, ncol);
+  return wh::SaabasForest{nodes.data_ptr(), ptr<int32_t>(tree_off), ptr<float>(node_m),
+                          ptr<int32_t>(node_col), (int)T, (int)out.size(0), (int)out.size(2),
+                          ptr<float>(out)};
+}
+
+void gbdt_saabas(const Tensor& X, const Tensor& nodes, const Tensor& tree_off,
+                 const Tensor& node_m, const Tensor& node_col, int64_t ncol, int64_t max_feat,
+                 const Tensor& out) {
+  CHECK_IN(X, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && max_feat < X.size(1), "forest splits on a feature X does not have");
+  c10::DeviceGuard g(X.device());
+  const auto f = saabas_forest(nodes, tree_off, node_m, node_col, ncol, out, X.size(0));
+  wh::gbdt_saabas(ptr<float>(X), X.size(0), (int)X.size(1), f, cur_stream(X));
+}
+
+void gbdt_saabas_csr(const Tensor& row_off, const Tensor& fid, const c10::optional<Tensor>& val,
+                     const Tensor& nodes, const Tensor& tree_off, const Tensor& node_m,
+                     const Tensor& node_col, int64_t ncol, const Tensor& out) {
+  const int64_t n = shap_csr_check(row_off, fid, val);
+  c10::DeviceGuard g(row_off.device());
+  const auto f = saabas_forest(nodes, tree_off, node_m, node_col, ncol, out, n);
+  wh::gbdt_saabas_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val), n, f,
+                      cur_stream(row_off));
+}
+
+int64_t gbdt_shap_max_blocks() { return wh::gbdt_shap_max_blocks(); }
 
 // ----------------------------------------------------- learning to rank
 // The task plan of a matrix's query groups (host/gbdt_rank_plan.h), on the
@@ -1217,6 +1444,35 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_predict_forest_csr", &gbdt_predict_forest_csr, py::arg("row_off"), py::arg("fid"),
         py::arg("val"), py::arg("nodes"), py::arg("tree_off"), py::arg("chunks"), py::arg("out"),
         py::arg("leaf") = false);
+  // feature contributions: pack, plan, capacities and the host references
+  // need no GPU
+  m.def("gbdt_shap_pack", &gbdt_shap_pack, py::arg("feat"), py::arg("cond"), py::arg("left"),
+        py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cover"),
+        py::arg("num_class"), py::arg("lds_elems") = (int64_t)wh::kShapLdsElems);
+  m.def("gbdt_shap_plan", &gbdt_shap_plan, py::arg("path_len"), py::arg("path_class"),
+        py::arg("path_tree"), py::arg("lds_elems"));
+  m.def("gbdt_shap_lds_elems", &wh::gbdt_shap_lds_elems);
+  m.def("gbdt_shap_lds_cols", &wh::gbdt_shap_lds_cols);
+  m.def("gbdt_shap_max_blocks", &gbdt_shap_max_blocks);
+  m.def("gbdt_shap_rows", &gbdt_shap_rows, py::arg("feat"), py::arg("cond"), py::arg("left"),
+        py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cover"),
+        py::arg("num_class"), py::arg("base"), py::arg("X"), py::arg("approx") = false,
+        py::arg("f32") = false);
+  m.def("gbdt_shap_rows_csr", &gbdt_shap_rows_csr, py::arg("feat"), py::arg("cond"),
+        py::arg("left"), py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cover"),
+        py::arg("num_class"), py::arg("base"), py::arg("row_off"), py::arg("fid"), py::arg("val"),
+        py::arg("approx") = false, py::arg("f32") = false);
+  m.def("gbdt_shap", &gbdt_shap, py::arg("X"), py::arg("paths"), py::arg("elems"),
+        py::arg("ecol"), py::arg("chunks"), py::arg("ncol"), py::arg("max_feat"), py::arg("out"));
+  m.def("gbdt_shap_csr", &gbdt_shap_csr, py::arg("row_off"), py::arg("fid"), py::arg("val"),
+        py::arg("paths"), py::arg("elems"), py::arg("ecol"), py::arg("chunks"), py::arg("ncol"),
+        py::arg("out"));
+  m.def("gbdt_saabas", &gbdt_saabas, py::arg("X"), py::arg("nodes"), py::arg("tree_off"),
+        py::arg("node_m"), py::arg("node_col"), py::arg("ncol"), py::arg("max_feat"),
+        py::arg("out"));
+  m.def("gbdt_saabas_csr", &gbdt_saabas_csr, py::arg("row_off"), py::arg("fid"), py::arg("val"),
+        py::arg("nodes"), py::arg("tree_off"), py::arg("node_m"), py::arg("node_col"),
+        py::arg("ncol"), py::arg("out"));
   m.def("gbdt_rank_plan", &gbdt_rank_plan, py::arg("group_off"), py::arg("n"),
         py::arg("lds_rows") = (int64_t)wh::kRankLdsRows);
   m.def("gbdt_rank_lds_rows", &wh::gbdt_rank_lds_rows);

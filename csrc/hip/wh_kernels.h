@@ -678,6 +678,46 @@ void gbdt_predict_forest(const float* X, int64_t n, int f, const ForestChunk& c,
 void gbdt_predict_forest_csr(const int64_t* row_off, const int32_t* fid, const float* val,
                              int64_t n, const ForestChunk& c, const ForestOut& o, hipStream_t s);
 
+// ---------------------------------------------------------- gbdt_shap.hip
+// Per-feature contributions of a packed forest (host/gbdt_shap_plan.h), in
+// compact columns: out rows are [U1] = the model's used features and the
+// bias, which the caller has set (the kernels add to columns < U1 - 1 only).
+// One chunk of the plan per launch: `paths` [P, 4] and `elems` [E, 4] with
+// `ecol` [E] are the whole table in plan order, the chunk is paths
+// [path_begin, path_begin + npath) and their elements [elem_begin, elem_begin
+// + nelem), nelem <= gbdt_shap_lds_elems(), every path of at most width - 1
+// elements (width 16, 32 or 64); out is the [n, U1] slice of the chunk's
+// class. U1 <= gbdt_shap_lds_cols() accumulates in LDS, a wider row in out.
+// Dense rows as gbdt_predict_forest (every feature id < f). Nothing runs for
+// n <= 0 or an empty chunk.
+struct ShapChunk {
+  const void *paths, *elems;
+  const int32_t* ecol;
+  int path_begin, npath, elem_begin, nelem, width, U1;
+  float* out;
+};
+void gbdt_shap(const float* X, int64_t n, int f, const ShapChunk& c, hipStream_t s);
+void gbdt_shap_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
+                   const ShapChunk& c, hipStream_t s);
+// The Saabas attribution: every row walks trees [0, T) of the packed forest
+// `nodes` / tree_off, node_m and node_col beside it ([N] each: the subtree's
+// expected value; the compact column of the node's feature), and adds
+// m(child) - m(node) to out[(t % K), row, node_col]; out is [K, n, U1].
+struct SaabasForest {
+  const void* nodes;
+  const int32_t* tree_off;
+  const float* node_m;
+  const int32_t* node_col;
+  int T, K, U1;
+  float* out;
+};
+void gbdt_saabas(const float* X, int64_t n, int f, const SaabasForest& fo, hipStream_t s);
+void gbdt_saabas_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
+                     const SaabasForest& fo, hipStream_t s);
+// blocks the exact kernels keep resident on the current device (the grid
+// strides over row tiles of 1024 / width rows beyond that)
+int gbdt_shap_max_blocks();
+
 // ---------------------------------------------------------- gbdt_rank.hip
 // Learning to rank over query groups: rows [group_off[q], group_off[q + 1])
 // are group q (int32 [Q + 1] on the device, n rows in all). The three task

@@ -18,7 +18,14 @@ num_feature; for task=pred and task=eval ntree_limit (use the first N
 boosting rounds, N x num_class trees; 0 or more than the model has: all), for
 task=pred pred_margin (write the untransformed margins: n lines, or n x K
 row-major for a multi: objective) and pred_leaf (write n x T row-major leaf
-node ids, numbered as in task=dump; not together with pred_margin).
+node ids, numbered as in task=dump; not together with pred_margin),
+pred_contribs (per-feature contributions in margin space, exact TreeSHAP over
+the trees' stored covers) and approx_contribs (the same by the Saabas
+attribution; implies pred_contribs); neither goes with pred_margin or
+pred_leaf. They write one line per row (per row and class, row-major, for a
+multi: objective): ``j:value`` for every feature j with a non-zero
+contribution, ascending, then ``num_feature:bias``; a line's values sum to the
+row's margin (docs/bsp_apps.md "Contributions").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -83,6 +90,7 @@ def main(argv):
     num_feature = 0
     dsparse = None  # dsparse=1|0: keep the data CSR / dense (default: by width)
     ntree_limit, pred_margin, pred_leaf = 0, False, False
+    pred_contribs, approx_contribs = False, False
     evals = []
     for k, v in parse_args(argv):
         if param.set(k, v):
@@ -127,6 +135,10 @@ def main(argv):
             pred_margin = bool(int(v))
         elif k == "pred_leaf":
             pred_leaf = bool(int(v))
+        elif k == "pred_contribs":
+            pred_contribs = bool(int(v))
+        elif k == "approx_contribs":
+            approx_contribs = bool(int(v))
         elif k in ("dsplit",):
             if v not in ("row", "auto"):
                 raise SystemExit("only dsplit=row is supported")
@@ -140,6 +152,10 @@ def main(argv):
         raise SystemExit("ntree_limit must not be negative")
     if pred_leaf and pred_margin:
         raise SystemExit("pred_leaf=1 and pred_margin=1 exclude each other")
+    pred_contribs = pred_contribs or approx_contribs
+    if pred_contribs and (pred_leaf or pred_margin):
+        raise SystemExit("pred_contribs=1 / approx_contribs=1 and pred_%s=1 exclude each other"
+                         % ("leaf" if pred_leaf else "margin"))
     host = _native.host()
 
     def load(path):
@@ -253,7 +269,10 @@ def main(argv):
             # the untransformed margins, n or n x K row-major; pred_leaf: the
             # n x T row-major node ids (the dump's numbering) of the leaves
             fmt = "%d\n" if pred_leaf else "%g\n"
-            if pred_leaf:
+            if pred_contribs:
+                fmt = "%s\n"
+                pred = _contrib_lines(b, dm, limit, approx_contribs)
+            elif pred_leaf:
                 pred = b.predict_leaf(dm, limit)
             else:
                 margin = b.predict_margin(dm, limit)
@@ -261,7 +280,9 @@ def main(argv):
                     pred = margin if margin.dim() == 1 else margin.t()
                 else:
                     pred = b.obj.pred(margin).float()
-            parts = bsp.comm.allgather_object(pred.cpu().reshape(-1).tolist())
+            if not pred_contribs:
+                pred = pred.cpu().reshape(-1).tolist()
+            parts = bsp.comm.allgather_object(pred)
             if bsp.rank == 0:
                 with open_uri(name_pred, "w") as f:
                     for part in parts:
@@ -335,6 +356,30 @@ def main(argv):
         booster.save(out)
     bsp.finalize()
     return 0
+
+
+# bytes of a row block's compact contributions [K, rows, U + 1] (fp32)
+CONTRIB_BLOCK_BYTES = 256 << 20
+
+
+def _contrib_lines(b, dm, limit, approx):
+    """The pred_contribs lines of a matrix, n x K of them, row-major:
+    ``j:%g`` for the non-zero columns, ascending, then ``num_feature:%g``,
+    the bias. Computed in row blocks whose compact contributions stay under
+    CONTRIB_BLOCK_BYTES."""
+    K, F, lines = b.obj.n_group, b.num_feature, []
+    ntree = min(limit, len(b.trees)) if limit else len(b.trees)
+    U = len({f for t in b.trees[:ntree] for f in t.feat if f >= 0})
+    block = max(1, CONTRIB_BLOCK_BYTES // (4 * K * (U + 1)))
+    for a in range(0, dm.n, block):
+        phi, used = b.predict_contribs(dm, limit, approx=approx, compact=True,
+                                       rows=(a, min(dm.n, a + block)))
+        phi = (phi if K > 1 else phi[None]).transpose(0, 1).cpu().double().numpy()
+        cols = used.tolist()
+        for row in phi.reshape(-1, phi.shape[-1]):
+            toks = ["%d:%g" % (cols[j], row[j]) for j in row[:-1].nonzero()[0]]
+            lines.append(" ".join(toks + ["%d:%g" % (F, row[-1])]))
+    return lines
 
 
 def _booster_state(b):

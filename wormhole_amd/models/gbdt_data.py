@@ -80,6 +80,30 @@ class DMatrix(_QueryGroups):
                                           out=out, leaf=leaf)
         return out
 
+    def predict_contribs(self, shap, approx=False, rows=None):
+        """Contributions of a packed forest (gbdt_tree.py ShapForest) on the
+        GPU, rows [a, b) (default: all): float32 [K, b - a, U + 1] in the
+        forest's compact columns, the bias last. approx: Saabas."""
+        a, b = rows if rows is not None else (0, self.n)
+        X = self.X[a:b]
+        out = shap.new_out(b - a, self.device)
+        if approx:
+            _native.hip().gbdt_saabas(X=X, nodes=shap.nodes, tree_off=shap.tree_off,
+                                      node_m=shap.node_m, node_col=shap.node_col,
+                                      ncol=shap.used.numel(), max_feat=shap.max_feat, out=out)
+        else:
+            _native.hip().gbdt_shap(X=X, paths=shap.paths, elems=shap.elems, ecol=shap.ecol,
+                                    chunks=shap.chunks, ncol=shap.used.numel(),
+                                    max_feat=shap.max_feat, out=out)
+        return out
+
+    def predict_contribs_host(self, model, approx=False, rows=None):
+        """The same on a CPU matrix by the host reference: (float64
+        [K, b - a, U + 1], used). model: the trees' lists, covers, num_class
+        and base margin as gbdt_shap_rows names them."""
+        a, b = rows if rows is not None else (0, self.n)
+        return _native.hip().gbdt_shap_rows(X=self.X[a:b].contiguous(), approx=approx, **model)
+
 
 class CSRMatrix(_QueryGroups):
     """A rank's rows kept sparse (libsvm data with a wide feature space:
@@ -127,6 +151,29 @@ class CSRMatrix(_QueryGroups):
                                               nodes=forest.nodes, tree_off=forest.tree_off,
                                               chunks=forest.chunks, out=out, leaf=leaf)
         return out
+
+    def predict_contribs(self, shap, approx=False, rows=None):
+        """As DMatrix.predict_contribs, an absent feature standing for NaN."""
+        a, b = rows if rows is not None else (0, self.n)
+        row_off = self.row_off[a:b + 1]  # (offsets stay absolute: fid and val are whole)
+        out = shap.new_out(b - a, self.device)
+        if approx:
+            _native.hip().gbdt_saabas_csr(row_off=row_off, fid=self.fid, val=self.val,
+                                          nodes=shap.nodes, tree_off=shap.tree_off,
+                                          node_m=shap.node_m, node_col=shap.node_col,
+                                          ncol=shap.used.numel(), out=out)
+        else:
+            _native.hip().gbdt_shap_csr(row_off=row_off, fid=self.fid, val=self.val,
+                                        paths=shap.paths, elems=shap.elems, ecol=shap.ecol,
+                                        chunks=shap.chunks, ncol=shap.used.numel(), out=out)
+        return out
+
+    def predict_contribs_host(self, model, approx=False, rows=None):
+        """As DMatrix.predict_contribs_host, over the CSR rows themselves."""
+        a, b = rows if rows is not None else (0, self.n)
+        return _native.hip().gbdt_shap_rows_csr(row_off=self.row_off[a:b + 1].contiguous(),
+                                                fid=self.fid, val=self.val, approx=approx,
+                                                **model)
 
     def dense_cpu(self):
         """(CPU reference path only: small matrices)"""

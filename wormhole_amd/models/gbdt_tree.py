@@ -211,6 +211,40 @@ class Forest:
         self.nodes, self.tree_off = nodes.to(device), tree_off.to(device)
 
 
+class ShapForest:
+    """Trees packed for the contribution kernels (csrc/host/gbdt_shap_plan.h,
+    csrc/hip/gbdt_shap.hip): the merged root-to-leaf paths in plan order with
+    their chunks (exact TreeSHAP), the forest with every node's expected
+    value and compact column beside it (Saabas), ``used`` (the distinct split
+    features, ascending: the compact columns) and ``bias`` (float64 [K]: the
+    base margin plus the expected values of the class's trees). Packing
+    raises ValueError for a tree without usable cover statistics and for a
+    path of more than 63 distinct features."""
+
+    def __init__(self, trees, K, base_margin, device):
+        hip = _native.hip()
+        kw = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
+                  left=[t.left for t in trees], right=[t.right for t in trees],
+                  defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                  cover=[t.cover for t in trees])
+        (used, tree_E, paths, elems, ecol, self.chunks, nodes, tree_off, node_m,
+         node_col) = hip.gbdt_shap_pack(num_class=K, **kw)
+        self.ntree, self.K = len(trees), K
+        self.used = used
+        self.max_feat = int(used[-1]) if used.numel() else -1
+        self.bias = torch.tensor([base_margin + float(tree_E[k::K].sum()) for k in range(K)],
+                                 dtype=torch.float64)
+        self.paths, self.elems, self.ecol = paths.to(device), elems.to(device), ecol.to(device)
+        self.nodes, self.tree_off = nodes.to(device), tree_off.to(device)
+        self.node_m, self.node_col = node_m.to(device), node_col.to(device)
+
+    def new_out(self, n, device):
+        """float32 [K, n, U + 1]: zeros, the bias in the last column."""
+        out = torch.zeros((self.K, n, self.used.numel() + 1), dtype=torch.float32, device=device)
+        out[:, :, -1] = self.bias.to(torch.float32).to(device)[:, None]
+        return out
+
+
 # ---------------------------------------------------------------- booster
 class Booster:
     MAGIC = b"WHGB"
@@ -271,6 +305,54 @@ class Booster:
         cols = [t.leaf_index(X).to(torch.int32) for t in self.trees[:ntree]]
         out = torch.stack(cols, 1) if cols else torch.empty((dm.n, 0), dtype=torch.int32)
         return out.to(dm.device)
+
+    def shap_forest(self, device, ntree=0):
+        """The first ``ntree`` trees (0: all) packed for the contribution
+        kernels on ``device``; kept as ``forest`` keeps its table."""
+        ntree = self._ntree(ntree)
+        key = (torch.device(device), len(self.trees), ntree)
+        if self.__dict__.get("_shap_key") != key:
+            self._shap = ShapForest(self.trees[:ntree], self.obj.n_group, self.base_margin, device)
+            self._shap_key = key
+        return self._shap
+
+    def predict_contribs(self, dm, ntree_limit=0, approx=False, compact=False, rows=None):
+        """Per-feature contributions in margin space (docs/bsp_apps.md
+        "Contributions"): [n, F + 1], or [K, n, F + 1] for K classes; column
+        j < F is the sum over the (class's) trees of feature j's Shapley
+        value in the tree's cover-weighted game (approx: the Saabas
+        attribution along the row's walk), column F the bias; a row sums to
+        its predict_margin. F is the model's num_feature (or the matrix's
+        width, if larger). compact: (phi [.., U + 1], used) over the U
+        features the trees split on (``used`` int64, ascending) and the bias.
+        rows = (a, b): only rows [a, b). A GPU matrix goes through the HIP
+        kernels (float32); a CPU matrix through the host reference (float64).
+        ValueError: a tree without usable cover statistics; on the GPU, a
+        path of more than 63 distinct features."""
+        K = self.obj.n_group
+        ntree = self._ntree(ntree_limit)
+        a, b = rows if rows is not None else (0, dm.n)
+        if not 0 <= a <= b <= dm.n:
+            raise ValueError("rows must be a range within the matrix")
+        if torch.device(dm.device).type == "cuda":
+            sf = self.shap_forest(dm.device, ntree)
+            phi, used = dm.predict_contribs(sf, approx=approx, rows=(a, b)), sf.used
+        else:
+            trees = self.trees[:ntree]
+            model = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
+                         left=[t.left for t in trees], right=[t.right for t in trees],
+                         defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                         cover=[t.cover for t in trees], num_class=K, base=self.base_margin)
+            phi, used = dm.predict_contribs_host(model, approx=approx, rows=(a, b))
+        used = used.long()
+        if not compact:
+            F = max(self.num_feature, dm.ncol, int(used[-1]) + 1 if used.numel() else 0)
+            full = torch.zeros(phi.shape[:2] + (F + 1,), dtype=phi.dtype, device=phi.device)
+            full[:, :, used.to(phi.device)] = phi[:, :, :-1]
+            full[:, :, F] = phi[:, :, -1]
+            phi = full
+        phi = phi[0] if K == 1 else phi
+        return (phi, used) if compact else phi
 
     def save(self, path):
         p = self.param
