@@ -10,9 +10,10 @@ Two shared objects are produced next to the Python sources:
   launches on the current HIP stream).
 * ``bin/native/{convert,text2crb}`` -- standalone C++ data conversion tools
   (reference learn/tool/), wrapped by ``bin/convert.dmlc`` / ``bin/text2crb.dmlc``.
-* ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test}`` --
-  stand-alone tests of host code (``--sanitize`` / ``--sanitize-rank-plan`` /
-  ``--sanitize-shap-plan`` build them under sanitizers).
+* ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test,
+  gbdt_shap_inter_test}`` -- stand-alone tests of host code (``--sanitize`` /
+  ``--sanitize-rank-plan`` / ``--sanitize-shap-plan`` / ``--sanitize-shap-inter``
+  build them under sanitizers).
 * ``wormhole_amd/_host.so`` -- the native C++ runtime (``csrc/host/*.cc``):
   proto-text config parser, data parsers (libsvm / criteo / adfea / crb),
   CityHash64, LZ4 block codec, RecordIO, workload pool, control-plane
@@ -144,6 +145,11 @@ def gen_ninja():
     lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, SHAP_PLAN_TEST_SRC)))
     lines.append("build %s: link_tool %s" % (
         os.path.join(ROOT, "bin", "native", "gbdt_shap_plan_test"), obj))
+    # interaction references test (header only): bin/native/gbdt_shap_inter_test
+    obj = os.path.join(BUILD, "tool", "gbdt_shap_inter_test.o")
+    lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, SHAP_INTER_TEST_SRC)))
+    lines.append("build %s: link_tool %s" % (
+        os.path.join(ROOT, "bin", "native", "gbdt_shap_inter_test"), obj))
     lines.append("build %s: link_hip %s" % (os.path.join(PKG, "_hip.so"), " ".join(hip_objs)))
     lines.append("build %s: link_host %s" % (os.path.join(PKG, "_host.so"), " ".join(host_objs)))
     os.makedirs(BUILD, exist_ok=True)
@@ -153,6 +159,7 @@ def gen_ninja():
 
 RANK_PLAN_TEST_SRC = "csrc/tests/gbdt_rank_plan_test.cc"
 SHAP_PLAN_TEST_SRC = "csrc/tests/gbdt_shap_plan_test.cc"
+SHAP_INTER_TEST_SRC = "csrc/tests/gbdt_shap_inter_test.cc"
 SELFTEST_SRCS = ("csrc/tests/host_selftest.cc", "csrc/host/parsers.cc", "csrc/host/io.cc",
                  "csrc/host/remote_fs.cc", "csrc/host/lz4.cc", "csrc/host/cityhash.cc", "csrc/host/workload_pool.cc",
                  "csrc/host/conf_parser.cc", "csrc/host/van.cc", "csrc/host/json.cc")
@@ -203,6 +210,14 @@ def build_shap_plan_sanitized():
     return _build_plan_test_sanitized("shap-plan", SHAP_PLAN_TEST_SRC)
 
 
+def build_shap_inter_sanitized():
+    """The interaction references test (csrc/host/gbdt_shap_plan.h, its own
+    main) under -fsanitize=address,undefined:
+    build/san-shap-inter/gbdt_shap_inter_test. The plain build is
+    bin/native/gbdt_shap_inter_test."""
+    return _build_plan_test_sanitized("shap-inter", SHAP_INTER_TEST_SRC)
+
+
 def build(jobs=None, clean=False, verbose=False):
     if clean and os.path.isdir(BUILD):
         shutil.rmtree(BUILD)
@@ -227,7 +242,12 @@ if __name__ == "__main__":
                     help="build the ranking task plan test under address,undefined instead")
     ap.add_argument("--sanitize-shap-plan", action="store_true",
                     help="build the contribution plan test under address,undefined instead")
+    ap.add_argument("--sanitize-shap-inter", action="store_true",
+                    help="build the interaction references test under address,undefined instead")
     a = ap.parse_args()
+    if a.sanitize_shap_inter:
+        print(build_shap_inter_sanitized())
+        sys.exit(0)
     if a.sanitize_shap_plan:
         print(build_shap_plan_sanitized())
         sys.exit(0)

@@ -625,31 +625,80 @@ py::tuple gbdt_shap_rows(TreeInts feat, TreeReals cond, TreeInts left, TreeInts 
                         X.size(0), approx, f32);
 }
 
+// the CSR rows of a host reference, checked: (rows, n)
+std::pair<wh::ShapCsrRows, int64_t> shap_host_csr(const char* who, const Tensor& row_off,
+                                                  const Tensor& fid,
+                                                  const c10::optional<Tensor>& val) {
+  TORCH_CHECK(!row_off.is_cuda() && row_off.scalar_type() == torch::kInt64 &&
+                  row_off.is_contiguous() && row_off.numel() >= 1 && !fid.is_cuda() &&
+                  fid.scalar_type() == torch::kInt32 && fid.is_contiguous(),
+              who, ": row_off int64 [n + 1] and fid int32 on the CPU");
+  const int64_t n = row_off.numel() - 1;
+  const int64_t* off = row_off.data_ptr<int64_t>();
+  TORCH_CHECK(off[0] >= 0 && off[n] <= fid.numel(), who, ": row_off leaves fid");
+  for (int64_t r = 0; r < n; ++r)
+    TORCH_CHECK(off[r] <= off[r + 1], who, ": row_off must not decrease");
+  const float* v = nullptr;
+  if (present(val)) {
+    TORCH_CHECK(!val->is_cuda() && val->scalar_type() == torch::kFloat32 && val->is_contiguous() &&
+                    val->numel() == fid.numel(),
+                who, ": val must be float32 of fid's size");
+    v = val->data_ptr<float>();
+  }
+  return {wh::ShapCsrRows{off, fid.data_ptr<int32_t>(), v}, n};
+}
+
 py::tuple gbdt_shap_rows_csr(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
                              TreeInts defl, TreeReals leaf, const TreeReals& cover,
                              int64_t num_class, double base, const Tensor& row_off,
                              const Tensor& fid, const c10::optional<Tensor>& val, bool approx,
                              bool f32) {
-  TORCH_CHECK(!row_off.is_cuda() && row_off.scalar_type() == torch::kInt64 &&
-                  row_off.is_contiguous() && row_off.numel() >= 1 && !fid.is_cuda() &&
-                  fid.scalar_type() == torch::kInt32 && fid.is_contiguous(),
-              "gbdt_shap_rows_csr: row_off int64 [n + 1] and fid int32 on the CPU");
-  const int64_t n = row_off.numel() - 1;
-  const int64_t* off = row_off.data_ptr<int64_t>();
-  TORCH_CHECK(off[0] >= 0 && off[n] <= fid.numel(), "gbdt_shap_rows_csr: row_off leaves fid");
-  for (int64_t r = 0; r < n; ++r)
-    TORCH_CHECK(off[r] <= off[r + 1], "gbdt_shap_rows_csr: row_off must not decrease");
-  const float* v = nullptr;
-  if (present(val)) {
-    TORCH_CHECK(!val->is_cuda() && val->scalar_type() == torch::kFloat32 && val->is_contiguous() &&
-                    val->numel() == fid.numel(),
-                "gbdt_shap_rows_csr: val must be float32 of fid's size");
-    v = val->data_ptr<float>();
-  }
+  const auto [rows, n] = shap_host_csr("gbdt_shap_rows_csr", row_off, fid, val);
   return shap_rows_host(wh::GbdtForestTrees{std::move(feat), std::move(left), std::move(right),
                                             std::move(defl), std::move(cond), std::move(leaf)},
-                        cover, num_class, base,
-                        wh::ShapCsrRows{off, fid.data_ptr<int32_t>(), v}, n, approx, f32);
+                        cover, num_class, base, rows, n, approx, f32);
+}
+
+// The interactions' host references: (Phi float64 [K, n, U + 1, U + 1] in
+// compact columns, the bias last; used int32 [U]); f32: computed in fp32
+// throughout.
+template <class Rows>
+py::tuple shap_inter_rows_host(wh::GbdtForestTrees tr, const TreeReals& cover, int64_t num_class,
+                               double base, const Rows& rows, int64_t n, bool f32) {
+  const wh::GbdtShapModel m = wh::gbdt_shap_pack(tr, cover, (int)num_class);
+  const int64_t U1 = (int64_t)m.used.size() + 1;
+  auto phi = torch::empty({num_class, n, U1, U1}, torch::kFloat64);
+  if (f32) {
+    auto p32 = torch::empty({num_class, n, U1, U1}, torch::kFloat32);
+    wh::gbdt_shap_inter_rows<float>(m, rows, n, base, p32.data_ptr<float>());
+    phi.copy_(p32);
+  } else {
+    wh::gbdt_shap_inter_rows<double>(m, rows, n, base, phi.data_ptr<double>());
+  }
+  return py::make_tuple(phi, int32_tensor(m.used, {U1 - 1}));
+}
+
+py::tuple gbdt_shap_inter_rows(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
+                               TreeInts defl, TreeReals leaf, const TreeReals& cover,
+                               int64_t num_class, double base, const Tensor& X, bool f32) {
+  TORCH_CHECK(!X.is_cuda() && X.dim() == 2 && X.scalar_type() == torch::kFloat32 &&
+                  X.is_contiguous(),
+              "gbdt_shap_inter_rows: X must be a contiguous CPU float32 matrix");
+  return shap_inter_rows_host(
+      wh::GbdtForestTrees{std::move(feat), std::move(left), std::move(right), std::move(defl),
+                          std::move(cond), std::move(leaf)},
+      cover, num_class, base, wh::ShapDenseRows{X.data_ptr<float>(), X.size(1)}, X.size(0), f32);
+}
+
+py::tuple gbdt_shap_inter_rows_csr(TreeInts feat, TreeReals cond, TreeInts left, TreeInts right,
+                                   TreeInts defl, TreeReals leaf, const TreeReals& cover,
+                                   int64_t num_class, double base, const Tensor& row_off,
+                                   const Tensor& fid, const c10::optional<Tensor>& val, bool f32) {
+  const auto [rows, n] = shap_host_csr("gbdt_shap_inter_rows_csr", row_off, fid, val);
+  return shap_inter_rows_host(
+      wh::GbdtForestTrees{std::move(feat), std::move(left), std::move(right), std::move(defl),
+                          std::move(cond), std::move(leaf)},
+      cover, num_class, base, rows, n, f32);
 }
 
 // out: float32 [K, n, U + 1], contiguous, the bias column set by the caller.
@@ -723,6 +772,67 @@ void gbdt_shap_csr(const Tensor& row_off, const Tensor& fid, const c10::optional
   shap_run(paths, elems, ecol, chunks, ncol, out, n, [&](const wh::ShapChunk& c) {
     wh::gbdt_shap_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val), n, c, s);
   });
+}
+
+// Interactions: out float32 [K, n, U + 1, U + 1], contiguous, cell (U, U) of
+// every matrix (the bias) set by the caller; every other cell is written. The
+// exact contributions of the same rows (launch_phi: the unchanged kernels)
+// give the diagonal; the pairs are gathered in a scratch triangle
+// [K, n, U (U - 1) / 2].
+template <class LaunchPhi, class LaunchInter>
+void shap_inter_run(const Tensor& paths, const Tensor& elems, const Tensor& ecol,
+                    const ShapChunks& chunks, int64_t ncol, const Tensor& out, int64_t n,
+                    hipStream_t s, LaunchPhi launch_phi, LaunchInter launch_inter) {
+  CHECK_IN(out, torch::kFloat32);
+  TORCH_CHECK(out.dim() == 4 && out.size(0) >= 1 && out.size(1) == n && out.size(2) == ncol + 1 &&
+                  out.size(3) == ncol + 1 && ncol < INT32_MAX,
+              "interactions must be [K, n, U + 1, U + 1]");
+  const int64_t K = out.size(0), U1 = ncol + 1, TP = wh::gbdt_shap_inter_pairs(ncol);
+  auto phi = torch::zeros({K, n, U1}, out.options());
+  phi.select(2, ncol).copy_(out.select(2, ncol).select(2, ncol));
+  shap_run(paths, elems, ecol, chunks, ncol, phi, n, launch_phi);  // (checks the table)
+  auto tri = torch::zeros({K, n, TP}, out.options());
+  if (n == 0) return;
+  for (auto& [path_begin, npath, elem_begin, nelem, cls, width] : chunks)
+    launch_inter(wh::ShapChunk{paths.data_ptr(), elems.data_ptr(), ptr<int32_t>(ecol),
+                               (int)path_begin, (int)npath, (int)elem_begin, (int)nelem,
+                               (int)width, (int)U1, ptr<float>(tri) + cls * n * TP});
+  wh::gbdt_shap_inter_out(ptr<float>(tri), ptr<float>(phi), K * n, (int)U1, ptr<float>(out), s);
+}
+
+void gbdt_shap_inter(const Tensor& X, const Tensor& paths, const Tensor& elems,
+                     const Tensor& ecol, const ShapChunks& chunks, int64_t ncol, int64_t max_feat,
+                     const Tensor& out) {
+  CHECK_IN(X, torch::kFloat32);
+  TORCH_CHECK(X.dim() == 2 && max_feat < X.size(1), "forest splits on a feature X does not have");
+  c10::DeviceGuard g(X.device());
+  auto s = cur_stream(X);
+  shap_inter_run(
+      paths, elems, ecol, chunks, ncol, out, X.size(0), s,
+      [&](const wh::ShapChunk& c) {
+        wh::gbdt_shap(ptr<float>(X), X.size(0), (int)X.size(1), c, s);
+      },
+      [&](const wh::ShapChunk& c) {
+        wh::gbdt_shap_inter(ptr<float>(X), X.size(0), (int)X.size(1), c, s);
+      });
+}
+
+void gbdt_shap_inter_csr(const Tensor& row_off, const Tensor& fid,
+                         const c10::optional<Tensor>& val, const Tensor& paths,
+                         const Tensor& elems, const Tensor& ecol, const ShapChunks& chunks,
+                         int64_t ncol, const Tensor& out) {
+  const int64_t n = shap_csr_check(row_off, fid, val);
+  c10::DeviceGuard g(row_off.device());
+  auto s = cur_stream(row_off);
+  shap_inter_run(
+      paths, elems, ecol, chunks, ncol, out, n, s,
+      [&](const wh::ShapChunk& c) {
+        wh::gbdt_shap_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val), n, c, s);
+      },
+      [&](const wh::ShapChunk& c) {
+        wh::gbdt_shap_inter_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid), optptr<float>(val), n, c,
+                                s);
+      });
 }
 
 wh::SaabasForest saabas_forest(const Tensor& nodes, const Tensor& tree_off, const Tensor& node_m,
@@ -1467,6 +1577,19 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_shap_csr", &gbdt_shap_csr, py::arg("row_off"), py::arg("fid"), py::arg("val"),
         py::arg("paths"), py::arg("elems"), py::arg("ecol"), py::arg("chunks"), py::arg("ncol"),
         py::arg("out"));
+  m.def("gbdt_shap_inter_lds_cols", &wh::gbdt_shap_inter_lds_cols);
+  m.def("gbdt_shap_inter_rows", &gbdt_shap_inter_rows, py::arg("feat"), py::arg("cond"),
+        py::arg("left"), py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cover"),
+        py::arg("num_class"), py::arg("base"), py::arg("X"), py::arg("f32") = false);
+  m.def("gbdt_shap_inter_rows_csr", &gbdt_shap_inter_rows_csr, py::arg("feat"), py::arg("cond"),
+        py::arg("left"), py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cover"),
+        py::arg("num_class"), py::arg("base"), py::arg("row_off"), py::arg("fid"), py::arg("val"),
+        py::arg("f32") = false);
+  m.def("gbdt_shap_inter", &gbdt_shap_inter, py::arg("X"), py::arg("paths"), py::arg("elems"),
+        py::arg("ecol"), py::arg("chunks"), py::arg("ncol"), py::arg("max_feat"), py::arg("out"));
+  m.def("gbdt_shap_inter_csr", &gbdt_shap_inter_csr, py::arg("row_off"), py::arg("fid"),
+        py::arg("val"), py::arg("paths"), py::arg("elems"), py::arg("ecol"), py::arg("chunks"),
+        py::arg("ncol"), py::arg("out"));
   m.def("gbdt_saabas", &gbdt_saabas, py::arg("X"), py::arg("nodes"), py::arg("tree_off"),
         py::arg("node_m"), py::arg("node_col"), py::arg("ncol"), py::arg("max_feat"),
         py::arg("out"));

@@ -21,6 +21,18 @@
 // on n nor on the run.
 // Saabas: one row per lane walks the forest with the table of expected
 // values beside it and adds m(child) - m(node) into its own output row.
+//   gbdt_shap_inter, gbdt_shap_inter_csr   pairwise interactions, one chunk
+//   gbdt_shap_inter_out                    triangle and phi -> the matrices
+// Interactions (pred_interactions): the exact kernel's structure once more,
+// per path one EXTEND and UNWOUND-SUM for every element conditioned on, so
+// about path length times its work. The packed triangles of a block's rows,
+// U (U - 1) / 2 floats each, stay in LDS beside the path table up to
+// gbdt_shap_inter_lds_cols() columns: the block is then as many whole waves,
+// 1024 threads down to 704, as the chunk's table leaves room for (the
+// arithmetic is in gbdt_shap_plan.h); above that a row accumulates in its own
+// slice of the global scratch triangle. The epilogue mirrors the triangle,
+// takes the diagonal from the exact kernel's phi and writes the bias row and
+// column.
 #include <algorithm>
 
 #include "host/gbdt_shap_plan.h"
@@ -221,6 +233,131 @@ __global__ __launch_bounds__(kSaabasThreads) void k_saabas(
   }
 }
 
+// LDS of the interaction kernel: the path table as in k_shap, then the
+// packed triangles [block threads / W][TP] of the block's rows.
+__host__ __device__ inline size_t shap_inter_lds_bytes(int npath, int nelem, int rows, int64_t TP,
+                                                       bool lds_acc) {
+  return (size_t)npath * 16 + (size_t)nelem * 20 + 65 * 4 +
+         (lds_acc ? (size_t)rows * (size_t)TP * 4 : 0);
+}
+
+// Pairwise interactions of one chunk of paths, the structure of k_shap. For
+// each path every element c in turn is conditioned on: EXTEND over the other
+// d - 1 elements (lane j holds w[j]), UNWOUND-SUM of the lane's own element,
+// and the lane whose column is the larger of the pair adds into the row's
+// packed triangle, entry col (col - 1) / 2 + col_c of TP: the statements of
+// gbdt_shap_inter_path<float> in its order. A path's pairs are distinct
+// cells, so the lanes of a group never meet in one within a path, and the
+// paths are fenced from each other. tri: the class's [n, TP] slice of the
+// scratch triangle: the LDS tile is added to it once per chunk, or, kLdsAcc
+// false, the row's slice of it is the accumulator. The block is whole waves,
+// as many as the launch found room for (shap_inter_threads).
+template <class Rows, int W, bool kLdsAcc>
+__global__ __launch_bounds__(kShapThreads) void k_shap_inter(
+    Rows rows, int64_t n, const uint4* __restrict__ paths, const uint4* __restrict__ elems,
+    const int32_t* __restrict__ ecol, int elem_begin, int nelem, int npath, int64_t TP,
+    float* tri) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) uint4 shap_lds[];
+  const int R = blockDim.x / W;
+  uint4* sp = shap_lds;
+  uint4* se = sp + npath;
+  int32_t* sc = reinterpret_cast<int32_t*>(se + nelem);
+  float* sinv = reinterpret_cast<float*>(sc + nelem);
+  float* tile = sinv + 65;
+  for (int j = threadIdx.x; j < npath; j += blockDim.x) sp[j] = paths[j];
+  for (int j = threadIdx.x; j < nelem; j += blockDim.x) {
+    se[j] = elems[elem_begin + j];
+    sc[j] = ecol[elem_begin + j];
+  }
+  if (threadIdx.x < 65) sinv[threadIdx.x] = 1.f / (float)max((int)threadIdx.x, 1);
+  __syncthreads();
+  const int g = threadIdx.x / W, lane = threadIdx.x % W;
+  const int64_t tiles = (n + R - 1) / R;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t r = t * R + g;
+    const bool live = r < n;
+    const typename Rows::Row row = rows.row(live ? r : n - 1);
+    float* acc = kLdsAcc ? tile + (size_t)g * TP : tri + (live ? r : n - 1) * TP;
+    if constexpr (kLdsAcc) {
+      for (int c = lane; c < TP; c += W) acc[c] = 0.f;
+      wave_fence();
+    }
+    ShapLane nxt = shap_lane(rows, row, sp, se, sc, 0, elem_begin, lane);
+    for (int p = 0; p < npath; ++p) {
+      const ShapLane cur = nxt;
+      if (p + 1 < npath) nxt = shap_lane(rows, row, sp, se, sc, p + 1, elem_begin, lane);
+      const int d = cur.d, m = d - 1;
+      if (d < 2) continue;  // (d is the path's: the same in every lane)
+      const float z = fabsf(cur.zo), o = cur.zo > 0.f ? 1.f : 0.f;
+      const float half = cur.leaf * 0.5f, mp1 = (float)(m + 1), rz = 1.f / z;
+      const int64_t base = (int64_t)cur.col * (cur.col - 1) / 2;
+      for (int c = 1; c <= d; ++c) {
+        const float zc = __shfl(cur.zo, c, W);
+        const int colc = __shfl(cur.col, c, W);
+        // the element of the path's largest column has no lane above it (the
+        // columns are the path's: the same in every group of the wave)
+        if (!__any(lane >= 1 && lane <= d && cur.col > colc)) continue;
+        const float fc = (zc > 0.f ? 1.f : 0.f) - fabsf(zc);
+        // EXTEND by the elements beside c
+        float w = lane == 0 ? 1.f : 0.f;
+        for (int l = 1; l <= m; ++l) {
+          const float zs = __shfl(cur.zo, l < c ? l : l + 1, W);
+          const float wp = lane_below(w);
+          const float a = fabsf(zs) * w * (float)(l - lane);
+          const float bb = lane && zs > 0.f ? wp * (float)lane : 0.f;
+          w = (a + bb) * sinv[l + 1];
+        }
+        // UNWOUND-SUM without the lane's own element
+        float next = __shfl(w, m, W), tot1 = 0.f, tot0 = 0.f;
+        for (int j = m - 1; j >= 0; --j) {
+          const float wj = __shfl(w, j, W);
+          const float tmp = next * (mp1 * sinv[j + 1]);
+          tot1 += tmp;
+          next = wj - tmp * z * ((float)(m - j) * sinv[m + 1]);
+          tot0 += wj * rz * (mp1 * sinv[m - j]);
+        }
+        if (lane >= 1 && lane <= d && cur.col > colc && live)
+          acc[base + colc] += (o != 0.f ? tot1 : tot0) * (o - z) * fc * half;
+      }
+      wave_fence();
+    }
+    if constexpr (kLdsAcc) {
+      if (live)
+        for (int c = lane; c < TP; c += W) tri[r * TP + c] += acc[c];
+      wave_fence();
+    }
+  }
+}
+
+// out [rows, U1, U1] of tri [rows, TP] and phi [rows, U1] (rows = classes x
+// matrix rows), one thread per cell: a pair's two cells are one number of
+// the triangle, the diagonal is phi[i] minus the cells of row i one after
+// the other by ascending column (gbdt_shap_inter_rows), cell (U, U) is
+// phi's bias, the rest of row and column U is zero.
+__global__ __launch_bounds__(kSaabasThreads) void k_shap_inter_out(
+    const float* __restrict__ tri, const float* __restrict__ phi, int64_t rows, int U1,
+    int64_t TP, float* __restrict__ out) {
+  const int U = U1 - 1;
+  const int64_t cells = rows * U1 * U1, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < cells; x += step) {
+    const int64_t r = x / ((int64_t)U1 * U1);
+    const int i = (int)((x / U1) % U1), j = (int)(x % U1);
+    const float* t = tri + r * TP;
+    float v = 0.f;
+    if (i == U || j == U) {
+      if (i == j) v = phi[r * U1 + U];
+    } else if (i != j) {
+      v = i > j ? t[(int64_t)i * (i - 1) / 2 + j] : t[(int64_t)j * (j - 1) / 2 + i];
+    } else {
+      v = phi[r * U1 + i];
+      for (int k = 0; k < U; ++k)
+        if (k != i) v -= k < i ? t[(int64_t)i * (i - 1) / 2 + k] : t[(int64_t)k * (k - 1) / 2 + i];
+    }
+    out[x] = v;
+  }
+}
+
 int shap_cus() {  // of the current device
   int dev = 0, cus = 0;
   WH_HIP_CHECK(hipGetDevice(&dev));
@@ -258,6 +395,50 @@ void shap_launch(const Rows& rows, int64_t n, const ShapChunk& c, hipStream_t s)
   else shap_launch_w<Rows, 64>(rows, n, c, s);
 }
 
+// Threads of the block that takes a chunk: kShapThreads, or, with the LDS
+// accumulator, the most whole waves whose rows' triangles fit beside the
+// chunk's table (at least kShapInterThreads up to kShapInterLdsCols columns,
+// whatever the table holds).
+inline int shap_inter_threads(int npath, int nelem, int W, int64_t TP, bool lds_acc) {
+  int threads = kShapThreads;
+  while (threads > 64 && shap_inter_lds_bytes(npath, nelem, threads / W, TP, lds_acc) >
+                             (size_t)kShapLdsBytes)
+    threads -= 64;
+  return threads;
+}
+
+template <class Rows, int W>
+void shap_inter_launch_w(const Rows& rows, int64_t n, const ShapChunk& c, hipStream_t s) {
+  const int U = c.U1 - 1;
+  const int64_t TP = gbdt_shap_inter_pairs(U);
+  const bool lds_acc = U <= kShapInterLdsCols;
+  const int threads = shap_inter_threads(c.npath, c.nelem, W, TP, lds_acc), R = threads / W;
+  const size_t lds = shap_inter_lds_bytes(c.npath, c.nelem, R, TP, lds_acc);
+  static bool attr = false;
+  if (!attr) {  // dynamic LDS above 64 KB must be opted into per kernel
+    const void* ks[2] = {(const void*)k_shap_inter<Rows, W, true>,
+                         (const void*)k_shap_inter<Rows, W, false>};
+    for (const void* k : ks)
+      WH_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       kShapLdsBytes));
+    attr = true;
+  }
+  const int grid = grid_for(n, R, shap_cus() * kShapBlocksPerCu);
+  auto kern = lds_acc ? k_shap_inter<Rows, W, true> : k_shap_inter<Rows, W, false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, rows, n,
+                     reinterpret_cast<const uint4*>(c.paths) + c.path_begin,
+                     reinterpret_cast<const uint4*>(c.elems), c.ecol, c.elem_begin, c.nelem,
+                     c.npath, TP, c.out);
+}
+
+template <class Rows>
+void shap_inter_launch(const Rows& rows, int64_t n, const ShapChunk& c, hipStream_t s) {
+  if (n <= 0 || c.npath <= 0 || c.U1 < 3) return;  // (one column: no pairs)
+  if (c.width == 16) shap_inter_launch_w<Rows, 16>(rows, n, c, s);
+  else if (c.width == 32) shap_inter_launch_w<Rows, 32>(rows, n, c, s);
+  else shap_inter_launch_w<Rows, 64>(rows, n, c, s);
+}
+
 template <class Rows>
 void saabas_launch(const Rows& rows, int64_t n, const SaabasForest& f, hipStream_t s) {
   if (n <= 0 || f.T <= 0) return;
@@ -278,6 +459,23 @@ void gbdt_shap(const float* X, int64_t n, int f, const ShapChunk& c, hipStream_t
 void gbdt_shap_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
                    const ShapChunk& c, hipStream_t s) {
   shap_launch(CsrRows{row_off, fid, val}, n, c, s);
+}
+
+void gbdt_shap_inter(const float* X, int64_t n, int f, const ShapChunk& c, hipStream_t s) {
+  shap_inter_launch(DenseRows{X, f}, n, c, s);
+}
+
+void gbdt_shap_inter_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
+                         const ShapChunk& c, hipStream_t s) {
+  shap_inter_launch(CsrRows{row_off, fid, val}, n, c, s);
+}
+
+void gbdt_shap_inter_out(const float* tri, const float* phi, int64_t rows, int U1, float* out,
+                         hipStream_t s) {
+  if (rows <= 0) return;
+  const int grid = grid_for(rows * U1 * U1, kSaabasThreads, shap_cus() * 8);
+  hipLaunchKernelGGL(k_shap_inter_out, dim3(grid), dim3(kSaabasThreads), 0, s, tri, phi, rows, U1,
+                     gbdt_shap_inter_pairs(U1 - 1), out);
 }
 
 void gbdt_saabas(const float* X, int64_t n, int f, const SaabasForest& fo, hipStream_t s) {

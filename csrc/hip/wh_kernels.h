@@ -714,6 +714,22 @@ struct SaabasForest {
 void gbdt_saabas(const float* X, int64_t n, int f, const SaabasForest& fo, hipStream_t s);
 void gbdt_saabas_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
                      const SaabasForest& fo, hipStream_t s);
+// Pairwise interactions (pred_interactions), one chunk of the same plan per
+// launch: c.out is the class's [n, TP] slice of a scratch triangle, TP =
+// U (U - 1) / 2 with U = c.U1 - 1, zero before the first chunk; a row's cell
+// (a, b), a > b compact columns, is entry a (a - 1) / 2 + b. U <=
+// gbdt_shap_inter_lds_cols() accumulates in LDS, a wider model in the
+// triangle itself. Nothing runs for n <= 0, an empty chunk or U < 2.
+void gbdt_shap_inter(const float* X, int64_t n, int f, const ShapChunk& c, hipStream_t s);
+void gbdt_shap_inter_csr(const int64_t* row_off, const int32_t* fid, const float* val, int64_t n,
+                         const ShapChunk& c, hipStream_t s);
+// The matrices out [rows, U1, U1] of tri [rows, TP] and phi [rows, U1] (the
+// exact contributions of the same rows, the bias last; rows = classes x
+// matrix rows): both cells of a pair from the triangle, the diagonal phi[i]
+// minus the cells of row i by ascending column, cell (U, U) the bias, zeros
+// in the rest of row and column U. Every cell of out is written.
+void gbdt_shap_inter_out(const float* tri, const float* phi, int64_t rows, int U1, float* out,
+                         hipStream_t s);
 // blocks the exact kernels keep resident on the current device (the grid
 // strides over row tiles of 1024 / width rows beyond that)
 int gbdt_shap_max_blocks();

@@ -5,7 +5,9 @@
 // list, the launch plan of the kernels, and the reference implementations
 // templated on the float type (double: the CPU path and the tests' oracle;
 // float: the yardstick of the kernels' rounding error, which they mirror
-// operation by operation). Free of HIP and torch.
+// operation by operation). The same tables and plan serve the pairwise
+// interaction values (pred_interactions; the last section: the accumulator
+// limit of their kernel and their references). Free of HIP and torch.
 //
 // The game (docs/bsp_apps.md "Contributions"): v(S) walks the tree; a node
 // whose feature is in S sends the row where it goes (v < cond left, missing
@@ -358,6 +360,136 @@ inline void gbdt_shap_rows(const GbdtShapModel& m, const Rows& rows, int64_t n, 
       gbdt_shap_path<T>(e, p.len, (T)p.leaf, one.data(), out + ((p.tree % m.K) * n + r) * U1,
                         &scratch);
     }
+}
+
+// ----------------------------------------------------------- interactions
+// pred_interactions (docs/bsp_apps.md "Interactions"): per row and class the
+// matrix [U + 1, U + 1] over the compact columns. The pair accumulator of a
+// row is the packed strict lower triangle: cell (a, b), a > b, is entry
+// a (a - 1) / 2 + b of U (U - 1) / 2.
+//
+// What shapes the kernel's plan. It consumes the tables and chunks above
+// unchanged, so a block holds up to kShapLdsElems elements and as many paths
+// (36 B per one-element path) and the table of 1 / k:
+//   2048 * 36 + 65 * 4                = 73 988 B of the CU's 163 840 B (160 KB),
+//   163 840 - 73 988                  = 89 852 B for the triangles of its rows.
+// A block of 1024 threads (64 rows at 16 lanes a row) would keep only U <= 26
+// in LDS beside a full table, less than the 28 columns of the benchmarks'
+// matrices, and a group of 64 lanes (a path of 32 elements or more) could
+// never meet an LDS accumulator below U = 32. So the block shrinks by whole
+// waves while the chunk's own table asks for it, down to 704 threads, 11
+// waves, 44 rows at 16 lanes:
+//   89 852 / (44 * 4)                 = 510 floats a row,
+//   U (U - 1) / 2 <= 510              : U = 32 (496; 33 needs 528),
+// and no larger block reaches 32 columns beside a full table. (The table of
+// one full depth-8 tree, 256 paths of 8 elements, is 45 KB: with 28 columns
+// 1024 threads have room.)
+constexpr int kShapLdsBytes = 160 * 1024;
+constexpr int kShapInterThreads = 704;
+constexpr int kShapInterLdsCols = 32;
+static_assert(kShapInterThreads % 64 == 0, "whole waves");
+static_assert((size_t)kShapLdsElems * 36 + 65 * 4 +
+                      (size_t)(kShapInterThreads / 16) * 4 *
+                          (kShapInterLdsCols * (kShapInterLdsCols - 1) / 2) <=
+                  kShapLdsBytes,
+              "table and triangles fit the CU's LDS");
+static_assert((size_t)kShapLdsElems * 36 + 65 * 4 +
+                      (size_t)(kShapInterThreads / 16) * 4 *
+                          ((kShapInterLdsCols + 1) * kShapInterLdsCols / 2) >
+                  kShapLdsBytes,
+              "one more column would not");
+inline int gbdt_shap_inter_lds_cols() { return kShapInterLdsCols; }
+inline int64_t gbdt_shap_inter_pairs(int64_t U) { return U * (U - 1) / 2; }
+
+// One path of d elements for one row: for every conditioning element c,
+// EXTEND over the other d - 1 elements in path order, then UNWOUND-SUM of
+// every element i whose column is above c's (each unordered pair once):
+// tri[(col_i, col_c)] += unwound_sum * (o_i - z_i) * (o_c - z_c) * (leaf / 2).
+// A path of one element has no pairs. Every product is written in the order
+// the kernel takes it; w is scratch.
+template <class T>
+inline void gbdt_shap_inter_path(const GbdtShapElem* e, int d, T leaf, const uint8_t* one, T* tri,
+                                 std::vector<T>* scratch) {
+  if (d < 2) return;
+  std::vector<T>& w = *scratch;
+  const int m = d - 1;  // the elements beside c
+  const T half = leaf * T(0.5), mp1 = T(m + 1);
+  for (int c = 1; c <= d; ++c) {
+    const T fc = (one[c - 1] ? T(1) : T(0)) - (T)e[c - 1].z;
+    w.assign(m + 1, T(0));
+    w[0] = T(1);
+    for (int l = 1; l <= m; ++l) {  // EXTEND by the l-th element beside c
+      const int k = l < c ? l : l + 1;
+      const T z = (T)e[k - 1].z, o = one[k - 1] ? T(1) : T(0), inv = T(1) / T(l + 1);
+      for (int j = l; j >= 0; --j) {
+        const T a = z * w[j] * T(l - j);
+        const T b = j ? o * w[j - 1] * T(j) : T(0);
+        w[j] = (a + b) * inv;
+      }
+    }
+    for (int i = 1; i <= d; ++i) {  // UNWOUND-SUM without element i
+      if (i == c || e[i - 1].col < e[c - 1].col) continue;
+      const T z = (T)e[i - 1].z, rz = T(1) / z;
+      T total = T(0), next = w[m];
+      for (int j = m - 1; j >= 0; --j) {
+        if (one[i - 1]) {
+          const T tmp = next * (mp1 * (T(1) / T(j + 1)));
+          total += tmp;
+          next = w[j] - tmp * z * (T(m - j) * (T(1) / T(m + 1)));
+        } else {
+          total += w[j] * rz * (mp1 * (T(1) / T(m - j)));
+        }
+      }
+      tri[gbdt_shap_inter_pairs(e[i - 1].col) + e[c - 1].col] +=
+          total * ((one[i - 1] ? T(1) : T(0)) - z) * fc * half;
+    }
+  }
+}
+
+// out [K, n, U + 1, U + 1] (compact columns, the bias last): the interaction
+// values of the model's trees, paths in tree order. Off the diagonal the
+// row's pair accumulator, both cells of a pair the same number; on it
+// phi[i] (gbdt_shap_rows<T>) minus the off-diagonal cells of row i, one after
+// the other by ascending column; cell (U, U) the bias, the rest of row and
+// column U zero. Everything in T.
+template <class T, class Rows>
+inline void gbdt_shap_inter_rows(const GbdtShapModel& m, const Rows& rows, int64_t n, double base,
+                                 T* out) {
+  const int64_t U = (int64_t)m.used.size(), U1 = U + 1, TP = gbdt_shap_inter_pairs(U);
+  std::vector<T> phi((size_t)m.K * n * U1);
+  gbdt_shap_rows<T>(m, rows, n, base, false, phi.data());
+  std::fill(out, out + (int64_t)m.K * n * U1 * U1, T(0));
+  std::vector<uint8_t> one;
+  std::vector<T> scratch, tri((size_t)m.K * TP);
+  for (int64_t r = 0; r < n; ++r) {
+    std::fill(tri.begin(), tri.end(), T(0));
+    for (const GbdtShapPath& p : m.paths) {
+      const GbdtShapElem* e = m.elems.data() + p.begin;
+      one.resize(p.len);
+      for (int k = 0; k < p.len; ++k) {
+        float v;
+        one[k] = rows.value(r, e[k].feat, &v) ? (e[k].lo <= v && v < e[k].hi) : e[k].missing_ok;
+      }
+      gbdt_shap_inter_path<T>(e, p.len, (T)p.leaf, one.data(), tri.data() + (p.tree % m.K) * TP,
+                              &scratch);
+    }
+    for (int k = 0; k < m.K; ++k) {
+      const T* t = tri.data() + k * TP;
+      const T* ph = phi.data() + (k * n + r) * U1;
+      T* o = out + (k * n + r) * U1 * U1;
+      for (int64_t i = 0; i < U; ++i) {
+        T diag = ph[i];
+        for (int64_t j = 0; j < U; ++j) {
+          if (j == i) continue;
+          const T v = i > j ? t[gbdt_shap_inter_pairs(i) + j] : t[gbdt_shap_inter_pairs(j) + i];
+          o[i * U1 + j] = v;
+          diag -= v;
+        }
+        o[i * U1 + i] = diag;
+      }
+      o[U * U1 + U] = ph[U];
+    }
+  }
 }
 
 }  // namespace wh

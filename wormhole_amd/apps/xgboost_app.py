@@ -25,7 +25,14 @@ attribution; implies pred_contribs); neither goes with pred_margin or
 pred_leaf. They write one line per row (per row and class, row-major, for a
 multi: objective): ``j:value`` for every feature j with a non-zero
 contribution, ascending, then ``num_feature:bias``; a line's values sum to the
-row's margin (docs/bsp_apps.md "Contributions").
+row's margin (docs/bsp_apps.md "Contributions"). pred_interactions (SHAP
+interaction values, the matrix of which pred_contribs is the row sums; with
+none of pred_margin, pred_leaf, pred_contribs, approx_contribs) writes lines
+of the same count and order: ``i:j:value`` for every non-zero cell with
+i <= j, ascending by (i, j), then ``num_feature:num_feature:bias``; an
+off-diagonal token is one of the pair's two equal cells, so a line's diagonal
+tokens plus twice its off-diagonal tokens sum to the row's margin
+(docs/bsp_apps.md "Interactions").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -90,7 +97,7 @@ def main(argv):
     num_feature = 0
     dsparse = None  # dsparse=1|0: keep the data CSR / dense (default: by width)
     ntree_limit, pred_margin, pred_leaf = 0, False, False
-    pred_contribs, approx_contribs = False, False
+    pred_contribs, approx_contribs, pred_interactions = False, False, False
     evals = []
     for k, v in parse_args(argv):
         if param.set(k, v):
@@ -139,6 +146,8 @@ def main(argv):
             pred_contribs = bool(int(v))
         elif k == "approx_contribs":
             approx_contribs = bool(int(v))
+        elif k == "pred_interactions":
+            pred_interactions = bool(int(v))
         elif k in ("dsplit",):
             if v not in ("row", "auto"):
                 raise SystemExit("only dsplit=row is supported")
@@ -156,6 +165,11 @@ def main(argv):
     if pred_contribs and (pred_leaf or pred_margin):
         raise SystemExit("pred_contribs=1 / approx_contribs=1 and pred_%s=1 exclude each other"
                          % ("leaf" if pred_leaf else "margin"))
+    if pred_interactions:
+        for name, on in (("pred_margin", pred_margin), ("pred_leaf", pred_leaf),
+                         ("approx_contribs", approx_contribs), ("pred_contribs", pred_contribs)):
+            if on:
+                raise SystemExit("pred_interactions=1 and %s=1 exclude each other" % name)
     host = _native.host()
 
     def load(path):
@@ -269,7 +283,11 @@ def main(argv):
             # the untransformed margins, n or n x K row-major; pred_leaf: the
             # n x T row-major node ids (the dump's numbering) of the leaves
             fmt = "%d\n" if pred_leaf else "%g\n"
-            if pred_contribs:
+            lines = pred_contribs or pred_interactions
+            if pred_interactions:
+                fmt = "%s\n"
+                pred = _interaction_lines(b, dm, limit)
+            elif pred_contribs:
                 fmt = "%s\n"
                 pred = _contrib_lines(b, dm, limit, approx_contribs)
             elif pred_leaf:
@@ -280,7 +298,7 @@ def main(argv):
                     pred = margin if margin.dim() == 1 else margin.t()
                 else:
                     pred = b.obj.pred(margin).float()
-            if not pred_contribs:
+            if not lines:
                 pred = pred.cpu().reshape(-1).tolist()
             parts = bsp.comm.allgather_object(pred)
             if bsp.rank == 0:
@@ -379,6 +397,27 @@ def _contrib_lines(b, dm, limit, approx):
         for row in phi.reshape(-1, phi.shape[-1]):
             toks = ["%d:%g" % (cols[j], row[j]) for j in row[:-1].nonzero()[0]]
             lines.append(" ".join(toks + ["%d:%g" % (F, row[-1])]))
+    return lines
+
+
+def _interaction_lines(b, dm, limit):
+    """The pred_interactions lines of a matrix, n x K of them, row-major:
+    ``i:j:%g`` for the non-zero cells with i <= j, ascending by (i, j), then
+    ``num_feature:num_feature:%g``, the bias. Computed in row blocks whose
+    compact matrices stay under CONTRIB_BLOCK_BYTES."""
+    K, F, lines = b.obj.n_group, b.num_feature, []
+    ntree = min(limit, len(b.trees)) if limit else len(b.trees)
+    U = len({f for t in b.trees[:ntree] for f in t.feat if f >= 0})
+    block = max(1, CONTRIB_BLOCK_BYTES // (4 * K * (U + 1) ** 2))
+    for a in range(0, dm.n, block):
+        phi, used = b.predict_interactions(dm, limit, compact=True,
+                                           rows=(a, min(dm.n, a + block)))
+        phi = (phi if K > 1 else phi[None]).transpose(0, 1).cpu().double().numpy()
+        cols = used.tolist()
+        for mat in phi.reshape(-1, U + 1, U + 1):
+            toks = ["%d:%d:%g" % (cols[i], cols[j], mat[i, j])
+                    for i, j in zip(*mat[:U, :U].nonzero()) if i <= j]
+            lines.append(" ".join(toks + ["%d:%d:%g" % (F, F, mat[U, U])]))
     return lines
 
 

@@ -104,6 +104,23 @@ class DMatrix(_QueryGroups):
         a, b = rows if rows is not None else (0, self.n)
         return _native.hip().gbdt_shap_rows(X=self.X[a:b].contiguous(), approx=approx, **model)
 
+    def predict_interactions(self, shap, rows=None):
+        """Interaction values of a packed forest (gbdt_tree.py ShapForest) on
+        the GPU, rows [a, b) (default: all): float32 [K, b - a, U + 1, U + 1]
+        in the forest's compact columns, the bias last."""
+        a, b = rows if rows is not None else (0, self.n)
+        out = shap.new_inter_out(b - a, self.device)
+        _native.hip().gbdt_shap_inter(X=self.X[a:b], paths=shap.paths, elems=shap.elems,
+                                      ecol=shap.ecol, chunks=shap.chunks, ncol=shap.used.numel(),
+                                      max_feat=shap.max_feat, out=out)
+        return out
+
+    def predict_interactions_host(self, model, rows=None):
+        """The same on a CPU matrix by the host reference: (float64
+        [K, b - a, U + 1, U + 1], used). model: as predict_contribs_host."""
+        a, b = rows if rows is not None else (0, self.n)
+        return _native.hip().gbdt_shap_inter_rows(X=self.X[a:b].contiguous(), **model)
+
 
 class CSRMatrix(_QueryGroups):
     """A rank's rows kept sparse (libsvm data with a wide feature space:
@@ -174,6 +191,22 @@ class CSRMatrix(_QueryGroups):
         return _native.hip().gbdt_shap_rows_csr(row_off=self.row_off[a:b + 1].contiguous(),
                                                 fid=self.fid, val=self.val, approx=approx,
                                                 **model)
+
+    def predict_interactions(self, shap, rows=None):
+        """As DMatrix.predict_interactions, an absent feature standing for NaN."""
+        a, b = rows if rows is not None else (0, self.n)
+        out = shap.new_inter_out(b - a, self.device)
+        _native.hip().gbdt_shap_inter_csr(row_off=self.row_off[a:b + 1], fid=self.fid,
+                                          val=self.val, paths=shap.paths, elems=shap.elems,
+                                          ecol=shap.ecol, chunks=shap.chunks,
+                                          ncol=shap.used.numel(), out=out)
+        return out
+
+    def predict_interactions_host(self, model, rows=None):
+        """As DMatrix.predict_interactions_host, over the CSR rows themselves."""
+        a, b = rows if rows is not None else (0, self.n)
+        return _native.hip().gbdt_shap_inter_rows_csr(row_off=self.row_off[a:b + 1].contiguous(),
+                                                      fid=self.fid, val=self.val, **model)
 
     def dense_cpu(self):
         """(CPU reference path only: small matrices)"""

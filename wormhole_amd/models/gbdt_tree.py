@@ -244,6 +244,13 @@ class ShapForest:
         out[:, :, -1] = self.bias.to(torch.float32).to(device)[:, None]
         return out
 
+    def new_inter_out(self, n, device):
+        """float32 [K, n, U + 1, U + 1]: zeros, the bias in cell (U, U)."""
+        U1 = self.used.numel() + 1
+        out = torch.zeros((self.K, n, U1, U1), dtype=torch.float32, device=device)
+        out[:, :, -1, -1] = self.bias.to(torch.float32).to(device)[:, None]
+        return out
+
 
 # ---------------------------------------------------------------- booster
 class Booster:
@@ -350,6 +357,42 @@ class Booster:
             full = torch.zeros(phi.shape[:2] + (F + 1,), dtype=phi.dtype, device=phi.device)
             full[:, :, used.to(phi.device)] = phi[:, :, :-1]
             full[:, :, F] = phi[:, :, -1]
+            phi = full
+        phi = phi[0] if K == 1 else phi
+        return (phi, used) if compact else phi
+
+    def predict_interactions(self, dm, ntree_limit=0, compact=False, rows=None):
+        """SHAP interaction values in margin space (docs/bsp_apps.md
+        "Interactions"): [n, F + 1, F + 1], or [K, n, F + 1, F + 1] for K
+        classes. Cell (i, j), i != j, is half the Shapley interaction index
+        of features i and j summed over the (class's) trees, the same number
+        in (j, i); cell (i, i) is predict_contribs' column i minus the rest
+        of row i, so a row of the matrix sums to that column and the matrix
+        to the row's predict_margin; cell (F, F) is the bias, the rest of row
+        and column F zero. F, compact ((Phi [.., U + 1, U + 1], used)), rows,
+        the float type per device and the ValueErrors are predict_contribs'."""
+        K = self.obj.n_group
+        ntree = self._ntree(ntree_limit)
+        a, b = rows if rows is not None else (0, dm.n)
+        if not 0 <= a <= b <= dm.n:
+            raise ValueError("rows must be a range within the matrix")
+        if torch.device(dm.device).type == "cuda":
+            sf = self.shap_forest(dm.device, ntree)
+            phi, used = dm.predict_interactions(sf, rows=(a, b)), sf.used
+        else:
+            trees = self.trees[:ntree]
+            model = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
+                         left=[t.left for t in trees], right=[t.right for t in trees],
+                         defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                         cover=[t.cover for t in trees], num_class=K, base=self.base_margin)
+            phi, used = dm.predict_interactions_host(model, rows=(a, b))
+        used = used.long()
+        if not compact:
+            F = max(self.num_feature, dm.ncol, int(used[-1]) + 1 if used.numel() else 0)
+            full = torch.zeros(phi.shape[:2] + (F + 1, F + 1), dtype=phi.dtype, device=phi.device)
+            u = used.to(phi.device)
+            full[:, :, u[:, None], u[None, :]] = phi[:, :, :-1, :-1]
+            full[:, :, F, F] = phi[:, :, -1, -1]
             phi = full
         phi = phi[0] if K == 1 else phi
         return (phi, used) if compact else phi
