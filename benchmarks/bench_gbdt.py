@@ -8,6 +8,11 @@ the ranks (row split, histogram allreduce per level over RCCL).
 --num-class K: multi:softprob on K quantile classes of the same synthetic
 score (K trees per round; reports rounds/s and trees/s, and the softmax
 gradient kernel alone against its plain-torch form and the 12 K n byte floor).
+
+--monotone PATTERN: train with monotone_constraints, PATTERN's characters
+``+`` / ``-`` / ``0`` cycled over the features (``"+-0"``: feature 0 rising,
+1 falling, 2 free, 3 rising, ...): the bounded split search and the weight
+intervals of every grower, against the same run without the option.
 """
 import argparse
 import json
@@ -68,6 +73,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--num-class", type=int, default=0,
                     help="K > 1: multi:softprob, K trees per round (--trees counts trees)")
+    ap.add_argument("--monotone", default="",
+                    help='monotone_constraints as a pattern of + - 0 cycled over the features')
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the framework's PyTorch CPU path (anchor numbers)")
     ap.add_argument("--gpus", type=int, default=1,
@@ -96,6 +103,12 @@ def main():
     p.max_depth = a.depth
     p.eta = 0.1
     p.max_bin = a.max_bin
+    if a.monotone:
+        if set(a.monotone) - set("+-0"):
+            ap.error("--monotone takes a pattern of the characters + - 0")
+        sign = {"+": "1", "-": "-1", "0": "0"}
+        p.set("monotone_constraints", ",".join(sign[a.monotone[j % len(a.monotone)]]
+                                               for j in range(a.features)))
     sync()
     t_prep = time.perf_counter()
     cuts = G.Cuts.build(dm, p.max_bin, bsp)
@@ -142,7 +155,8 @@ def main():
         print(json.dumps({"metric": "GBDT trees/s (hist, depth %d, %dx%d)" % (a.depth, a.rows, a.features),
                           "value": ntree / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
                           "ms_per_tree": 1000 * dt / ntree,
-                          "trees": ntree, **extra, "sketch_bin_s": t_prep,
+                          "trees": ntree, **extra, "monotone": a.monotone or None,
+                          "sketch_bin_s": t_prep,
                           "hist_exchange": ("feature-reduce-scatter" if tb.xchg is not None
                                             else "allreduce") if bsp.world > 1 else None,
                           "hist_bytes_per_rank_per_tree": hb,

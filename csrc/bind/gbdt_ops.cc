@@ -107,15 +107,33 @@ void gbdt_hist(const Tensor& B, int64_t nbin, const Tensor& ridx, const Tensor& 
 // The best split of each of S slots into out [S, 6] {gain, feature, bin, dir,
 // GL, HL}: hist [S, F, nbin, 2], totals [S x 2] and the [F x nbin] candidate
 // mask on hist's device. False: the kernel refused (nbin > 1024 or no input).
+// monotone_constraints: mono (int8 per feature of hist, else null) and the
+// slots' weight intervals bounds [S x 2].
 bool split_search(const Tensor& hist, const double* totals, const uint8_t* valid, int S,
-                  double alpha, double lambda, double mcw, const Tensor& out, hipStream_t s) {
+                  double alpha, double lambda, double mcw, const Tensor& out, hipStream_t s,
+                  const int8_t* mono = nullptr, const double* bounds = nullptr) {
   auto cand = torch::empty({std::max<int64_t>(S * hist.size(1) * 4, 1)}, hist.options());
   return wh::gbdt_split(ptr<double>(hist), totals, valid, S, (int)hist.size(1), (int)hist.size(2),
-                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s);
+                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s, mono, bounds);
+}
+
+// the optional (mono [F] int8, bounds [S, 2] float64) pair of a split search
+// on `like`'s device: both or neither
+void check_mono(const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds,
+                const Tensor& like, int64_t S, int64_t F) {
+  TORCH_CHECK(mono.has_value() == bounds.has_value(), "mono and bounds go together");
+  if (!mono.has_value()) return;
+  CHECK_IN(*mono, torch::kInt8);
+  CHECK_IN(*bounds, torch::kFloat64);
+  TORCH_CHECK(mono->device() == like.device() && bounds->device() == like.device(),
+              "mono / bounds on another device");
+  TORCH_CHECK(mono->numel() == F, "mono must be [F]");
+  TORCH_CHECK(bounds->numel() == 2 * S, "bounds must be [S, 2]");
 }
 
 Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid, double alpha,
-                  double lambda, double min_child_weight) {
+                  double lambda, double min_child_weight, const c10::optional<Tensor>& mono,
+                  const c10::optional<Tensor>& bounds) {
   CHECK_IN(hist, torch::kFloat64);
   CHECK_IN(totals, torch::kFloat64);
   CHECK_IN(valid, torch::kBool);
@@ -125,8 +143,10 @@ Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid,
   TORCH_CHECK(totals.numel() == 2 * (int64_t)S, "totals must be [S, 2]");
   TORCH_CHECK(valid.numel() == (int64_t)F * nbin, "valid must be [F, nbin]");
   auto out = torch::empty({S, 6}, hist.options());
+  check_mono(mono, bounds, hist, S, F);
   TORCH_CHECK(split_search(hist, ptr<double>(totals), ptr<uint8_t>(valid), S, alpha, lambda,
-                           min_child_weight, out, cur_stream(hist)),
+                           min_child_weight, out, cur_stream(hist), optptr<int8_t>(mono),
+                           optptr<double>(bounds)),
               "gbdt_split: nbin > 1024 or empty input");
   return out;
 }
@@ -375,7 +395,8 @@ Tensor gbdt_hist_csr(const Tensor& row_off, const Tensor& gbin, const Tensor& ri
 }
 
 Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cut_off,
-                      const c10::optional<Tensor>& fvalid, double alpha, double lambda, double mcw) {
+                      const c10::optional<Tensor>& fvalid, double alpha, double lambda, double mcw,
+                      const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds) {
   CHECK_IN(hist, torch::kFloat64);
   CHECK_IN(totals, torch::kFloat64);
   CHECK_IN(cut_off, torch::kInt32);
@@ -384,9 +405,11 @@ Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cu
   const int F = (int)cut_off.numel() - 1;
   auto out = torch::empty({S, 6}, hist.options());
   auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 5, 1)}, hist.options());
+  check_mono(mono, bounds, hist, S, F);
   wh::gbdt_split_csr(ptr<double>(hist), hist.size(1), ptr<double>(totals), ptr<int32_t>(cut_off),
                      optptr<uint8_t>(fvalid), S, F, alpha, lambda, mcw, ptr<double>(cand),
-                     ptr<double>(out), cur_stream(hist));
+                     ptr<double>(out), cur_stream(hist), optptr<int8_t>(mono),
+                     optptr<double>(bounds));
   return out;
 }
 
@@ -1036,7 +1059,8 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
                     std::vector<std::pair<int64_t, int64_t>> fgroups, int64_t max_fcnt,
                     std::vector<double> root_tot, std::vector<float> cut_vals,
                     std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
-                    double mcw, int64_t max_depth, double rt_eps, py::object allreduce) {
+                    double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
+                    const c10::optional<Tensor>& mono) {
   const GrowCtx cx(B, Bc, ridx0, gpair, qscale, valid, nbin, fgroups, max_fcnt);
   c10::DeviceGuard g(B.device());
   const auto s = cx.s;
@@ -1045,12 +1069,29 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   const auto &f64 = cx.f64, &i32 = cx.i32;
   const int64_t per = (int64_t)F * nbin * 2;
   const bool reduce = !allreduce.is_none();
+  // monotone_constraints: the signs on the device (the split search) and on
+  // the host (the children's intervals), and every node's weight interval
+  const bool mono_on = present(mono);
+  std::vector<int8_t> mono_h;
+  if (mono_on) {
+    CHECK_IN(*mono, torch::kInt8);
+    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(), "mono must be [F] on B's device");
+    auto mh = mono->cpu();
+    mono_h.assign(mh.data_ptr<int8_t>(), mh.data_ptr<int8_t>() + F);
+  }
+  const double inf = std::numeric_limits<double>::infinity();
   // host tree
   TreeLists t;
   std::vector<std::array<double, 2>> tot;
-  auto add = [&](int par) { return tot.push_back({0, 0}), t.add(par); };
-  auto weight = [&](double G_, double H_) {
+  std::vector<wh::GbdtBounds> bnd;
+  auto add = [&](int par) { return tot.push_back({0, 0}), bnd.push_back({-inf, inf}), t.add(par); };
+  auto weight0 = [&](double G_, double H_) {
     return H_ < mcw ? 0.0 : -l1_threshold(G_, alpha) / (H_ + lambda);
+  };
+  // a node's weight: clamped to its interval ({-inf, inf} without constraints)
+  auto weight = [&](int nd) {
+    const double w = weight0(tot[nd][0], tot[nd][1]);
+    return mono_on ? wh::gbdt_clamp_weight(w, bnd[nd]) : w;
   };
   const int root = add(-1);
   tot[root] = {root_tot[0], root_tot[1]};
@@ -1116,13 +1157,19 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     const bool last = depth == max_depth;
     Tensor split_out;
     if (!last) {
-      double* th = up.get<double>(2 * S);
+      // totals [S x 2], then (constraints) the weight intervals [S x 2]
+      const int nb = mono_on ? 2 : 1;
+      double* th = up.get<double>(2 * S * nb);
       for (int k = 0; k < S; ++k) th[2 * k] = tot[frontier[k]][0], th[2 * k + 1] = tot[frontier[k]][1];
-      auto T = up.tensor().narrow(0, 0, 16 * S).to(B.device(), true).view(torch::kFloat64);
+      if (mono_on)
+        for (int k = 0; k < S; ++k)
+          th[2 * S + 2 * k] = bnd[frontier[k]][0], th[2 * S + 2 * k + 1] = bnd[frontier[k]][1];
+      auto T = up.tensor().narrow(0, 0, 16 * S * nb).to(B.device(), true).view(torch::kFloat64);
       up.mark(s);
       split_out = torch::empty({S, 6}, f64);
       TORCH_CHECK(split_search(H_front, ptr<double>(T), ptr<uint8_t>(valid), S, alpha, lambda, mcw,
-                               split_out, s),
+                               split_out, s, optptr<int8_t>(mono),
+                               mono_on ? ptr<double>(T) + 2 * S : nullptr),
                   "gbdt_split failed");
     }
     // the level's one synchronisation: split results + previous partition counts
@@ -1137,7 +1184,7 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     resolve_pending(nl_h);
     for (int nd : frontier) {
       t.cover[nd] = tot[nd][1];
-      t.bw[nd] = weight(tot[nd][0], tot[nd][1]);
+      t.bw[nd] = weight(nd);
       t.leaf[nd] = eta * t.bw[nd];
     }
     if (last) break;
@@ -1152,6 +1199,13 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       t.left[nd] = l, t.right[nd] = r;
       tot[l] = {o[4], o[5]};
       tot[r] = {tot[nd][0] - o[4], tot[nd][1] - o[5]};
+      if (mono_on) {
+        const wh::GbdtBounds pb = bnd[nd];  // (bnd grew: no reference into it)
+        const auto cb = wh::gbdt_child_bounds(
+            mono_h[f], pb, wh::gbdt_clamp_weight(weight0(tot[l][0], tot[l][1]), pb),
+            wh::gbdt_clamp_weight(weight0(tot[r][0], tot[r][1]), pb));
+        bnd[l] = cb[0], bnd[r] = cb[1];
+      }
       split_k.push_back(k);
     }
     if (split_k.empty()) break;
@@ -1322,7 +1376,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                         std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
                         double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
                         py::object reduce_scatter, py::object pick, int64_t f_lo, bool walk,
-                        bool defer) {
+                        bool defer, const c10::optional<Tensor>& mono) {
   // Multi-rank: either every level's built histograms are allreduced (all
   // features on every rank), or -- reduce_scatter / pick given
   // (models/gbdt.py HistExchange) -- each rank receives the global sums of
@@ -1340,6 +1394,23 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
   const auto &f64 = cx.f64, &i32 = cx.i32, &u8 = cx.u8;
   const bool shard = !reduce_scatter.is_none();
   TORCH_CHECK(!shard || !pick.is_none(), "gbdt_grow_dev: reduce_scatter needs pick");
+  // monotone_constraints: mono [F] int8 (all features: the split search reads
+  // this rank's slice, the apply kernel the picked, global feature) and the
+  // slots' weight intervals, ping-ponged level by level like the totals
+  const bool mono_on = present(mono);
+  if (mono_on) {
+    CHECK_IN(*mono, torch::kInt8);
+    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(),
+                "gbdt_grow_dev: mono must be [F] on B's device");
+  }
+  const int8_t* d_mono = optptr<int8_t>(mono);
+  Tensor bounds_cur;
+  if (mono_on) {
+    const double inf = std::numeric_limits<double>::infinity();
+    bounds_cur = torch::empty({1, 2}, f64);
+    bounds_cur.select(1, 0).fill_(-inf);
+    bounds_cur.select(1, 1).fill_(inf);
+  }
   const bool reduce = shard || !allreduce.is_none();
   // rank partials -> global sums: all features, or this rank's slice
   auto reduce_hist = [&](Tensor h) -> Tensor {
@@ -1410,7 +1481,8 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
       so = torch::empty({S, 6}, f64);
       if (Fl > 0) {
         TORCH_CHECK(split_search(H_front, ptr<double>(tot_cur), vp + (int64_t)f_lo * nbin, S, alpha,
-                                 lambda, mcw, so, s),
+                                 lambda, mcw, so, s, mono_on ? d_mono + f_lo : nullptr,
+                                 mono_on ? ptr<double>(bounds_cur) : nullptr),
                     "gbdt_split failed");
       } else {  // (more ranks than features: this rank owns none)
         so.zero_();
@@ -1426,13 +1498,16 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     auto pi = torch::empty({4 * S}, i32);  // pfeat | pbin | lcur | rcur
     auto pb = torch::empty({3 * S}, u8);   // pdefl | split | build_left
     Tensor tot_next = last ? Tensor() : torch::empty({2 * S, 2}, f64);
+    Tensor bounds_next = last || !mono_on ? Tensor() : torch::empty({2 * S, 2}, f64);
     int32_t* pfeat = ptr<int32_t>(pi);
     uint8_t* pdefl = ptr<uint8_t>(pb);
     wh::gbdt_dev_apply(S, S - 1, last, last ? nullptr : ptr<double>(so), ptr<double>(tot_cur),
                        ptr<int32_t>(seg_cur), ptr<uint8_t>(alive_cur), eta, alpha, lambda, mcw,
                        rt_eps, ptr<double>(nodes), pfeat, pfeat + S, pdefl, pfeat + 2 * S,
                        pfeat + 3 * S, pdefl + S, pdefl + 2 * S,
-                       last ? nullptr : ptr<double>(tot_next), nullptr, s);
+                       last ? nullptr : ptr<double>(tot_next), nullptr, s, d_mono,
+                       mono_on ? ptr<double>(bounds_cur) : nullptr,
+                       bounds_next.defined() ? ptr<double>(bounds_next) : nullptr);
     if (last) break;
     // walk: the caller adds the leaf values by walking the tree over each
     // row's bins (models/gbdt.py _finish), so the level whose children are
@@ -1467,6 +1542,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                 "gbdt_grow_dev: too many slots");
     if (leaves_next) {  // (leaf segments: left child empty -- unused by the walk)
       tot_cur = tot_next;
+      bounds_cur = bounds_next;
       seg_cur = seg_next;
       alive_cur = alive_next;
       continue;
@@ -1488,6 +1564,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     }
     H_front = H_next;
     tot_cur = tot_next;
+    bounds_cur = bounds_next;
     seg_cur = seg_next;
     alive_cur = alive_next;
   }
@@ -1510,7 +1587,9 @@ void bind_gbdt(py::module_& m) {
         py::arg("node_feat"), py::arg("node_bin"), py::arg("node_defl"), py::arg("seg_beg"),
         py::arg("seg_end"), py::arg("nleft"), py::arg("Bc") = py::none());
   m.def("gbdt_seg_fill", &gbdt_seg_fill);
-  m.def("gbdt_split", &gbdt_split);
+  m.def("gbdt_split", &gbdt_split, py::arg("hist"), py::arg("totals"), py::arg("valid"),
+        py::arg("alpha"), py::arg("reg_lambda"), py::arg("min_child_weight"),
+        py::arg("mono") = py::none(), py::arg("bounds") = py::none());
   m.def("gbdt_leaf_add", &gbdt_leaf_add);
   m.def("gbdt_leaf_walk", &gbdt_leaf_walk, py::arg("B"), py::arg("feat"), py::arg("bin"),
         py::arg("defl"), py::arg("left"), py::arg("right"), py::arg("val"), py::arg("margin"),
@@ -1523,13 +1602,14 @@ void bind_gbdt(py::module_& m) {
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
-        py::arg("allreduce"));
+        py::arg("allreduce"), py::arg("mono") = py::none());
   m.def("gbdt_grow_dev", &gbdt_grow_dev, py::arg("B"), py::arg("Bc"), py::arg("ridx0"), py::arg("gpair"),
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
         py::arg("allreduce"), py::arg("reduce_scatter") = py::none(), py::arg("pick") = py::none(),
-        py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false);
+        py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false,
+        py::arg("mono") = py::none());
   m.def("gbdt_tree_from_nodes", &gbdt_tree_from_nodes);
   m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
         py::arg("lds") = true);
@@ -1540,7 +1620,9 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_qscale", &gbdt_qscale);
   m.def("gbdt_bin_csr", &gbdt_bin_csr);
   m.def("gbdt_hist_csr", &gbdt_hist_csr);
-  m.def("gbdt_split_csr", &gbdt_split_csr);
+  m.def("gbdt_split_csr", &gbdt_split_csr, py::arg("hist"), py::arg("totals"), py::arg("cut_off"),
+        py::arg("fvalid"), py::arg("alpha"), py::arg("reg_lambda"), py::arg("min_child_weight"),
+        py::arg("mono") = py::none(), py::arg("bounds") = py::none());
   m.def("gbdt_partition_csr", &gbdt_partition_csr);
   m.def("gbdt_predict_csr", &gbdt_predict_csr);
   // forest prediction: pack, plan and the capacity need no GPU

@@ -1249,6 +1249,23 @@ void gbdt_predict(const float* X, int64_t n, int f, const int32_t* feat, const f
 
 }  // namespace wh
 
+// The L1 threshold T(G) of alpha and the unclamped node weight -T(G) / (H +
+// lambda) (0 below min_child_weight): said once for the level loop's
+// bookkeeping and the bounded split search, which must evaluate the same
+// operations.
+namespace {
+
+__device__ __forceinline__ double gbdt_l1(double G, double alpha) {
+  return alpha <= 0 ? G : (G > alpha ? G - alpha : (G < -alpha ? G + alpha : 0.0));
+}
+
+__device__ __forceinline__ double gbdt_weight0(double G, double H, double alpha, double lambda,
+                                               double mcw) {
+  return H >= mcw ? -gbdt_l1(G, alpha) / (H + lambda) : 0.0;
+}
+
+}  // namespace
+
 namespace wh {
 namespace {
 
@@ -1288,14 +1305,21 @@ __global__ __launch_bounds__(256) void k_heap_tree(const double* __restrict__ no
 
 // One block: for slot s of depth d (S slots), decide its split from the
 // split search's result, record the node, and set up the partition and the
-// next level's totals (the host grower's level bookkeeping).
-__global__ __launch_bounds__(256) void k_gd_apply(
+// next level's totals (the host grower's level bookkeeping). MONO
+// (monotone_constraints): the slot's weight is clamped to its interval bnd
+// [S x 2], and an accepted split's children get theirs (bnd_next [2S x 2]):
+// the interval cut at the mean of the clamped child weights, by the sign of
+// mono [split feature] (global feature ids, as in `so`).
+template <bool MONO>
+__device__ __forceinline__ void gd_apply(
     int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
     const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
     double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
     int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
     int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
-    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft) {
+    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
+    const int8_t* __restrict__ mono, const double* __restrict__ bnd,
+    double* __restrict__ bnd_next) {
   for (int sl = threadIdx.x; sl < S; sl += blockDim.x) {
     if (nleft) nleft[sl] = 0;  // the partition's left counts (no memset launch)
     const double G = tot[2 * sl], H = tot[2 * sl + 1];
@@ -1304,10 +1328,12 @@ __global__ __launch_bounds__(256) void k_gd_apply(
     const bool al = alive[sl] != 0;
     const double* o = so + (int64_t)sl * 6;
     const bool sp = al && !last && o[0] > rt_eps;
-    double bw = 0.0;
-    if (H >= mcw) {
-      const double g = alpha <= 0 ? G : (G > alpha ? G - alpha : (G < -alpha ? G + alpha : 0.0));
-      bw = -g / (H + lambda);
+    double bw = gbdt_weight0(G, H, alpha, lambda, mcw);
+    double lo = 0.0, hi = 0.0;
+    if (MONO) {
+      lo = bnd[2 * sl];
+      hi = bnd[2 * sl + 1];
+      bw = bw < lo ? lo : (bw > hi ? hi : bw);
     }
     nd[0] = al ? 1.0 : 0.0;
     nd[1] = sp ? o[1] : -1.0;
@@ -1334,7 +1360,50 @@ __global__ __launch_bounds__(256) void k_gd_apply(
       tot_next[4 * sl + 2] = GR;
       tot_next[4 * sl + 3] = HR;
     }
+    if (MONO && bnd_next) {
+      double llo = lo, lhi = hi, rlo = lo, rhi = hi;
+      const int c = sp ? mono[(int32_t)o[1]] : 0;
+      if (c != 0) {
+        double wl = gbdt_weight0(GL, HL, alpha, lambda, mcw);
+        double wr = gbdt_weight0(GR, HR, alpha, lambda, mcw);
+        wl = wl < lo ? lo : (wl > hi ? hi : wl);
+        wr = wr < lo ? lo : (wr > hi ? hi : wr);
+        const double mid = (wl + wr) / 2;
+        if (c > 0) lhi = mid, rlo = mid;
+        else llo = mid, rhi = mid;
+      }
+      bnd_next[4 * sl] = llo;
+      bnd_next[4 * sl + 1] = lhi;
+      bnd_next[4 * sl + 2] = rlo;
+      bnd_next[4 * sl + 3] = rhi;
+    }
   }
+}
+
+// (two entry points, so that the unconstrained launch keeps its argument list)
+__global__ __launch_bounds__(256) void k_gd_apply(
+    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
+    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
+    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
+    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
+    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
+    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft) {
+  gd_apply<false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat,
+                  pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr, nullptr,
+                  nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_gd_apply_mono(
+    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
+    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
+    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
+    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
+    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
+    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
+    const int8_t* __restrict__ mono, const double* __restrict__ bnd,
+    double* __restrict__ bnd_next) {
+  gd_apply<true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat,
+                 pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next);
 }
 
 // One block (S <= 1024 slots): the next level's segments / alive flags, the
@@ -1441,10 +1510,16 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     const int32_t* seg, const uint8_t* alive, double eta, double alpha,
                     double lambda, double mcw, double rt_eps, double* nodes, int32_t* pfeat,
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
-                    uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s) {
-  hipLaunchKernelGGL(k_gd_apply, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot, seg,
-                     alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur, rcur,
-                     split, build_left, tot_next, nleft);
+                    uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
+                    const int8_t* mono, const double* bnd, double* bnd_next) {
+  if (mono)
+    hipLaunchKernelGGL(k_gd_apply_mono, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot,
+                       seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur,
+                       rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next);
+  else
+    hipLaunchKernelGGL(k_gd_apply, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot, seg,
+                       alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur, rcur,
+                       split, build_left, tot_next, nleft);
 }
 
 bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const uint8_t* build_left,
@@ -1483,6 +1558,44 @@ __device__ __forceinline__ double split_gain(double G, double H, const SplitPara
   return g * g / (H + p.lambda);
 }
 
+// monotone_constraints (MONO instantiations only): a node's weight is clamped
+// to its interval [lo, hi]; an unclamped side keeps split_gain's closed form,
+// a clamped one scores -(2 T(G) w + (H + lambda) w w). The host grower and
+// the torch reference evaluate exactly these operations, so no contraction
+// into fused multiply-adds here: the growers must pick equal split indexes.
+__device__ __forceinline__ double split_weight(double G, double H, const SplitParam& p, double lo,
+                                               double hi, double* w0_out = nullptr) {
+  const double w0 = gbdt_weight0(G, H, p.alpha, p.lambda, p.mcw);
+  if (w0_out) *w0_out = w0;
+  return w0 < lo ? lo : (w0 > hi ? hi : w0);
+}
+
+__device__ __forceinline__ double split_gain_bounded(double G, double H, const SplitParam& p,
+                                                     double lo, double hi, double* w_out) {
+#pragma clang fp contract(off)
+  double w0;
+  const double w = split_weight(G, H, p, lo, hi, &w0);
+  *w_out = w;
+  if (w == w0) return split_gain(G, H, p);
+  const double g = gbdt_l1(G, p.alpha);
+  const double d = H + p.lambda;
+  const double a = 2.0 * g * w;
+  const double b = d * w * w;
+  return -(a + b);
+}
+
+// gain of the candidate (GL, HL | GR, HR) of a feature with constraint c, or
+// -inf when its child weights are ordered against c
+__device__ __forceinline__ double split_cand_bounded(double GL, double HL, double GR, double HR,
+                                                     const SplitParam& p, double lo, double hi,
+                                                     int c, double parent) {
+  double wl, wr;
+  const double gl = split_gain_bounded(GL, HL, p, lo, hi, &wl);
+  const double gr = split_gain_bounded(GR, HR, p, lo, hi, &wr);
+  if ((c > 0 && wl > wr) || (c < 0 && wl < wr)) return -INFINITY;
+  return gl + gr - parent;
+}
+
 __device__ __forceinline__ double shfl_up_d(double v, int o) {
   return __shfl_up(v, o, 64);
 }
@@ -1491,9 +1604,14 @@ __device__ __forceinline__ bool better(double g, long long i, double bg, long lo
   return g > bg || (g == bg && i < bi);
 }
 
-__global__ __launch_bounds__(kSplitThreads) void k_split_feat(
+// MONO: mono [F] (int8: -1 | 0 | 1) and the slots' weight intervals bounds
+// [S x 2]; a rejected candidate has gain -inf and never wins (better() needs a
+// larger gain, and an all -inf block keeps its initial index).
+template <bool MONO>
+__device__ __forceinline__ void split_feat(
     const double* __restrict__ hist, const double* __restrict__ totals,
-    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand) {
+    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
+    const int8_t* __restrict__ mono, const double* __restrict__ bounds) {
   const int s = blockIdx.x / F, f = blockIdx.x % F;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const double* hb = hist + ((int64_t)s * F + f) * nbin * 2;
@@ -1536,7 +1654,15 @@ __global__ __launch_bounds__(kSplitThreads) void k_split_feat(
   }
   const double TG = totals[2 * s], TH = totals[2 * s + 1];
   const double mg = TG - pg, mh = TH - ph;  // rows missing this feature
-  const double parent = split_gain(TG, TH, p);
+  double blo = 0.0, bhi = 0.0, pw;
+  int mc = 0;
+  if (MONO) {
+    blo = bounds[2 * s];
+    bhi = bounds[2 * s + 1];
+    mc = mono[f];
+  }
+  const double parent =
+      MONO ? split_gain_bounded(TG, TH, p, blo, bhi, &pw) : split_gain(TG, TH, p);
   double best = -INFINITY;
   long long bidx = 0x7fffffffffffffffll;
   double bgl = 0.0, bhl = 0.0;
@@ -1550,8 +1676,10 @@ __global__ __launch_bounds__(kSplitThreads) void k_split_feat(
       const double GL = og + lg[u] + (d ? mg : 0.0), HL = oh + lh[u] + (d ? mh : 0.0);
       const double GR = TG - GL, HR = TH - HL;
       if (!(HL >= p.mcw && HR >= p.mcw)) continue;
-      const double g = split_gain(GL, HL, p) + split_gain(GR, HR, p) - parent;
+      const double g = MONO ? split_cand_bounded(GL, HL, GR, HR, p, blo, bhi, mc, parent)
+                            : split_gain(GL, HL, p) + split_gain(GR, HR, p) - parent;
       const long long idx = ((long long)f * nbin + b) * 2 + d;
+      if (MONO && g == -INFINITY) continue;
       if (better(g, idx, best, bidx)) {
         best = g;
         bidx = idx;
@@ -1596,6 +1724,20 @@ __global__ __launch_bounds__(kSplitThreads) void k_split_feat(
     c[2] = bgl;
     c[3] = bhl;
   }
+}
+
+// (two entry points, so that the unconstrained launch keeps its argument list)
+__global__ __launch_bounds__(kSplitThreads) void k_split_feat(
+    const double* __restrict__ hist, const double* __restrict__ totals,
+    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand) {
+  split_feat<false>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kSplitThreads) void k_split_feat_mono(
+    const double* __restrict__ hist, const double* __restrict__ totals,
+    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
+    const int8_t* __restrict__ mono, const double* __restrict__ bounds) {
+  split_feat<true>(hist, totals, valid, F, nbin, p, cand, mono, bounds);
 }
 
 __global__ __launch_bounds__(64) void k_split_node(const double* __restrict__ cand, int F,
@@ -1643,11 +1785,15 @@ namespace wh {
 
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s) {
+                hipStream_t s, const int8_t* mono, const double* bounds) {
   if (nbin > kSplitThreads * kSplitMaxPer || S <= 0 || F <= 0) return false;
   const SplitParam p{alpha, lambda, mcw};
-  hipLaunchKernelGGL(k_split_feat, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
-                     totals, valid, F, nbin, p, cand);
+  if (mono)
+    hipLaunchKernelGGL(k_split_feat_mono, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
+                       totals, valid, F, nbin, p, cand, mono, bounds);
+  else
+    hipLaunchKernelGGL(k_split_feat, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
+                       totals, valid, F, nbin, p, cand);
   hipLaunchKernelGGL(k_split_node, dim3((unsigned)S), dim3(64), 0, s, cand, F, nbin, out);
   return true;
 }
@@ -1721,11 +1867,15 @@ __global__ void k_hist_csr_fin(const unsigned long long* __restrict__ q, int64_t
 // best split per (node, feature): one thread walks the feature's bins; then
 // per node the best feature (ties: smallest (feature, bin, dir) as dense).
 // cand [S][F] = {gain, bin, dir, GL, HL}
-__global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
-                                 const double* __restrict__ totals,
-                                 const int32_t* __restrict__ cut_off,
-                                 const uint8_t* __restrict__ fvalid, int F, SplitParam p,
-                                 double* __restrict__ cand) {
+// (MONO: as k_split_feat)
+template <bool MONO>
+__device__ __forceinline__ void split_csr_feat(const double* __restrict__ hist, int64_t tb,
+                                               const double* __restrict__ totals,
+                                               const int32_t* __restrict__ cut_off,
+                                               const uint8_t* __restrict__ fvalid, int F,
+                                               SplitParam p, double* __restrict__ cand,
+                                               const int8_t* __restrict__ mono,
+                                               const double* __restrict__ bounds) {
   const int s = blockIdx.y;
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
@@ -1737,7 +1887,16 @@ __global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
   const double TG = totals[2 * s], TH = totals[2 * s + 1];
   double pg = 0.0, ph = 0.0;
   for (int b = b0; b < b1; ++b) pg += hb[2 * b], ph += hb[2 * b + 1];
-  const double mg = TG - pg, mh = TH - ph, parent = split_gain(TG, TH, p);
+  const double mg = TG - pg, mh = TH - ph;
+  double blo = 0.0, bhi = 0.0, pw;
+  int mc = 0;
+  if (MONO) {
+    blo = bounds[2 * s];
+    bhi = bounds[2 * s + 1];
+    mc = mono[f];
+  }
+  const double parent =
+      MONO ? split_gain_bounded(TG, TH, p, blo, bhi, &pw) : split_gain(TG, TH, p);
   double best = -INFINITY, gl = 0.0, hl = 0.0, sg = 0.0, sh = 0.0;
   int bb = 0, bd = 0;
   for (int b = b0; b < b1; ++b) {
@@ -1747,13 +1906,31 @@ __global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
       const double GL = sg + (d ? mg : 0.0), HL = sh + (d ? mh : 0.0);
       const double GR = TG - GL, HR = TH - HL;
       if (!(HL >= p.mcw && HR >= p.mcw)) continue;
-      const double g = split_gain(GL, HL, p) + split_gain(GR, HR, p) - parent;
+      const double g = MONO ? split_cand_bounded(GL, HL, GR, HR, p, blo, bhi, mc, parent)
+                            : split_gain(GL, HL, p) + split_gain(GR, HR, p) - parent;
       if (g > best) {
         best = g, bb = b - b0, bd = d, gl = GL, hl = HL;
       }
     }
   }
   c[0] = best, c[1] = bb, c[2] = bd, c[3] = gl, c[4] = hl;
+}
+
+__global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
+                                 const double* __restrict__ totals,
+                                 const int32_t* __restrict__ cut_off,
+                                 const uint8_t* __restrict__ fvalid, int F, SplitParam p,
+                                 double* __restrict__ cand) {
+  split_csr_feat<false>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr);
+}
+
+__global__ void k_split_csr_feat_mono(const double* __restrict__ hist, int64_t tb,
+                                      const double* __restrict__ totals,
+                                      const int32_t* __restrict__ cut_off,
+                                      const uint8_t* __restrict__ fvalid, int F, SplitParam p,
+                                      double* __restrict__ cand, const int8_t* __restrict__ mono,
+                                      const double* __restrict__ bounds) {
+  split_csr_feat<true>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds);
 }
 
 __global__ __launch_bounds__(256) void k_split_csr_node(const double* __restrict__ cand, int F,
@@ -1881,11 +2058,16 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
 
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
-                    double lambda, double mcw, double* cand, double* out, hipStream_t s) {
+                    double lambda, double mcw, double* cand, double* out, hipStream_t s,
+                    const int8_t* mono, const double* bounds) {
   if (S <= 0 || F <= 0) return;
   const SplitParam p{alpha, lambda, mcw};
-  hipLaunchKernelGGL(k_split_csr_feat, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0, s,
-                     hist, tb, totals, cut_off, fvalid, F, p, cand);
+  if (mono)
+    hipLaunchKernelGGL(k_split_csr_feat_mono, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0,
+                       s, hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds);
+  else
+    hipLaunchKernelGGL(k_split_csr_feat, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0, s,
+                       hist, tb, totals, cut_off, fvalid, F, p, cand);
   hipLaunchKernelGGL(k_split_csr_node, dim3((unsigned)S), dim3(256), 0, s, cand, F, out);
 }
 

@@ -555,7 +555,12 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     const int32_t* seg, const uint8_t* alive, double eta, double alpha,
                     double lambda, double mcw, double rt_eps, double* nodes, int32_t* pfeat,
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
-                    uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s);
+                    uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
+                    const int8_t* mono = nullptr, const double* bnd = nullptr,
+                    double* bnd_next = nullptr);
+// (mono [F] int8, given under monotone_constraints: bnd [S x 2] are the slots'
+// weight intervals, the recorded weight is clamped to them, and bnd_next
+// [2S x 2] (optional) receives the children's)
 // lcur: the split slots' left cursors after the partition (their left
 // children end there; = the segment begin when no partition ran)
 bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const uint8_t* build_left,
@@ -599,7 +604,10 @@ void gbdt_leaf_add(const int32_t* ridx, int64_t n, const int32_t* pos_node, cons
 // [S * F * 4] double scratch. false when nbin > 1024.
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s);
+                hipStream_t s, const int8_t* mono = nullptr, const double* bounds = nullptr);
+// (mono [F] int8 in {-1, 0, 1}, given under monotone_constraints, with the
+// slots' weight intervals bounds [S x 2]: gains at the clamped weights, and a
+// candidate whose children are ordered against its feature's sign is dropped)
 // sparse (CSR) input: global bin ids (cut_off[f] + bin, -1 = unbinned),
 // compact [slots][total bins][2] histograms (tasks [ntask x 3] = {slot,
 // rbeg, rend}, hq: int64 scratch of the histogram's size), split search over
@@ -612,7 +620,8 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
                    int max_rows, int64_t tb, int nslot, int64_t* hq, double* hist, hipStream_t s);
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
-                    double lambda, double mcw, double* cand, double* out, hipStream_t s);
+                    double lambda, double mcw, double* cand, double* out, hipStream_t s,
+                    const int8_t* mono = nullptr, const double* bounds = nullptr);
 void gbdt_goleft_csr(const int64_t* row_off, const int32_t* fid, const int32_t* gbin,
                      const int32_t* cut_off, const int32_t* ridx, int64_t n,
                      const int32_t* pos_node, const int32_t* node_feat, const int32_t* node_bin,

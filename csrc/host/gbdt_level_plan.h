@@ -42,4 +42,24 @@ struct GbdtNodeTables {
         lc(par + nsplit), rc(lc + nnode), nwords(rc + nnode) {}
 };
 
+// monotone_constraints: a node's weight interval {lo, hi}. A weight is
+// clamped to it; an accepted split on a feature of sign c cuts it at the mean
+// of the children's clamped weights (wl, wr): c > 0 gives the left child
+// {lo, mid} and the right {mid, hi}, c < 0 the mirror image, c == 0 hands the
+// interval down unchanged. The same rule as models/gbdt.py child_bounds and
+// gbdt.hip k_gd_apply.
+using GbdtBounds = std::array<double, 2>;
+
+inline double gbdt_clamp_weight(double w, const GbdtBounds& b) {
+  return w < b[0] ? b[0] : (w > b[1] ? b[1] : w);
+}
+
+inline std::array<GbdtBounds, 2> gbdt_child_bounds(int c, const GbdtBounds& b, double wl,
+                                                   double wr) {
+  const double mid = (wl + wr) / 2;
+  if (c > 0) return {GbdtBounds{b[0], mid}, GbdtBounds{mid, b[1]}};
+  if (c < 0) return {GbdtBounds{mid, b[1]}, GbdtBounds{b[0], mid}};
+  return {b, b};
+}
+
 }  // namespace wh

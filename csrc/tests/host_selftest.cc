@@ -10,6 +10,8 @@
 // arithmetic of the exact AUC, of the two store guards' plans, of the
 // localize job's bookkeeping and of the GBDT histogram task lists and level
 // tables; and the host-thread AUC's job ledger under test workers.
+#include <cmath>
+#include <limits>
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -621,6 +623,22 @@ static void test_gbdt_level_plan() {
   EXPECT(wh::GbdtNodeTables(8, 1, 1).tb == 32 + 2);
   EXPECT(wh::GbdtNodeTables(1, 1, 0).tb == 4 + 1);
   EXPECT(wh::GbdtNodeTables(1, 1, 0).nwords == 5 + 1 + 1 + 0 + 0 + 1 + 1);
+  // weight intervals under monotone_constraints
+  {
+    const double inf = std::numeric_limits<double>::infinity();
+    const wh::GbdtBounds root{-inf, inf}, b{-1.0, 2.0};
+    EXPECT(wh::gbdt_clamp_weight(0.25, root) == 0.25);
+    EXPECT(wh::gbdt_clamp_weight(-3.0, b) == -1.0 && wh::gbdt_clamp_weight(5.0, b) == 2.0);
+    EXPECT(wh::gbdt_clamp_weight(2.0, b) == 2.0 && wh::gbdt_clamp_weight(-1.0, b) == -1.0);
+    // a negative zero inside the interval stays what it is (leaf text "-0")
+    EXPECT(std::signbit(wh::gbdt_clamp_weight(-0.0, wh::GbdtBounds{0.0, 1.0})));
+    auto up = wh::gbdt_child_bounds(1, root, -0.5, 1.5);
+    EXPECT((up[0] == wh::GbdtBounds{-inf, 0.5}) && (up[1] == wh::GbdtBounds{0.5, inf}));
+    auto down = wh::gbdt_child_bounds(-1, b, 1.0, 0.0);
+    EXPECT((down[0] == wh::GbdtBounds{0.5, 2.0}) && (down[1] == wh::GbdtBounds{-1.0, 0.5}));
+    auto free_ = wh::gbdt_child_bounds(0, b, 1.0, 0.0);
+    EXPECT(free_[0] == b && free_[1] == b);
+  }
 }
 
 // the localize job's bookkeeping (host/localize_plan.h) through the job

@@ -10,7 +10,7 @@ objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
 gamma, min_child_weight, max_depth, lambda, alpha, base_score, max_bin,
-subsample, colsample_bytree, seed, eval_metric, num_round, save_period,
+subsample, colsample_bytree, monotone_constraints, seed, eval_metric, num_round, save_period,
 eval_train, eval[name]=path, data, test:data, model_in, model_out, model_dir,
 fmap, name_dump, name_pred, dump_stats, dsplit=row, dsparse (keep the rows CSR:
 wide libsvm data; default when num_feature > 4096), nthread (ignored),
@@ -33,6 +33,19 @@ i <= j, ascending by (i, j), then ``num_feature:num_feature:bias``; an
 off-diagonal token is one of the pair's two equal cells, so a line's diagonal
 tokens plus twice its off-diagonal tokens sum to the row's margin
 (docs/bsp_apps.md "Interactions").
+
+Monotone constraints: ``monotone_constraints=(1,0,-1)`` (task=train only)
+lists -1, 0 or 1 per feature id from 0, comma-separated; the parentheses are
+optional, spaces are allowed, and in a conf file the value is quoted
+(``monotone_constraints = "(1,0,-1)"``). Missing trailing entries are 0; more
+entries than the data has features, or any other value, ends the run with an
+error. With +1 (-1) on feature j no tree's output falls (rises) when x_j
+rises and the other features stay put, for rows that store x_j: in every
+split on j every leaf of the left subtree is <= (>=) every leaf of the
+right one. Rows missing x_j follow the splits' default directions and are
+outside the guarantee. Every class's trees of a multi: objective are
+constrained; the model file, task=dump, pred and eval are unchanged
+(docs/bsp_apps.md "Monotone constraints").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -317,6 +330,8 @@ def main(argv):
     ncol = max([int(r[0].max().item()) + 1 if r[0].numel() else 0
                 for r in [train_raw] + [e[1] for e in eval_raw]] + [num_feature])
     ncol = int(bsp.allreduce_scalar(ncol, "max", torch.int64))
+    # (the same answer on every rank, before any further collective)
+    param.monotone_vector(ncol)
     dtrain = G.make_dmatrix(*train_raw, ncol=ncol, device=dev, sparse=dsparse,
                             group=load_group(data, train_raw[3].numel()))
     deval = [(name, G.make_dmatrix(*r, ncol=ncol, device=dev, sparse=dsparse,

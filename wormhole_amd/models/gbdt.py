@@ -133,22 +133,36 @@ def split_fields(t):
     return t[:, 0], t[:, 1].long(), t[:, 2].long(), t[:, 3].long(), t[:, 4:6]
 
 
-def find_splits_ref(p, hist, totals, valid):
-    """Parameters p; hist [S, F, nbin, 2] (global sums); totals [S, 2]; valid
-    [F, nbin] bool -> the host split table: the torch reference of the fused
-    kernels (and the CPU path)."""
+def split_gains(p, hist, totals, valid, mono=None, bounds=None):
+    """Every candidate of a level: (gain [S, F, nbin, 2 directions] with -inf
+    for what is no candidate, left sums [S, F, nbin, 2 directions, 2]); the
+    arguments of :func:`find_splits_ref`."""
     cum = hist.cumsum(2)
     present = cum[:, :, -1, :]
     tot = totals[:, None, None, :]
     miss = (totals[:, None, :] - present)[:, :, None, :]
     G, H = totals[:, 0], totals[:, 1]
-    parent_gain = p.calc_gain(G, H)[:, None, None]
+    if mono is None:
+        parent_gain = p.calc_gain(G, H)[:, None, None]
+    else:
+        bounds = bounds.to(hist.device).double()
+        c = mono.to(hist.device)[None, :, None]
+        lo, hi = bounds[:, 0], bounds[:, 1]
+        parent_gain = p.calc_gain_bounded(G, H, lo, hi)[0][:, None, None]
+        lo, hi = lo[:, None, None], hi[:, None, None]
     cands = []
     for defl in (0, 1):
         L = cum + (miss if defl else 0.0)
         R = tot - L
         ok = (L[..., 1] >= p.min_child_weight) & (R[..., 1] >= p.min_child_weight)
-        gain = p.calc_gain(L[..., 0], L[..., 1]) + p.calc_gain(R[..., 0], R[..., 1]) - parent_gain
+        if mono is None:
+            gain = (p.calc_gain(L[..., 0], L[..., 1]) + p.calc_gain(R[..., 0], R[..., 1])
+                    - parent_gain)
+        else:
+            gl, wl = p.calc_gain_bounded(L[..., 0], L[..., 1], lo, hi)
+            gr, wr = p.calc_gain_bounded(R[..., 0], R[..., 1], lo, hi)
+            gain = gl + gr - parent_gain
+            ok = ok & ~(((c > 0) & (wl > wr)) | ((c < 0) & (wl < wr)))
         gain = torch.where(ok, gain, torch.full_like(gain, -float("inf")))
         cands.append((gain, L))
     gain = torch.stack([c[0] for c in cands], -1)  # [S, F, nbin, 2dir]
@@ -156,6 +170,17 @@ def find_splits_ref(p, hist, totals, valid):
     # colsample_bytree, are not candidates
     gain = torch.where(valid.to(gain.device)[None, :, :, None], gain,
                        torch.full_like(gain, -float("inf")))
+    return gain, torch.stack([cands[0][1], cands[1][1]], 3)
+
+
+def find_splits_ref(p, hist, totals, valid, mono=None, bounds=None):
+    """Parameters p; hist [S, F, nbin, 2] (global sums); totals [S, 2]; valid
+    [F, nbin] bool -> the host split table: the torch reference of the fused
+    kernels (and the CPU path). monotone_constraints: mono [F] int8 and the
+    slots' weight intervals bounds [S, 2] (float64) -- each side's gain is
+    taken at its clamped weight and a candidate whose child weights are
+    ordered against its feature's constraint is rejected."""
+    gain, Lall = split_gains(p, hist, totals, valid, mono, bounds)  # Lall [S, F, nbin, 2dir, 2]
     S, nbin = gain.shape[0], gain.shape[2]
     flat = gain.reshape(S, -1)
     arg = flat.argmax(1)
@@ -164,21 +189,82 @@ def find_splits_ref(p, hist, totals, valid):
     rest = arg // 2
     b = rest % nbin
     f = rest // nbin
-    Lall = torch.stack([cands[0][1], cands[1][1]], 3)  # [S, F, nbin, 2dir, 2]
     Ls = Lall[torch.arange(S, device=arg.device), f, b, d]  # [S, 2]
     # one device->host transfer for the whole level
     return split_table(bg, f, b, d, Ls).cpu()
 
 
-def find_splits(p, hist, totals, valid):
+def find_splits(p, hist, totals, valid, mono=None, bounds=None):
     """:func:`find_splits_ref`, on the GPU by the fused split-search kernels
     (csrc/hip/gbdt.hip k_split_feat / k_split_node: scan + gain + argmax in
     two launches instead of ~40 elementwise ops per level)."""
     if hist.is_cuda and hist.shape[0] > 0 and hist.shape[2] <= 1024:
+        if mono is not None:
+            mono = mono.to(hist.device).contiguous()
+            bounds = bounds.to(hist.device).double().contiguous()
         return _native.hip().gbdt_split(hist.double().contiguous(), totals.double().contiguous(),
                                         valid.to(hist.device).contiguous(), float(p.alpha),
-                                        float(p.reg_lambda), float(p.min_child_weight)).cpu()
-    return find_splits_ref(p, hist, totals, valid)
+                                        float(p.reg_lambda), float(p.min_child_weight),
+                                        mono=mono, bounds=bounds).cpu()
+    return find_splits_ref(p, hist, totals, valid, mono, bounds)
+
+
+def find_splits_csr_ref(p, hist, totals, cut_off, fvalid=None, mono=None, bounds=None):
+    """:func:`find_splits_ref` over compact histograms [S, total bins, 2]
+    (feature f owns bins cut_off[f]:cut_off[f + 1], a list; fvalid [F]: this
+    tree's candidate features, or None): the CSR builder's CPU path and the
+    reference of the CSR split kernels. (Unconstrained gains are taken on
+    torch scalars, in fp32; bounded ones in Python floats.)"""
+    o = cut_off
+    S = hist.shape[0]
+    res = torch.zeros(S, 6, dtype=torch.float64)
+    for s_ in range(S):
+        TG, TH = float(totals[s_, 0]), float(totals[s_, 1])
+        if mono is None:
+            parent = float(p.calc_gain(torch.tensor(TG), torch.tensor(TH)))
+        else:
+            lo, hi = float(bounds[s_, 0]), float(bounds[s_, 1])
+            parent = p.side_gain_bounded(TG, TH, lo, hi)[0]
+        best = (-float("inf"), 0, 0, 0, 0.0, 0.0)
+        for f in range(len(o) - 1):
+            if o[f + 1] <= o[f] or (fvalid is not None and not int(fvalid[f])):
+                continue
+            hb = hist[s_, o[f]:o[f + 1]]
+            cum = hb.cumsum(0)
+            mg, mh = TG - float(cum[-1, 0]), TH - float(cum[-1, 1])
+            for b in range(hb.shape[0]):
+                for d in (0, 1):
+                    GL = float(cum[b, 0]) + (mg if d else 0.0)
+                    HL = float(cum[b, 1]) + (mh if d else 0.0)
+                    GR, HR = TG - GL, TH - HL
+                    if not (HL >= p.min_child_weight and HR >= p.min_child_weight):
+                        continue
+                    if mono is None:
+                        g = (float(p.calc_gain(torch.tensor(GL), torch.tensor(HL))) +
+                             float(p.calc_gain(torch.tensor(GR), torch.tensor(HR))) - parent)
+                    else:
+                        gl, wl = p.side_gain_bounded(GL, HL, lo, hi)
+                        gr, wr = p.side_gain_bounded(GR, HR, lo, hi)
+                        c = int(mono[f])
+                        if (c > 0 and wl > wr) or (c < 0 and wl < wr):
+                            continue
+                        g = gl + gr - parent
+                    if g > best[0]:
+                        best = (g, f, b, d, GL, HL)
+        res[s_] = torch.tensor(best, dtype=torch.float64)
+    return res
+
+
+def child_bounds(c, lo, hi, wl, wr):
+    """The weight intervals of an accepted split's children ((lo, hi) left,
+    (lo, hi) right): its feature's constraint c cuts the node's interval at
+    the mean of the (clamped) child weights."""
+    mid = (wl + wr) / 2
+    if c > 0:
+        return (lo, mid), (mid, hi)
+    if c < 0:
+        return (mid, hi), (lo, mid)
+    return (lo, hi), (lo, hi)
 
 
 def partition_ref(ridx, node_feat, node_bin, node_defl, seg_beg, seg_end, local_bin):
@@ -223,6 +309,15 @@ class _LevelGrower:
         self._pending = None  # the deferred device tree whose host lists are still to build
         self._qscale = None  # this tree's fixed-point histogram scales (GPU)
         self._cut_lists = (cuts.values.tolist(), cuts.offsets.tolist())
+        # monotone_constraints: int8 [F] (host), None when not set; _mono_dev
+        # is the device copy the kernels read
+        self.mono = param.monotone_vector(self.F)
+        self._mono_dev = None
+
+    def _mono(self):
+        if self.mono is not None and self._mono_dev is None:
+            self._mono_dev = self.mono.to(self.device).contiguous()
+        return self._mono_dev
 
     def _draw_features(self, gen):
         """colsample_bytree: the bool mask [F] of this tree's candidate
@@ -283,6 +378,9 @@ class _LevelGrower:
         tot = gpair_stats(gpair)[0] if n else torch.zeros(2, dtype=torch.float64, device=dev)
         self.bsp.allreduce(tot)
         totals = {root: tot.cpu()}
+        # monotone_constraints: every node's weight interval, beside its totals
+        inf = float("inf")
+        bounds = {root: (-inf, inf)} if self.mono is not None else None
         seg = {root: (0, n)}
         done = {}  # finished leaves -> their final ridx segment
         if self.gpu:
@@ -297,14 +395,18 @@ class _LevelGrower:
             for nd in frontier:
                 G, H = float(totals[nd][0]), float(totals[nd][1])
                 tree.cover[nd] = H
-                tree.base_weight[nd] = p.calc_weight(G, H)
+                tree.base_weight[nd] = (p.calc_weight(G, H) if bounds is None else
+                                        p.calc_weight_bounded(G, H, *bounds[nd]))
                 tree.leaf[nd] = p.eta * tree.base_weight[nd]
             if depth == p.max_depth:
                 break
             S = len(frontier)
             H_all = H_front
             T_all = _h2d(torch.stack([totals[nd] for nd in frontier]), H_all.device)
-            bg, bf, bb, bd, bL = split_fields(self._find_splits(H_all, T_all))
+            B_all = None
+            if bounds is not None:
+                B_all = torch.tensor([bounds[nd] for nd in frontier], dtype=torch.float64)
+            bg, bf, bb, bd, bL = split_fields(self._find_splits(H_all, T_all, B_all))
             split_nodes = []
             for k, nd in enumerate(frontier):
                 if float(bg[k]) > RT_EPS:
@@ -318,6 +420,11 @@ class _LevelGrower:
                     tree.left[nd], tree.right[nd] = l, r
                     totals[l] = bL[k].double()
                     totals[r] = (totals[nd] - bL[k]).double()
+                    if bounds is not None:
+                        lo, hi = bounds[nd]
+                        wl = p.calc_weight_bounded(float(totals[l][0]), float(totals[l][1]), lo, hi)
+                        wr = p.calc_weight_bounded(float(totals[r][0]), float(totals[r][1]), lo, hi)
+                        bounds[l], bounds[r] = child_bounds(int(self.mono[f]), lo, hi, wl, wr)
                     split_nodes.append(nd)
             if not split_nodes:
                 break
@@ -369,7 +476,8 @@ class _LevelGrower:
             sil = small_is_left.view(-1, *([1] * (hsmall.dim() - 1)))
             hl = torch.where(sil, hsmall, hbig)
             hr = torch.where(sil, hbig, hsmall)
-            H_front = torch.stack([hl, hr], 1).reshape(-1, *H_front.shape[1:])
+            # (a rank that owns no feature of a sharded exchange holds [S, 0, ...])
+            H_front = torch.stack([hl, hr], 1).reshape(2 * len(split_nodes), *H_front.shape[1:])
             frontier = new_frontier
         # margins of the training rows from the final leaf segments
         done.update(seg)
@@ -591,15 +699,19 @@ class TreeBuilder(_LevelGrower):
         return hist
 
     # -------------------------------------------------------- split search
-    def _find_splits(self, hist, totals):
+    def _find_splits(self, hist, totals, bounds=None):
         """hist [S, F, nbin, 2] (global); totals [S, 2] -> the host split
         table. With a feature-sharded exchange, hist holds this rank's feature
-        slice only: the local best goes through :meth:`HistExchange.pick`."""
+        slice only: the local best goes through :meth:`HistExchange.pick`.
+        bounds [S, 2]: the slots' weight intervals under monotone_constraints
+        (the same on every rank: each derives them from the picked table)."""
         x = self.xchg
+        mono = self._mono() if bounds is not None else None
         if x is None:
-            return find_splits(self.p, hist, totals, self._valid())
+            return find_splits(self.p, hist, totals, self._valid(), mono, bounds)
         if x.hi > x.lo:
-            cand = find_splits(self.p, hist, totals, self._valid()[x.lo:x.hi])
+            cand = find_splits(self.p, hist, totals, self._valid()[x.lo:x.hi],
+                               mono[x.lo:x.hi] if mono is not None else None, bounds)
             cand[:, 1] += x.lo  # global feature ids
         else:  # (more ranks than features: this rank owns none)
             cand = torch.zeros(hist.shape[0], 6, dtype=torch.float64)
@@ -626,7 +738,7 @@ class TreeBuilder(_LevelGrower):
                   max_fcnt=self.max_fcnt, cut_vals=self._cut_lists[0],
                   cut_off=self._cut_lists[1], eta=float(p.eta), alpha=float(p.alpha),
                   reg_lambda=float(p.reg_lambda), min_child_weight=float(p.min_child_weight),
-                  max_depth=int(p.max_depth), rt_eps=RT_EPS, allreduce=ar)
+                  max_depth=int(p.max_depth), rt_eps=RT_EPS, allreduce=ar, mono=self._mono())
         # deferred: the tree stays a device node table, the margins are
         # walked from it on the device, and its host lists are built one tree
         # later (no GPU idle between trees); needs the row walk and no
@@ -711,40 +823,17 @@ class CSRTreeBuilder(_LevelGrower):
                 hist[sl, :, c].index_add_(0, gb, gh[:, c])
         return hist
 
-    def _find_splits(self, hist, totals):
+    def _find_splits(self, hist, totals, bounds=None):
         p = self.p
+        mono = self._mono() if bounds is not None else None
         if self.gpu:
+            if bounds is not None:
+                bounds = bounds.to(self.device).double().contiguous()
             return _native.hip().gbdt_split_csr(hist.contiguous(), totals.double().contiguous(),
                                                 self.cut_off, self.fvalid, float(p.alpha),
-                                                float(p.reg_lambda),
-                                                float(p.min_child_weight)).cpu()
-        # reference: per feature scans over its compact bins
-        o = self._cut_lists[1]
-        S = hist.shape[0]
-        res = torch.zeros(S, 6, dtype=torch.float64)
-        for s_ in range(S):
-            TG, TH = float(totals[s_, 0]), float(totals[s_, 1])
-            parent = float(p.calc_gain(torch.tensor(TG), torch.tensor(TH)))
-            best = (-float("inf"), 0, 0, 0, 0.0, 0.0)
-            for f in range(self.F):
-                if o[f + 1] <= o[f] or (self.fvalid is not None and not int(self.fvalid[f])):
-                    continue
-                hb = hist[s_, o[f]:o[f + 1]]
-                cum = hb.cumsum(0)
-                mg, mh = TG - float(cum[-1, 0]), TH - float(cum[-1, 1])
-                for b in range(hb.shape[0]):
-                    for d in (0, 1):
-                        GL = float(cum[b, 0]) + (mg if d else 0.0)
-                        HL = float(cum[b, 1]) + (mh if d else 0.0)
-                        GR, HR = TG - GL, TH - HL
-                        if not (HL >= p.min_child_weight and HR >= p.min_child_weight):
-                            continue
-                        g = (float(p.calc_gain(torch.tensor(GL), torch.tensor(HL))) +
-                             float(p.calc_gain(torch.tensor(GR), torch.tensor(HR))) - parent)
-                        if g > best[0]:
-                            best = (g, f, b, d, GL, HL)
-            res[s_] = torch.tensor(best, dtype=torch.float64)
-        return res
+                                                float(p.reg_lambda), float(p.min_child_weight),
+                                                mono=mono, bounds=bounds).cpu()
+        return find_splits_csr_ref(p, hist, totals, self._cut_lists[1], self.fvalid, mono, bounds)
 
     def _local_bin(self, f, rows):
         lb = torch.full((self.dm.n,), MISSING_BIN, dtype=torch.long)

@@ -31,11 +31,14 @@ class GBDTParam:
         self.num_class = 0  # multi:softmax / multi:softprob: classes (trees per round)
         self.eval_metric = []
         self.silent = 0
+        self.monotone = []  # monotone_constraints: -1 | 0 | 1 per feature id (rest: 0)
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
         if name == "lambda":
             self.reg_lambda = float(val)
+        elif name == "monotone_constraints":
+            self.monotone = parse_monotone(val)
         elif name in ("eta", "gamma", "min_child_weight", "alpha", "base_score", "subsample",
                       "colsample_bytree"):
             setattr(self, name, float(val))
@@ -61,6 +64,63 @@ class GBDTParam:
         if self.alpha > 0:
             g = G - self.alpha if G > self.alpha else (G + self.alpha if G < -self.alpha else 0.0)
         return -g / (H + self.reg_lambda)
+
+    # ---- monotone_constraints: a node's weight is clamped to its interval
+    # (lo, hi); a side whose weight is clamped scores -(2 T(G) w + (H + lambda)
+    # w w), an unclamped one keeps the closed form above, evaluated as above
+    # (so infinite bounds change nothing). Every path -- these, the host
+    # grower, the kernels -- evaluates the same operations in the same order.
+    def monotone_vector(self, F):
+        """The constraints of F features, zero-padded -> int8 [F], or None
+        when monotone_constraints is not set."""
+        if not self.monotone:
+            return None
+        if len(self.monotone) > F:
+            raise SystemExit("monotone_constraints has %d entries, the data has %d features"
+                             % (len(self.monotone), F))
+        return torch.tensor(self.monotone + [0] * (F - len(self.monotone)), dtype=torch.int8)
+
+    def calc_weight_bounded(self, G, H, lo, hi):
+        """:meth:`calc_weight` clamped to [lo, hi] (floats)."""
+        w = self.calc_weight(G, H)
+        return lo if w < lo else (hi if w > hi else w)
+
+    def side_gain_bounded(self, G, H, lo, hi):
+        """(gain, weight) of one side under the bounds, in floats."""
+        w0 = self.calc_weight(G, H)
+        w = lo if w0 < lo else (hi if w0 > hi else w0)
+        g = G
+        if self.alpha > 0:
+            g = G - self.alpha if G > self.alpha else (G + self.alpha if G < -self.alpha else 0.0)
+        d = H + self.reg_lambda
+        if w == w0:
+            return (0.0 if H < self.min_child_weight else g * g / d), w
+        return -(2.0 * g * w + d * w * w), w
+
+    def calc_gain_bounded(self, G, H, lo, hi):
+        """:meth:`calc_gain` under the bounds, on tensors -> (gain, weight)."""
+        g = _threshold_l1(G, self.alpha)
+        d = H + self.reg_lambda
+        w0 = torch.where(H < self.min_child_weight, torch.zeros_like(d), -g / d)
+        w = torch.where(w0 < lo, lo, torch.where(w0 > hi, hi, w0))
+        return torch.where(w == w0, self.calc_gain(G, H), -(2.0 * g * w + d * w * w)), w
+
+
+def parse_monotone(val):
+    """``(1,0,-1)`` | ``1,0,-1`` (spaces and quotes allowed) -> [1, 0, -1]."""
+    s = str(val).strip()
+    if len(s) >= 2 and s[0] == s[-1] and s[0] in "\"'":
+        s = s[1:-1].strip()
+    if s.startswith("(") and s.endswith(")"):
+        s = s[1:-1]
+    out = []
+    for tok in s.split(","):
+        tok = tok.strip()
+        if tok not in ("-1", "0", "1", "+1"):
+            raise SystemExit("monotone_constraints=%s: every entry is -1, 0 or 1, got %r"
+                             % (val, tok))
+        out.append(int(tok))
+    return out
 
 
 def _threshold_l1(G, alpha):
