@@ -13,6 +13,10 @@ gradient kernel alone against its plain-torch form and the 12 K n byte floor).
 ``+`` / ``-`` / ``0`` cycled over the features (``"+-0"``: feature 0 rising,
 1 falling, 2 free, 3 rising, ...): the bounded split search and the weight
 intervals of every grower, against the same run without the option.
+
+--interaction GROUPS: train with interaction_constraints, GROUPS as the app
+takes them (``"[[0,1,2],[2,3]]"``), or ``halves``: two groups, the lower and
+the upper half of the features. Composes with --monotone.
 """
 import argparse
 import json
@@ -75,6 +79,8 @@ def main():
                     help="K > 1: multi:softprob, K trees per round (--trees counts trees)")
     ap.add_argument("--monotone", default="",
                     help='monotone_constraints as a pattern of + - 0 cycled over the features')
+    ap.add_argument("--interaction", default="",
+                    help='interaction_constraints: "[[0,1],[2,3]]", or "halves"')
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: the framework's PyTorch CPU path (anchor numbers)")
     ap.add_argument("--gpus", type=int, default=1,
@@ -109,6 +115,12 @@ def main():
         sign = {"+": "1", "-": "-1", "0": "0"}
         p.set("monotone_constraints", ",".join(sign[a.monotone[j % len(a.monotone)]]
                                                for j in range(a.features)))
+    if a.interaction:
+        h = a.features // 2
+        halves = "[[%s],[%s]]" % (",".join(map(str, range(h))),
+                                  ",".join(map(str, range(h, a.features))))
+        p.set("interaction_constraints", halves if a.interaction == "halves" else a.interaction)
+        p.interaction_vector(a.features)  # (ids past --features end the run here)
     sync()
     t_prep = time.perf_counter()
     cuts = G.Cuts.build(dm, p.max_bin, bsp)
@@ -156,6 +168,7 @@ def main():
                           "value": ntree / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
                           "ms_per_tree": 1000 * dt / ntree,
                           "trees": ntree, **extra, "monotone": a.monotone or None,
+                          "interaction": p.interaction or None,
                           "sketch_bin_s": t_prep,
                           "hist_exchange": ("feature-reduce-scatter" if tb.xchg is not None
                                             else "allreduce") if bsp.world > 1 else None,

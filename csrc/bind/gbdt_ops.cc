@@ -108,13 +108,16 @@ void gbdt_hist(const Tensor& B, int64_t nbin, const Tensor& ridx, const Tensor& 
 // GL, HL}: hist [S, F, nbin, 2], totals [S x 2] and the [F x nbin] candidate
 // mask on hist's device. False: the kernel refused (nbin > 1024 or no input).
 // monotone_constraints: mono (int8 per feature of hist, else null) and the
-// slots' weight intervals bounds [S x 2].
+// slots' weight intervals bounds [S x 2]. interaction_constraints: fmask (a
+// group bit set per feature of hist, else null) and the slots' state [S].
 bool split_search(const Tensor& hist, const double* totals, const uint8_t* valid, int S,
                   double alpha, double lambda, double mcw, const Tensor& out, hipStream_t s,
-                  const int8_t* mono = nullptr, const double* bounds = nullptr) {
+                  const int8_t* mono = nullptr, const double* bounds = nullptr,
+                  const uint64_t* fmask = nullptr, const uint64_t* state = nullptr) {
   auto cand = torch::empty({std::max<int64_t>(S * hist.size(1) * 4, 1)}, hist.options());
   return wh::gbdt_split(ptr<double>(hist), totals, valid, S, (int)hist.size(1), (int)hist.size(2),
-                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s, mono, bounds);
+                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s, mono, bounds,
+                        fmask, state);
 }
 
 // the optional (mono [F] int8, bounds [S, 2] float64) pair of a split search
@@ -131,9 +134,33 @@ void check_mono(const c10::optional<Tensor>& mono, const c10::optional<Tensor>& 
   TORCH_CHECK(bounds->numel() == 2 * S, "bounds must be [S, 2]");
 }
 
+// the optional (fmask [F], state [S]) pair of a split search on `like`'s
+// device, int64 bit patterns (host/gbdt_level_plan.h): both or neither
+void check_inter(const c10::optional<Tensor>& fmask, const c10::optional<Tensor>& state,
+                 const Tensor& like, int64_t S, int64_t F) {
+  TORCH_CHECK(fmask.has_value() == state.has_value(), "fmask and state go together");
+  if (!fmask.has_value()) return;
+  CHECK_IN(*fmask, torch::kInt64);
+  CHECK_IN(*state, torch::kInt64);
+  TORCH_CHECK(fmask->device() == like.device() && state->device() == like.device(),
+              "fmask / state on another device");
+  TORCH_CHECK(fmask->numel() == F, "fmask must be [F]");
+  TORCH_CHECK(state->numel() == S, "state must be [S]");
+}
+
+// the feature masks of a grower: int64 [F] on B's device, or null
+const uint64_t* grower_fmask(const c10::optional<Tensor>& fmask, const Tensor& B, int F) {
+  if (!present(fmask)) return nullptr;
+  CHECK_IN(*fmask, torch::kInt64);
+  TORCH_CHECK(fmask->numel() == F && fmask->device() == B.device(),
+              "fmask must be [F] on B's device");
+  return optptr<uint64_t>(fmask);
+}
+
 Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid, double alpha,
                   double lambda, double min_child_weight, const c10::optional<Tensor>& mono,
-                  const c10::optional<Tensor>& bounds) {
+                  const c10::optional<Tensor>& bounds, const c10::optional<Tensor>& fmask,
+                  const c10::optional<Tensor>& state) {
   CHECK_IN(hist, torch::kFloat64);
   CHECK_IN(totals, torch::kFloat64);
   CHECK_IN(valid, torch::kBool);
@@ -144,9 +171,11 @@ Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid,
   TORCH_CHECK(valid.numel() == (int64_t)F * nbin, "valid must be [F, nbin]");
   auto out = torch::empty({S, 6}, hist.options());
   check_mono(mono, bounds, hist, S, F);
+  check_inter(fmask, state, hist, S, F);
   TORCH_CHECK(split_search(hist, ptr<double>(totals), ptr<uint8_t>(valid), S, alpha, lambda,
                            min_child_weight, out, cur_stream(hist), optptr<int8_t>(mono),
-                           optptr<double>(bounds)),
+                           optptr<double>(bounds), optptr<uint64_t>(fmask),
+                           optptr<uint64_t>(state)),
               "gbdt_split: nbin > 1024 or empty input");
   return out;
 }
@@ -396,7 +425,8 @@ Tensor gbdt_hist_csr(const Tensor& row_off, const Tensor& gbin, const Tensor& ri
 
 Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cut_off,
                       const c10::optional<Tensor>& fvalid, double alpha, double lambda, double mcw,
-                      const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds) {
+                      const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds,
+                      const c10::optional<Tensor>& fmask, const c10::optional<Tensor>& state) {
   CHECK_IN(hist, torch::kFloat64);
   CHECK_IN(totals, torch::kFloat64);
   CHECK_IN(cut_off, torch::kInt32);
@@ -406,10 +436,11 @@ Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cu
   auto out = torch::empty({S, 6}, hist.options());
   auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 5, 1)}, hist.options());
   check_mono(mono, bounds, hist, S, F);
+  check_inter(fmask, state, hist, S, F);
   wh::gbdt_split_csr(ptr<double>(hist), hist.size(1), ptr<double>(totals), ptr<int32_t>(cut_off),
                      optptr<uint8_t>(fvalid), S, F, alpha, lambda, mcw, ptr<double>(cand),
                      ptr<double>(out), cur_stream(hist), optptr<int8_t>(mono),
-                     optptr<double>(bounds));
+                     optptr<double>(bounds), optptr<uint64_t>(fmask), optptr<uint64_t>(state));
   return out;
 }
 
@@ -1060,7 +1091,7 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
                     std::vector<double> root_tot, std::vector<float> cut_vals,
                     std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
                     double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
-                    const c10::optional<Tensor>& mono) {
+                    const c10::optional<Tensor>& mono, const c10::optional<Tensor>& fmask) {
   const GrowCtx cx(B, Bc, ridx0, gpair, qscale, valid, nbin, fgroups, max_fcnt);
   c10::DeviceGuard g(B.device());
   const auto s = cx.s;
@@ -1079,12 +1110,26 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     auto mh = mono->cpu();
     mono_h.assign(mh.data_ptr<int8_t>(), mh.data_ptr<int8_t>() + F);
   }
+  // interaction_constraints: the features' group bit sets on the device (the
+  // split search) and on the host (the children's states), and every node's
+  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
+  const bool inter_on = d_fmask != nullptr;
+  std::vector<uint64_t> fmask_h;
+  if (inter_on) {
+    auto fh = fmask->cpu();
+    const auto* q = reinterpret_cast<const uint64_t*>(fh.data_ptr<int64_t>());
+    fmask_h.assign(q, q + F);
+  }
   const double inf = std::numeric_limits<double>::infinity();
   // host tree
   TreeLists t;
   std::vector<std::array<double, 2>> tot;
   std::vector<wh::GbdtBounds> bnd;
-  auto add = [&](int par) { return tot.push_back({0, 0}), bnd.push_back({-inf, inf}), t.add(par); };
+  std::vector<uint64_t> state;
+  auto add = [&](int par) {
+    return tot.push_back({0, 0}), bnd.push_back({-inf, inf}), state.push_back(wh::kGbdtInterRoot),
+           t.add(par);
+  };
   auto weight0 = [&](double G_, double H_) {
     return H_ < mcw ? 0.0 : -l1_threshold(G_, alpha) / (H_ + lambda);
   };
@@ -1157,19 +1202,25 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     const bool last = depth == max_depth;
     Tensor split_out;
     if (!last) {
-      // totals [S x 2], then (constraints) the weight intervals [S x 2]
-      const int nb = mono_on ? 2 : 1;
-      double* th = up.get<double>(2 * S * nb);
+      // 8-byte words: totals [S x 2], then (constraints) the weight intervals
+      // [S x 2], then the group sets [S]
+      const int w_bnd = 2 * S, w_state = w_bnd + (mono_on ? 2 * S : 0);
+      const int nw = w_state + (inter_on ? S : 0);
+      double* th = up.get<double>(nw);
       for (int k = 0; k < S; ++k) th[2 * k] = tot[frontier[k]][0], th[2 * k + 1] = tot[frontier[k]][1];
       if (mono_on)
         for (int k = 0; k < S; ++k)
-          th[2 * S + 2 * k] = bnd[frontier[k]][0], th[2 * S + 2 * k + 1] = bnd[frontier[k]][1];
-      auto T = up.tensor().narrow(0, 0, 16 * S * nb).to(B.device(), true).view(torch::kFloat64);
+          th[w_bnd + 2 * k] = bnd[frontier[k]][0], th[w_bnd + 2 * k + 1] = bnd[frontier[k]][1];
+      if (inter_on)
+        for (int k = 0; k < S; ++k) std::memcpy(th + w_state + k, &state[frontier[k]], 8);
+      auto T = up.tensor().narrow(0, 0, 8 * (int64_t)nw).to(B.device(), true).view(torch::kFloat64);
       up.mark(s);
       split_out = torch::empty({S, 6}, f64);
       TORCH_CHECK(split_search(H_front, ptr<double>(T), ptr<uint8_t>(valid), S, alpha, lambda, mcw,
                                split_out, s, optptr<int8_t>(mono),
-                               mono_on ? ptr<double>(T) + 2 * S : nullptr),
+                               mono_on ? ptr<double>(T) + w_bnd : nullptr, d_fmask,
+                               inter_on ? reinterpret_cast<const uint64_t*>(ptr<double>(T) + w_state)
+                                        : nullptr),
                   "gbdt_split failed");
     }
     // the level's one synchronisation: split results + previous partition counts
@@ -1206,6 +1257,7 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
             wh::gbdt_clamp_weight(weight0(tot[r][0], tot[r][1]), pb));
         bnd[l] = cb[0], bnd[r] = cb[1];
       }
+      if (inter_on) state[l] = state[r] = wh::gbdt_child_state(state[nd], fmask_h[f]);
       split_k.push_back(k);
     }
     if (split_k.empty()) break;
@@ -1376,7 +1428,8 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                         std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
                         double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
                         py::object reduce_scatter, py::object pick, int64_t f_lo, bool walk,
-                        bool defer, const c10::optional<Tensor>& mono) {
+                        bool defer, const c10::optional<Tensor>& mono,
+                        const c10::optional<Tensor>& fmask) {
   // Multi-rank: either every level's built histograms are allreduced (all
   // features on every rank), or -- reduce_scatter / pick given
   // (models/gbdt.py HistExchange) -- each rank receives the global sums of
@@ -1411,6 +1464,13 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     bounds_cur.select(1, 0).fill_(-inf);
     bounds_cur.select(1, 1).fill_(inf);
   }
+  // interaction_constraints: fmask [F] int64 (all features, as mono) and the
+  // slots' group sets, ping-ponged like the weight intervals
+  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
+  const bool inter_on = d_fmask != nullptr;
+  const auto i64 = f64.dtype(torch::kInt64);
+  Tensor state_cur;
+  if (inter_on) state_cur = torch::full({1}, (int64_t)wh::kGbdtInterRoot, i64);
   const bool reduce = shard || !allreduce.is_none();
   // rank partials -> global sums: all features, or this rank's slice
   auto reduce_hist = [&](Tensor h) -> Tensor {
@@ -1482,7 +1542,9 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
       if (Fl > 0) {
         TORCH_CHECK(split_search(H_front, ptr<double>(tot_cur), vp + (int64_t)f_lo * nbin, S, alpha,
                                  lambda, mcw, so, s, mono_on ? d_mono + f_lo : nullptr,
-                                 mono_on ? ptr<double>(bounds_cur) : nullptr),
+                                 mono_on ? ptr<double>(bounds_cur) : nullptr,
+                                 inter_on ? d_fmask + f_lo : nullptr,
+                                 inter_on ? ptr<uint64_t>(state_cur) : nullptr),
                     "gbdt_split failed");
       } else {  // (more ranks than features: this rank owns none)
         so.zero_();
@@ -1499,6 +1561,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     auto pb = torch::empty({3 * S}, u8);   // pdefl | split | build_left
     Tensor tot_next = last ? Tensor() : torch::empty({2 * S, 2}, f64);
     Tensor bounds_next = last || !mono_on ? Tensor() : torch::empty({2 * S, 2}, f64);
+    Tensor state_next = last || !inter_on ? Tensor() : torch::empty({2 * S}, i64);
     int32_t* pfeat = ptr<int32_t>(pi);
     uint8_t* pdefl = ptr<uint8_t>(pb);
     wh::gbdt_dev_apply(S, S - 1, last, last ? nullptr : ptr<double>(so), ptr<double>(tot_cur),
@@ -1507,7 +1570,9 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                        pfeat + 3 * S, pdefl + S, pdefl + 2 * S,
                        last ? nullptr : ptr<double>(tot_next), nullptr, s, d_mono,
                        mono_on ? ptr<double>(bounds_cur) : nullptr,
-                       bounds_next.defined() ? ptr<double>(bounds_next) : nullptr);
+                       bounds_next.defined() ? ptr<double>(bounds_next) : nullptr, d_fmask,
+                       inter_on ? ptr<uint64_t>(state_cur) : nullptr,
+                       state_next.defined() ? ptr<uint64_t>(state_next) : nullptr);
     if (last) break;
     // walk: the caller adds the leaf values by walking the tree over each
     // row's bins (models/gbdt.py _finish), so the level whose children are
@@ -1543,6 +1608,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     if (leaves_next) {  // (leaf segments: left child empty -- unused by the walk)
       tot_cur = tot_next;
       bounds_cur = bounds_next;
+      state_cur = state_next;
       seg_cur = seg_next;
       alive_cur = alive_next;
       continue;
@@ -1565,6 +1631,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
     H_front = H_next;
     tot_cur = tot_next;
     bounds_cur = bounds_next;
+    state_cur = state_next;
     seg_cur = seg_next;
     alive_cur = alive_next;
   }
@@ -1589,7 +1656,8 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_seg_fill", &gbdt_seg_fill);
   m.def("gbdt_split", &gbdt_split, py::arg("hist"), py::arg("totals"), py::arg("valid"),
         py::arg("alpha"), py::arg("reg_lambda"), py::arg("min_child_weight"),
-        py::arg("mono") = py::none(), py::arg("bounds") = py::none());
+        py::arg("mono") = py::none(), py::arg("bounds") = py::none(),
+        py::arg("fmask") = py::none(), py::arg("state") = py::none());
   m.def("gbdt_leaf_add", &gbdt_leaf_add);
   m.def("gbdt_leaf_walk", &gbdt_leaf_walk, py::arg("B"), py::arg("feat"), py::arg("bin"),
         py::arg("defl"), py::arg("left"), py::arg("right"), py::arg("val"), py::arg("margin"),
@@ -1602,14 +1670,14 @@ void bind_gbdt(py::module_& m) {
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
-        py::arg("allreduce"), py::arg("mono") = py::none());
+        py::arg("allreduce"), py::arg("mono") = py::none(), py::arg("fmask") = py::none());
   m.def("gbdt_grow_dev", &gbdt_grow_dev, py::arg("B"), py::arg("Bc"), py::arg("ridx0"), py::arg("gpair"),
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
         py::arg("allreduce"), py::arg("reduce_scatter") = py::none(), py::arg("pick") = py::none(),
         py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false,
-        py::arg("mono") = py::none());
+        py::arg("mono") = py::none(), py::arg("fmask") = py::none());
   m.def("gbdt_tree_from_nodes", &gbdt_tree_from_nodes);
   m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
         py::arg("lds") = true);
@@ -1622,7 +1690,8 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_hist_csr", &gbdt_hist_csr);
   m.def("gbdt_split_csr", &gbdt_split_csr, py::arg("hist"), py::arg("totals"), py::arg("cut_off"),
         py::arg("fvalid"), py::arg("alpha"), py::arg("reg_lambda"), py::arg("min_child_weight"),
-        py::arg("mono") = py::none(), py::arg("bounds") = py::none());
+        py::arg("mono") = py::none(), py::arg("bounds") = py::none(),
+        py::arg("fmask") = py::none(), py::arg("state") = py::none());
   m.def("gbdt_partition_csr", &gbdt_partition_csr);
   m.def("gbdt_predict_csr", &gbdt_predict_csr);
   // forest prediction: pack, plan and the capacity need no GPU

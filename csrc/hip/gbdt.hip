@@ -1264,6 +1264,18 @@ __device__ __forceinline__ double gbdt_weight0(double G, double H, double alpha,
   return H >= mcw ? -gbdt_l1(G, alpha) / (H + lambda) : 0.0;
 }
 
+// interaction_constraints: a slot may split on a feature iff their group bit
+// sets (host/gbdt_level_plan.h) share a bit.
+__device__ __forceinline__ bool gbdt_admits(uint64_t state, uint64_t fmask) {
+  return (state & fmask) != 0;
+}
+
+// (the children of a split: bit 63, the mark of a feature in no group, is
+// dropped, so nothing is admitted below a split on such a feature)
+__device__ __forceinline__ uint64_t gbdt_child_state(uint64_t state, uint64_t fmask) {
+  return state & fmask & ~(1ull << 63);
+}
+
 }  // namespace
 
 namespace wh {
@@ -1309,8 +1321,11 @@ __global__ __launch_bounds__(256) void k_heap_tree(const double* __restrict__ no
 // (monotone_constraints): the slot's weight is clamped to its interval bnd
 // [S x 2], and an accepted split's children get theirs (bnd_next [2S x 2]):
 // the interval cut at the mean of the clamped child weights, by the sign of
-// mono [split feature] (global feature ids, as in `so`).
-template <bool MONO>
+// mono [split feature] (global feature ids, as in `so`). INTER
+// (interaction_constraints): an accepted split's children get the slot's
+// group set narrowed by the split feature's (state_next [2S]; 0 below a slot
+// that stays a leaf), again by global feature id.
+template <bool MONO, bool INTER>
 __device__ __forceinline__ void gd_apply(
     int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
     const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
@@ -1319,7 +1334,8 @@ __device__ __forceinline__ void gd_apply(
     int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
     uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
     const int8_t* __restrict__ mono, const double* __restrict__ bnd,
-    double* __restrict__ bnd_next) {
+    double* __restrict__ bnd_next, const uint64_t* __restrict__ fmask,
+    const uint64_t* __restrict__ state, uint64_t* __restrict__ state_next) {
   for (int sl = threadIdx.x; sl < S; sl += blockDim.x) {
     if (nleft) nleft[sl] = 0;  // the partition's left counts (no memset launch)
     const double G = tot[2 * sl], H = tot[2 * sl + 1];
@@ -1377,6 +1393,11 @@ __device__ __forceinline__ void gd_apply(
       bnd_next[4 * sl + 2] = rlo;
       bnd_next[4 * sl + 3] = rhi;
     }
+    if (INTER && state_next) {
+      const uint64_t c = sp ? gbdt_child_state(state[sl], fmask[(int32_t)o[1]]) : 0;
+      state_next[2 * sl] = c;
+      state_next[2 * sl + 1] = c;
+    }
   }
 }
 
@@ -1388,9 +1409,9 @@ __global__ __launch_bounds__(256) void k_gd_apply(
     int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
     int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
     uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft) {
-  gd_apply<false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat,
-                  pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr, nullptr,
-                  nullptr);
+  gd_apply<false, false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
+                         pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr,
+                         nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(256) void k_gd_apply_mono(
@@ -1402,8 +1423,38 @@ __global__ __launch_bounds__(256) void k_gd_apply_mono(
     uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
     const int8_t* __restrict__ mono, const double* __restrict__ bnd,
     double* __restrict__ bnd_next) {
-  gd_apply<true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat,
-                 pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next);
+  gd_apply<true, false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
+                        pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd,
+                        bnd_next, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_gd_apply_inter(
+    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
+    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
+    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
+    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
+    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
+    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
+    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state,
+    uint64_t* __restrict__ state_next) {
+  gd_apply<false, true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
+                        pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr,
+                        nullptr, nullptr, fmask, state, state_next);
+}
+
+__global__ __launch_bounds__(256) void k_gd_apply_mono_inter(
+    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
+    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
+    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
+    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
+    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
+    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
+    const int8_t* __restrict__ mono, const double* __restrict__ bnd,
+    double* __restrict__ bnd_next, const uint64_t* __restrict__ fmask,
+    const uint64_t* __restrict__ state, uint64_t* __restrict__ state_next) {
+  gd_apply<true, true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
+                       pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd,
+                       bnd_next, fmask, state, state_next);
 }
 
 // One block (S <= 1024 slots): the next level's segments / alive flags, the
@@ -1511,8 +1562,18 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     double lambda, double mcw, double rt_eps, double* nodes, int32_t* pfeat,
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
                     uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
-                    const int8_t* mono, const double* bnd, double* bnd_next) {
-  if (mono)
+                    const int8_t* mono, const double* bnd, double* bnd_next,
+                    const uint64_t* fmask, const uint64_t* state, uint64_t* state_next) {
+  if (fmask && mono)
+    hipLaunchKernelGGL(k_gd_apply_mono_inter, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so,
+                       tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl,
+                       lcur, rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next, fmask,
+                       state, state_next);
+  else if (fmask)
+    hipLaunchKernelGGL(k_gd_apply_inter, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot,
+                       seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur,
+                       rcur, split, build_left, tot_next, nleft, fmask, state, state_next);
+  else if (mono)
     hipLaunchKernelGGL(k_gd_apply_mono, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot,
                        seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur,
                        rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next);
@@ -1607,13 +1668,29 @@ __device__ __forceinline__ bool better(double g, long long i, double bg, long lo
 // MONO: mono [F] (int8: -1 | 0 | 1) and the slots' weight intervals bounds
 // [S x 2]; a rejected candidate has gain -inf and never wins (better() needs a
 // larger gain, and an all -inf block keeps its initial index).
-template <bool MONO>
+// INTER (interaction_constraints): fmask [F] are the features' group bit sets
+// and state [S] the slots'; a block whose (slot, feature) is not admitted
+// (gbdt_admits) writes the record of an all -inf block and returns before it
+// reads its histogram. The test is the same in every thread of the block, so
+// the barriers below are reached by all of them or by none.
+template <bool MONO, bool INTER>
 __device__ __forceinline__ void split_feat(
     const double* __restrict__ hist, const double* __restrict__ totals,
     const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
-    const int8_t* __restrict__ mono, const double* __restrict__ bounds) {
+    const int8_t* __restrict__ mono, const double* __restrict__ bounds,
+    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
   const int s = blockIdx.x / F, f = blockIdx.x % F;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (INTER && !gbdt_admits(state[s], fmask[f])) {
+    if (t == 0) {
+      double* c = cand + ((int64_t)s * F + f) * 4;
+      c[0] = -INFINITY;
+      c[1] = (double)0x7fffffffffffffffll;
+      c[2] = 0.0;
+      c[3] = 0.0;
+    }
+    return;
+  }
   const double* hb = hist + ((int64_t)s * F + f) * nbin * 2;
   const int per = (nbin + kSplitThreads - 1) / kSplitThreads;
   double lg[kSplitMaxPer], lh[kSplitMaxPer];
@@ -1730,14 +1807,30 @@ __device__ __forceinline__ void split_feat(
 __global__ __launch_bounds__(kSplitThreads) void k_split_feat(
     const double* __restrict__ hist, const double* __restrict__ totals,
     const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand) {
-  split_feat<false>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr);
+  split_feat<false, false>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr, nullptr,
+                           nullptr);
 }
 
 __global__ __launch_bounds__(kSplitThreads) void k_split_feat_mono(
     const double* __restrict__ hist, const double* __restrict__ totals,
     const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
     const int8_t* __restrict__ mono, const double* __restrict__ bounds) {
-  split_feat<true>(hist, totals, valid, F, nbin, p, cand, mono, bounds);
+  split_feat<true, false>(hist, totals, valid, F, nbin, p, cand, mono, bounds, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kSplitThreads) void k_split_feat_inter(
+    const double* __restrict__ hist, const double* __restrict__ totals,
+    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
+    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
+  split_feat<false, true>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr, fmask, state);
+}
+
+__global__ __launch_bounds__(kSplitThreads) void k_split_feat_mono_inter(
+    const double* __restrict__ hist, const double* __restrict__ totals,
+    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
+    const int8_t* __restrict__ mono, const double* __restrict__ bounds,
+    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
+  split_feat<true, true>(hist, totals, valid, F, nbin, p, cand, mono, bounds, fmask, state);
 }
 
 __global__ __launch_bounds__(64) void k_split_node(const double* __restrict__ cand, int F,
@@ -1785,10 +1878,17 @@ namespace wh {
 
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s, const int8_t* mono, const double* bounds) {
+                hipStream_t s, const int8_t* mono, const double* bounds, const uint64_t* fmask,
+                const uint64_t* state) {
   if (nbin > kSplitThreads * kSplitMaxPer || S <= 0 || F <= 0) return false;
   const SplitParam p{alpha, lambda, mcw};
-  if (mono)
+  if (fmask && mono)
+    hipLaunchKernelGGL(k_split_feat_mono_inter, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s,
+                       hist, totals, valid, F, nbin, p, cand, mono, bounds, fmask, state);
+  else if (fmask)
+    hipLaunchKernelGGL(k_split_feat_inter, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
+                       totals, valid, F, nbin, p, cand, fmask, state);
+  else if (mono)
     hipLaunchKernelGGL(k_split_feat_mono, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
                        totals, valid, F, nbin, p, cand, mono, bounds);
   else
@@ -1867,15 +1967,18 @@ __global__ void k_hist_csr_fin(const unsigned long long* __restrict__ q, int64_t
 // best split per (node, feature): one thread walks the feature's bins; then
 // per node the best feature (ties: smallest (feature, bin, dir) as dense).
 // cand [S][F] = {gain, bin, dir, GL, HL}
-// (MONO: as k_split_feat)
-template <bool MONO>
+// (MONO, INTER: as k_split_feat; a thread whose (slot, feature) is not
+// admitted writes the record of a feature without candidates)
+template <bool MONO, bool INTER>
 __device__ __forceinline__ void split_csr_feat(const double* __restrict__ hist, int64_t tb,
                                                const double* __restrict__ totals,
                                                const int32_t* __restrict__ cut_off,
                                                const uint8_t* __restrict__ fvalid, int F,
                                                SplitParam p, double* __restrict__ cand,
                                                const int8_t* __restrict__ mono,
-                                               const double* __restrict__ bounds) {
+                                               const double* __restrict__ bounds,
+                                               const uint64_t* __restrict__ fmask,
+                                               const uint64_t* __restrict__ state) {
   const int s = blockIdx.y;
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= F) return;
@@ -1883,6 +1986,7 @@ __device__ __forceinline__ void split_csr_feat(const double* __restrict__ hist, 
   c[0] = -INFINITY;
   const int b0 = cut_off[f], b1 = cut_off[f + 1];
   if (b1 <= b0 || (fvalid && !fvalid[f])) return;
+  if (INTER && !gbdt_admits(state[s], fmask[f])) return;
   const double* hb = hist + (int64_t)s * tb * 2;
   const double TG = totals[2 * s], TH = totals[2 * s + 1];
   double pg = 0.0, ph = 0.0;
@@ -1921,7 +2025,8 @@ __global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
                                  const int32_t* __restrict__ cut_off,
                                  const uint8_t* __restrict__ fvalid, int F, SplitParam p,
                                  double* __restrict__ cand) {
-  split_csr_feat<false>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr);
+  split_csr_feat<false, false>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr,
+                               nullptr, nullptr);
 }
 
 __global__ void k_split_csr_feat_mono(const double* __restrict__ hist, int64_t tb,
@@ -1930,7 +2035,28 @@ __global__ void k_split_csr_feat_mono(const double* __restrict__ hist, int64_t t
                                       const uint8_t* __restrict__ fvalid, int F, SplitParam p,
                                       double* __restrict__ cand, const int8_t* __restrict__ mono,
                                       const double* __restrict__ bounds) {
-  split_csr_feat<true>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds);
+  split_csr_feat<true, false>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds, nullptr,
+                              nullptr);
+}
+
+__global__ void k_split_csr_feat_inter(const double* __restrict__ hist, int64_t tb,
+                                       const double* __restrict__ totals,
+                                       const int32_t* __restrict__ cut_off,
+                                       const uint8_t* __restrict__ fvalid, int F, SplitParam p,
+                                       double* __restrict__ cand,
+                                       const uint64_t* __restrict__ fmask,
+                                       const uint64_t* __restrict__ state) {
+  split_csr_feat<false, true>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr,
+                              fmask, state);
+}
+
+__global__ void k_split_csr_feat_mono_inter(
+    const double* __restrict__ hist, int64_t tb, const double* __restrict__ totals,
+    const int32_t* __restrict__ cut_off, const uint8_t* __restrict__ fvalid, int F, SplitParam p,
+    double* __restrict__ cand, const int8_t* __restrict__ mono, const double* __restrict__ bounds,
+    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
+  split_csr_feat<true, true>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds, fmask,
+                             state);
 }
 
 __global__ __launch_bounds__(256) void k_split_csr_node(const double* __restrict__ cand, int F,
@@ -2059,10 +2185,18 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
                     double lambda, double mcw, double* cand, double* out, hipStream_t s,
-                    const int8_t* mono, const double* bounds) {
+                    const int8_t* mono, const double* bounds, const uint64_t* fmask,
+                    const uint64_t* state) {
   if (S <= 0 || F <= 0) return;
   const SplitParam p{alpha, lambda, mcw};
-  if (mono)
+  const dim3 grid((unsigned)((F + 255) / 256), S);
+  if (fmask && mono)
+    hipLaunchKernelGGL(k_split_csr_feat_mono_inter, grid, dim3(256), 0, s, hist, tb, totals,
+                       cut_off, fvalid, F, p, cand, mono, bounds, fmask, state);
+  else if (fmask)
+    hipLaunchKernelGGL(k_split_csr_feat_inter, grid, dim3(256), 0, s, hist, tb, totals, cut_off,
+                       fvalid, F, p, cand, fmask, state);
+  else if (mono)
     hipLaunchKernelGGL(k_split_csr_feat_mono, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0,
                        s, hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds);
   else

@@ -557,10 +557,14 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
                     uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
                     const int8_t* mono = nullptr, const double* bnd = nullptr,
-                    double* bnd_next = nullptr);
+                    double* bnd_next = nullptr, const uint64_t* fmask = nullptr,
+                    const uint64_t* state = nullptr, uint64_t* state_next = nullptr);
 // (mono [F] int8, given under monotone_constraints: bnd [S x 2] are the slots'
 // weight intervals, the recorded weight is clamped to them, and bnd_next
 // [2S x 2] (optional) receives the children's)
+// (fmask [F], given under interaction_constraints: the features' group bit
+// sets (host/gbdt_level_plan.h), state [S] the slots'; state_next [2S]
+// (optional) receives the children's, gbdt_child_state by the split feature)
 // lcur: the split slots' left cursors after the partition (their left
 // children end there; = the segment begin when no partition ran)
 bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const uint8_t* build_left,
@@ -604,10 +608,14 @@ void gbdt_leaf_add(const int32_t* ridx, int64_t n, const int32_t* pos_node, cons
 // [S * F * 4] double scratch. false when nbin > 1024.
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s, const int8_t* mono = nullptr, const double* bounds = nullptr);
+                hipStream_t s, const int8_t* mono = nullptr, const double* bounds = nullptr,
+                const uint64_t* fmask = nullptr, const uint64_t* state = nullptr);
 // (mono [F] int8 in {-1, 0, 1}, given under monotone_constraints, with the
 // slots' weight intervals bounds [S x 2]: gains at the clamped weights, and a
 // candidate whose children are ordered against its feature's sign is dropped)
+// (fmask [F] and state [S], given under interaction_constraints: slot s may
+// split on feature f iff state[s] & fmask[f] != 0; a pair that may not has no
+// candidate and its histogram is not read)
 // sparse (CSR) input: global bin ids (cut_off[f] + bin, -1 = unbinned),
 // compact [slots][total bins][2] histograms (tasks [ntask x 3] = {slot,
 // rbeg, rend}, hq: int64 scratch of the histogram's size), split search over
@@ -621,7 +629,8 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
                     double lambda, double mcw, double* cand, double* out, hipStream_t s,
-                    const int8_t* mono = nullptr, const double* bounds = nullptr);
+                    const int8_t* mono = nullptr, const double* bounds = nullptr,
+                    const uint64_t* fmask = nullptr, const uint64_t* state = nullptr);
 void gbdt_goleft_csr(const int64_t* row_off, const int32_t* fid, const int32_t* gbin,
                      const int32_t* cut_off, const int32_t* ridx, int64_t n,
                      const int32_t* pos_node, const int32_t* node_feat, const int32_t* node_bin,

@@ -62,4 +62,19 @@ inline std::array<GbdtBounds, 2> gbdt_child_bounds(int c, const GbdtBounds& b, d
   return {b, b};
 }
 
+// interaction_constraints on one 64-bit word: bit i < 63 of a feature's mask
+// says that group i contains it, and a feature in no group holds bit 63 alone.
+// A node's state is the set of groups that contain every feature split on
+// above it: all ones at the root, which therefore admits every feature; a
+// node admits feature f iff state & mask[f] != 0. The children of a split on
+// f narrow the state by mask[f] and drop bit 63, so nothing is admitted below
+// a split on an ungrouped feature. The same rule as models/gbdt_objective.py
+// interaction_child and gbdt.hip k_gd_apply.
+constexpr uint64_t kGbdtInterFree = 1ull << 63;
+constexpr uint64_t kGbdtInterRoot = ~0ull;
+
+inline uint64_t gbdt_child_state(uint64_t state, uint64_t fmask) {
+  return state & fmask & ~kGbdtInterFree;
+}
+
 }  // namespace wh

@@ -10,7 +10,8 @@ objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
 gamma, min_child_weight, max_depth, lambda, alpha, base_score, max_bin,
-subsample, colsample_bytree, monotone_constraints, seed, eval_metric, num_round, save_period,
+subsample, colsample_bytree, monotone_constraints, interaction_constraints, seed,
+eval_metric, num_round, save_period,
 eval_train, eval[name]=path, data, test:data, model_in, model_out, model_dir,
 fmap, name_dump, name_pred, dump_stats, dsplit=row, dsparse (keep the rows CSR:
 wide libsvm data; default when num_feature > 4096), nthread (ignored),
@@ -46,6 +47,20 @@ right one. Rows missing x_j follow the splits' default directions and are
 outside the guarantee. Every class's trees of a multi: objective are
 constrained; the model file, task=dump, pred and eval are unchanged
 (docs/bsp_apps.md "Monotone constraints").
+
+Interaction constraints: ``interaction_constraints=[[0,1,2],[2,3,4,5]]``
+(task=train only) lists groups of feature ids, which may overlap; spaces are
+allowed, and in a conf file the value is quoted (``interaction_constraints =
+"[[0,1],[2,3]]"``); ``[]`` is off. The root of a tree may split on any
+feature; any other node may split on feature f iff one group contains f and
+every feature split on above the node, so the distinct features of a
+root-to-leaf path lie within one group. A feature in no group can be split on
+at the root only, and the children of that root are leaves. At most 63
+groups; an empty group, an id that is no non-negative integer or not below
+the data's feature count, unbalanced brackets or a 64th group end the run
+with an error. Composes with colsample_bytree and monotone_constraints;
+every class's trees of a multi: objective are constrained (docs/bsp_apps.md
+"Interaction constraints").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -332,6 +347,7 @@ def main(argv):
     ncol = int(bsp.allreduce_scalar(ncol, "max", torch.int64))
     # (the same answer on every rank, before any further collective)
     param.monotone_vector(ncol)
+    param.interaction_vector(ncol)
     dtrain = G.make_dmatrix(*train_raw, ncol=ncol, device=dev, sparse=dsparse,
                             group=load_group(data, train_raw[3].numel()))
     deval = [(name, G.make_dmatrix(*r, ncol=ncol, device=dev, sparse=dsparse,

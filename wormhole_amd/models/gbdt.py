@@ -28,9 +28,10 @@ from .. import _native
 # the family's other modules: parameters / objectives / metrics, the data
 # matrices and cuts, the trees and the model (every public name stays
 # reachable from this module)
-from .gbdt_objective import (GBDTParam, MULTI_METRICS, NLL_MAX, Objective,  # noqa: F401
-                             RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
-                             eval_metric, first_argmax, gpair_stats, multi_eval_sums,
+from .gbdt_objective import (GBDTParam, INTERACTION_FREE, INTERACTION_ROOT,  # noqa: F401
+                             MULTI_METRICS, NLL_MAX, Objective, RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
+                             eval_metric, first_argmax, gpair_stats, interaction_child,
+                             multi_eval_sums,
                              parse_rank_metric, rank_eval, rank_eval_torch, rank_gpair_torch,
                              rank_metric, softmax_gpair_torch)
 from .gbdt_data import MISSING_BIN, CSRMatrix, Cuts, DMatrix, make_dmatrix  # noqa: F401
@@ -133,7 +134,14 @@ def split_fields(t):
     return t[:, 0], t[:, 1].long(), t[:, 2].long(), t[:, 3].long(), t[:, 4:6]
 
 
-def split_gains(p, hist, totals, valid, mono=None, bounds=None):
+def admitted(fmask, state):
+    """interaction_constraints: the bool table [S, F] of the (slot, feature)
+    pairs that may split -- the slot's group set shares a bit with the
+    feature's (fmask [F], state [S]: int64 bit patterns)."""
+    return (state.to(fmask.device)[:, None] & fmask[None, :]) != 0
+
+
+def split_gains(p, hist, totals, valid, mono=None, bounds=None, fmask=None, state=None):
     """Every candidate of a level: (gain [S, F, nbin, 2 directions] with -inf
     for what is no candidate, left sums [S, F, nbin, 2 directions, 2]); the
     arguments of :func:`find_splits_ref`."""
@@ -170,17 +178,24 @@ def split_gains(p, hist, totals, valid, mono=None, bounds=None):
     # colsample_bytree, are not candidates
     gain = torch.where(valid.to(gain.device)[None, :, :, None], gain,
                        torch.full_like(gain, -float("inf")))
+    if fmask is not None:
+        adm = admitted(fmask.to(gain.device), state)
+        gain = torch.where(adm[:, :, None, None], gain, torch.full_like(gain, -float("inf")))
     return gain, torch.stack([cands[0][1], cands[1][1]], 3)
 
 
-def find_splits_ref(p, hist, totals, valid, mono=None, bounds=None):
+def find_splits_ref(p, hist, totals, valid, mono=None, bounds=None, fmask=None, state=None):
     """Parameters p; hist [S, F, nbin, 2] (global sums); totals [S, 2]; valid
     [F, nbin] bool -> the host split table: the torch reference of the fused
     kernels (and the CPU path). monotone_constraints: mono [F] int8 and the
     slots' weight intervals bounds [S, 2] (float64) -- each side's gain is
     taken at its clamped weight and a candidate whose child weights are
-    ordered against its feature's constraint is rejected."""
-    gain, Lall = split_gains(p, hist, totals, valid, mono, bounds)  # Lall [S, F, nbin, 2dir, 2]
+    ordered against its feature's constraint is rejected.
+    interaction_constraints: fmask [F] and the slots' states [S] (int64 bit
+    sets of groups) -- a (slot, feature) pair that :func:`admitted` refuses
+    has no candidate."""
+    # Lall [S, F, nbin, 2dir, 2]
+    gain, Lall = split_gains(p, hist, totals, valid, mono, bounds, fmask, state)
     S, nbin = gain.shape[0], gain.shape[2]
     flat = gain.reshape(S, -1)
     arg = flat.argmax(1)
@@ -194,7 +209,7 @@ def find_splits_ref(p, hist, totals, valid, mono=None, bounds=None):
     return split_table(bg, f, b, d, Ls).cpu()
 
 
-def find_splits(p, hist, totals, valid, mono=None, bounds=None):
+def find_splits(p, hist, totals, valid, mono=None, bounds=None, fmask=None, state=None):
     """:func:`find_splits_ref`, on the GPU by the fused split-search kernels
     (csrc/hip/gbdt.hip k_split_feat / k_split_node: scan + gain + argmax in
     two launches instead of ~40 elementwise ops per level)."""
@@ -202,19 +217,25 @@ def find_splits(p, hist, totals, valid, mono=None, bounds=None):
         if mono is not None:
             mono = mono.to(hist.device).contiguous()
             bounds = bounds.to(hist.device).double().contiguous()
+        inter = {}
+        if fmask is not None:
+            inter = dict(fmask=fmask.to(hist.device).contiguous(),
+                         state=state.to(hist.device).contiguous())
         return _native.hip().gbdt_split(hist.double().contiguous(), totals.double().contiguous(),
                                         valid.to(hist.device).contiguous(), float(p.alpha),
                                         float(p.reg_lambda), float(p.min_child_weight),
-                                        mono=mono, bounds=bounds).cpu()
-    return find_splits_ref(p, hist, totals, valid, mono, bounds)
+                                        mono=mono, bounds=bounds, **inter).cpu()
+    return find_splits_ref(p, hist, totals, valid, mono, bounds, fmask, state)
 
 
-def find_splits_csr_ref(p, hist, totals, cut_off, fvalid=None, mono=None, bounds=None):
+def find_splits_csr_ref(p, hist, totals, cut_off, fvalid=None, mono=None, bounds=None,
+                        fmask=None, state=None):
     """:func:`find_splits_ref` over compact histograms [S, total bins, 2]
     (feature f owns bins cut_off[f]:cut_off[f + 1], a list; fvalid [F]: this
     tree's candidate features, or None): the CSR builder's CPU path and the
     reference of the CSR split kernels. (Unconstrained gains are taken on
-    torch scalars, in fp32; bounded ones in Python floats.)"""
+    torch scalars, in fp32; bounded ones in Python floats.) fmask / state: as
+    :func:`find_splits_ref`."""
     o = cut_off
     S = hist.shape[0]
     res = torch.zeros(S, 6, dtype=torch.float64)
@@ -228,6 +249,8 @@ def find_splits_csr_ref(p, hist, totals, cut_off, fvalid=None, mono=None, bounds
         best = (-float("inf"), 0, 0, 0, 0.0, 0.0)
         for f in range(len(o) - 1):
             if o[f + 1] <= o[f] or (fvalid is not None and not int(fvalid[f])):
+                continue
+            if fmask is not None and not int(state[s_]) & int(fmask[f]):
                 continue
             hb = hist[s_, o[f]:o[f + 1]]
             cum = hb.cumsum(0)
@@ -313,6 +336,15 @@ class _LevelGrower:
         # is the device copy the kernels read
         self.mono = param.monotone_vector(self.F)
         self._mono_dev = None
+        # interaction_constraints: the features' group bit sets, int64 [F]
+        # (host; gbdt_objective.py interaction_vector), None when not set
+        self.fmask = param.interaction_vector(self.F)
+        self._fmask_dev = None
+
+    def _fmask(self):
+        if self.fmask is not None and self._fmask_dev is None:
+            self._fmask_dev = self.fmask.to(self.device).contiguous()
+        return self._fmask_dev
 
     def _mono(self):
         if self.mono is not None and self._mono_dev is None:
@@ -381,6 +413,9 @@ class _LevelGrower:
         # monotone_constraints: every node's weight interval, beside its totals
         inf = float("inf")
         bounds = {root: (-inf, inf)} if self.mono is not None else None
+        # interaction_constraints: every node's set of still possible groups
+        state = {root: INTERACTION_ROOT} if self.fmask is not None else None
+        fmask_h = self.fmask.tolist() if self.fmask is not None else None
         seg = {root: (0, n)}
         done = {}  # finished leaves -> their final ridx segment
         if self.gpu:
@@ -406,7 +441,12 @@ class _LevelGrower:
             B_all = None
             if bounds is not None:
                 B_all = torch.tensor([bounds[nd] for nd in frontier], dtype=torch.float64)
-            bg, bf, bb, bd, bL = split_fields(self._find_splits(H_all, T_all, B_all))
+            if state is None:
+                found = self._find_splits(H_all, T_all, B_all)
+            else:
+                S_all = torch.tensor([state[nd] for nd in frontier], dtype=torch.int64)
+                found = self._find_splits(H_all, T_all, B_all, S_all)
+            bg, bf, bb, bd, bL = split_fields(found)
             split_nodes = []
             for k, nd in enumerate(frontier):
                 if float(bg[k]) > RT_EPS:
@@ -425,6 +465,8 @@ class _LevelGrower:
                         wl = p.calc_weight_bounded(float(totals[l][0]), float(totals[l][1]), lo, hi)
                         wr = p.calc_weight_bounded(float(totals[r][0]), float(totals[r][1]), lo, hi)
                         bounds[l], bounds[r] = child_bounds(int(self.mono[f]), lo, hi, wl, wr)
+                    if state is not None:
+                        state[l] = state[r] = interaction_child(state[nd], fmask_h[f])
                     split_nodes.append(nd)
             if not split_nodes:
                 break
@@ -699,19 +741,22 @@ class TreeBuilder(_LevelGrower):
         return hist
 
     # -------------------------------------------------------- split search
-    def _find_splits(self, hist, totals, bounds=None):
+    def _find_splits(self, hist, totals, bounds=None, state=None):
         """hist [S, F, nbin, 2] (global); totals [S, 2] -> the host split
         table. With a feature-sharded exchange, hist holds this rank's feature
         slice only: the local best goes through :meth:`HistExchange.pick`.
-        bounds [S, 2]: the slots' weight intervals under monotone_constraints
-        (the same on every rank: each derives them from the picked table)."""
+        bounds [S, 2]: the slots' weight intervals under monotone_constraints,
+        state [S]: their group sets under interaction_constraints (the same
+        on every rank: each derives them from the picked table)."""
         x = self.xchg
         mono = self._mono() if bounds is not None else None
+        fmask = self._fmask() if state is not None else None
         if x is None:
-            return find_splits(self.p, hist, totals, self._valid(), mono, bounds)
+            return find_splits(self.p, hist, totals, self._valid(), mono, bounds, fmask, state)
         if x.hi > x.lo:
             cand = find_splits(self.p, hist, totals, self._valid()[x.lo:x.hi],
-                               mono[x.lo:x.hi] if mono is not None else None, bounds)
+                               mono[x.lo:x.hi] if mono is not None else None, bounds,
+                               fmask[x.lo:x.hi] if fmask is not None else None, state)
             cand[:, 1] += x.lo  # global feature ids
         else:  # (more ranks than features: this rank owns none)
             cand = torch.zeros(hist.shape[0], 6, dtype=torch.float64)
@@ -739,6 +784,8 @@ class TreeBuilder(_LevelGrower):
                   cut_off=self._cut_lists[1], eta=float(p.eta), alpha=float(p.alpha),
                   reg_lambda=float(p.reg_lambda), min_child_weight=float(p.min_child_weight),
                   max_depth=int(p.max_depth), rt_eps=RT_EPS, allreduce=ar, mono=self._mono())
+        if self.fmask is not None:
+            kw["fmask"] = self._fmask()
         # deferred: the tree stays a device node table, the margins are
         # walked from it on the device, and its host lists are built one tree
         # later (no GPU idle between trees); needs the row walk and no
@@ -823,17 +870,22 @@ class CSRTreeBuilder(_LevelGrower):
                 hist[sl, :, c].index_add_(0, gb, gh[:, c])
         return hist
 
-    def _find_splits(self, hist, totals, bounds=None):
+    def _find_splits(self, hist, totals, bounds=None, state=None):
         p = self.p
         mono = self._mono() if bounds is not None else None
+        fmask = self._fmask() if state is not None else None
         if self.gpu:
             if bounds is not None:
                 bounds = bounds.to(self.device).double().contiguous()
+            inter = {}
+            if state is not None:
+                inter = dict(fmask=fmask, state=state.to(self.device).contiguous())
             return _native.hip().gbdt_split_csr(hist.contiguous(), totals.double().contiguous(),
                                                 self.cut_off, self.fvalid, float(p.alpha),
                                                 float(p.reg_lambda), float(p.min_child_weight),
-                                                mono=mono, bounds=bounds).cpu()
-        return find_splits_csr_ref(p, hist, totals, self._cut_lists[1], self.fvalid, mono, bounds)
+                                                mono=mono, bounds=bounds, **inter).cpu()
+        return find_splits_csr_ref(p, hist, totals, self._cut_lists[1], self.fvalid, mono, bounds,
+                                   fmask, state)
 
     def _local_bin(self, f, rows):
         lb = torch.full((self.dm.n,), MISSING_BIN, dtype=torch.long)

@@ -32,6 +32,7 @@ class GBDTParam:
         self.eval_metric = []
         self.silent = 0
         self.monotone = []  # monotone_constraints: -1 | 0 | 1 per feature id (rest: 0)
+        self.interaction = []  # interaction_constraints: groups of feature ids ([]: off)
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -39,6 +40,8 @@ class GBDTParam:
             self.reg_lambda = float(val)
         elif name == "monotone_constraints":
             self.monotone = parse_monotone(val)
+        elif name == "interaction_constraints":
+            self.interaction = parse_interaction(val)
         elif name in ("eta", "gamma", "min_child_weight", "alpha", "base_score", "subsample",
                       "colsample_bytree"):
             setattr(self, name, float(val))
@@ -104,6 +107,72 @@ class GBDTParam:
         w0 = torch.where(H < self.min_child_weight, torch.zeros_like(d), -g / d)
         w = torch.where(w0 < lo, lo, torch.where(w0 > hi, hi, w0))
         return torch.where(w == w0, self.calc_gain(G, H), -(2.0 * g * w + d * w * w)), w
+
+    # ---- interaction_constraints: feature f carries the bit set m[f] of the
+    # groups that contain it (bit 63 alone when none does), a node the bit set
+    # of the groups that contain every feature split on above it.
+    def interaction_vector(self, F):
+        """The group bit sets of F features -> int64 [F] (bit i: group i
+        contains the feature; a feature in no group holds INTERACTION_FREE,
+        bit 63, alone), or None when interaction_constraints is not set."""
+        if not self.interaction:
+            return None
+        m = [0] * F
+        for i, grp in enumerate(self.interaction):
+            for f in grp:
+                if f >= F:
+                    raise SystemExit("interaction_constraints names feature %d, the data has %d "
+                                     "features" % (f, F))
+                m[f] |= 1 << i
+        return torch.tensor([v if v else INTERACTION_FREE for v in m], dtype=torch.int64)
+
+
+# interaction_constraints on one 64-bit word per feature and per node (int64
+# bit patterns): bits 0..62 are the groups, bit 63 marks a feature in no group.
+# A root holds INTERACTION_ROOT and admits every feature; a node admits feature
+# f iff state & m[f] != 0; its children hold interaction_child(state, m[f]),
+# which drops bit 63: below a split on an ungrouped feature nothing is admitted.
+INTERACTION_MAX_GROUPS = 63
+INTERACTION_FREE = -(1 << 63)
+INTERACTION_ROOT = -1
+
+
+def interaction_child(state, m):
+    """The children's state of a node of state ``state`` split on a feature
+    of mask ``m`` (Python ints as int64 bit patterns)."""
+    return state & m & ~INTERACTION_FREE
+
+
+def parse_interaction(val):
+    """``[[0,1,2],[2,3]]`` (spaces and outer quotes allowed) -> [[0, 1, 2],
+    [2, 3]]: sorted ids without duplicates per group; ``[]`` -> [] (off)."""
+    def bad(why):
+        raise SystemExit("interaction_constraints=%s: %s" % (val, why))
+
+    s = str(val).strip()
+    if len(s) >= 2 and s[0] == s[-1] and s[0] in "\"'":
+        s = s[1:-1].strip()
+    s = re.sub(r"\s*([\[\],])\s*", r"\1", s)
+    if len(s) < 2 or s[0] != "[" or s[-1] != "]":
+        bad("expected a list of lists of feature ids, like [[0,1],[2,3]]")
+    body = s[1:-1]
+    if not body:
+        return []
+    if not re.fullmatch(r"\[[^\[\]]*\](,\[[^\[\]]*\])*", body):
+        bad("unbalanced brackets, or not a list of lists")
+    groups = []
+    for inner in re.findall(r"\[([^\[\]]*)\]", body):
+        if not inner:
+            bad("empty group")
+        ids = set()
+        for tok in inner.split(","):
+            if not re.fullmatch(r"\+?\d+", tok):
+                bad("every feature id is a non-negative integer, got %r" % tok)
+            ids.add(int(tok))
+        groups.append(sorted(ids))
+    if len(groups) > INTERACTION_MAX_GROUPS:
+        bad("%d groups, at most %d are supported" % (len(groups), INTERACTION_MAX_GROUPS))
+    return groups
 
 
 def parse_monotone(val):
