@@ -17,6 +17,13 @@ intervals of every grower, against the same run without the option.
 --interaction GROUPS: train with interaction_constraints, GROUPS as the app
 takes them (``"[[0,1,2],[2,3]]"``), or ``halves``: two groups, the lower and
 the upper half of the features. Composes with --monotone.
+
+--objective NAME: a single-output objective instead of binary:logistic
+(count:poisson, reg:gamma, reg:tweedie, binary:hinge, reg:pseudohubererror,
+reg:squaredlogerror), on labels of the same synthetic score that fit it
+(counts for count:poisson and reg:tweedie, positive reals for reg:gamma and
+reg:squaredlogerror). count:poisson brings max_delta_step = 0.7, so it takes
+the bounded split kernels. train_error is the objective's default metric.
 """
 import argparse
 import json
@@ -34,7 +41,10 @@ from wormhole_amd.parallel.comm import env_local_rank  # noqa: E402
 from wormhole_amd.parallel import launch  # noqa: E402
 
 
-def higgs_like(n, f, seed, dev, num_class=0):
+OBJECTIVES = ("binary:logistic",) + tuple(G.OBJ_IDS)
+
+
+def higgs_like(n, f, seed, dev, num_class=0, objective="binary:logistic"):
     g = torch.Generator(device=dev).manual_seed(seed)
     X = torch.randn(n, f, device=dev, generator=g)
     X[:, :7] = X[:, :7].abs()  # kinematic-like positive features
@@ -45,6 +55,12 @@ def higgs_like(n, f, seed, dev, num_class=0):
         srt = logit.sort().values
         edges = srt[[(n * k) // num_class for k in range(1, num_class)]]
         y = torch.bucketize(logit, edges).float()
+    elif objective in ("count:poisson", "reg:tweedie"):  # counts of mean exp(score / 2)
+        y = torch.poisson(torch.exp(0.5 * logit.clamp(-3, 3)), generator=g)
+    elif objective in ("reg:gamma", "reg:squaredlogerror"):  # positive reals around it
+        y = torch.exp(0.5 * logit.clamp(-3, 3)) * (0.5 + torch.rand(n, device=dev, generator=g))
+    elif objective == "reg:pseudohubererror":
+        y = logit + torch.randn(n, device=dev, generator=g)
     return X, y
 
 
@@ -77,6 +93,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--num-class", type=int, default=0,
                     help="K > 1: multi:softprob, K trees per round (--trees counts trees)")
+    ap.add_argument("--objective", default="binary:logistic", choices=OBJECTIVES,
+                    help="a single-output objective (not with --num-class); labels are drawn to fit")
     ap.add_argument("--monotone", default="",
                     help='monotone_constraints as a pattern of + - 0 cycled over the features')
     ap.add_argument("--interaction", default="",
@@ -101,10 +119,12 @@ def main():
     launch.verify_world(bsp.comm, a.gpus if launch.launched() else 1)
     n = a.rows // bsp.world
     K = a.num_class if a.num_class > 1 else 1
-    X, y = higgs_like(n, a.features, 7 + bsp.rank, dev, a.num_class)
+    if K > 1 and a.objective != "binary:logistic":
+        ap.error("--objective and --num-class exclude each other")
+    X, y = higgs_like(n, a.features, 7 + bsp.rank, dev, a.num_class, a.objective)
     dm = G.DMatrix.from_dense(X, y, dev)
     p = G.GBDTParam()
-    p.objective = "binary:logistic" if K == 1 else "multi:softprob"
+    p.objective = a.objective if K == 1 else "multi:softprob"
     p.num_class = a.num_class if K > 1 else 0
     p.max_depth = a.depth
     p.eta = 0.1
@@ -127,7 +147,7 @@ def main():
     B = cuts.bin(dm)
     sync()
     t_prep = time.perf_counter() - t_prep
-    obj = G.Objective(p.objective, p.num_class)
+    obj = G.Objective(p.objective, p.num_class, p)
     tb = G.TreeBuilder(p, bsp, dm, cuts, B)
     margin = torch.zeros(n, device=dev) if K == 1 else torch.zeros(K, n, device=dev)
     rounds = max(1, a.trees // K)
@@ -167,7 +187,8 @@ def main():
         print(json.dumps({"metric": "GBDT trees/s (hist, depth %d, %dx%d)" % (a.depth, a.rows, a.features),
                           "value": ntree / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
                           "ms_per_tree": 1000 * dt / ntree,
-                          "trees": ntree, **extra, "monotone": a.monotone or None,
+                          "trees": ntree, **extra, "objective": p.objective,
+                          "monotone": a.monotone or None,
                           "interaction": p.interaction or None,
                           "sketch_bin_s": t_prep,
                           "hist_exchange": ("feature-reduce-scatter" if tb.xchg is not None

@@ -15,6 +15,7 @@
 #include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
+#include "host/gbdt_objective.h"
 #include "host/gbdt_rank_plan.h"
 #include "host/gbdt_shap_plan.h"
 
@@ -275,6 +276,74 @@ std::vector<Tensor> gbdt_gpair(const Tensor& margin, const Tensor& label,
     wh::gbdt_gpair(n, ptr<float>(margin), ptr<float>(label), wp, logistic, ptr<float>(gp),
                    ptr<double>(scratch[dev]), ptr<double>(st), cur_stream(margin));
   return {gp, st};
+}
+
+// ---- the objectives of host/gbdt_objective.h
+namespace {
+const float* obj_args(const char* op, const Tensor& margin, const Tensor& label,
+                      const c10::optional<Tensor>& weight) {
+  CHECK_IN(margin, torch::kFloat32);
+  CHECK_IN(label, torch::kFloat32);
+  TORCH_CHECK(label.numel() == margin.numel(), op, ": label size mismatch");
+  if (!(weight.has_value() && weight->defined())) return nullptr;
+  CHECK_IN((*weight), torch::kFloat32);
+  TORCH_CHECK(weight->numel() == margin.numel(), op, ": weight size mismatch");
+  return ptr<float>(*weight);
+}
+
+// per device and per op (slot), zeroed once: the ticket words stay zeroed
+double* obj_scratch(const Tensor& like, int slot, int64_t need) {
+  static std::vector<Tensor> scratch(2 * 64);
+  Tensor& t = scratch[2 * like.device().index() + slot];
+  if (!t.defined()) t = torch::zeros({need}, like.options().dtype(torch::kFloat64));
+  return ptr<double>(t);
+}
+}  // namespace
+
+// (gpair f32 [n, 2], stats f64 [4]) as gbdt_gpair; objective: a wh::GbdtObj id
+std::vector<Tensor> gbdt_gpair_obj(const Tensor& margin, const Tensor& label,
+                                   const c10::optional<Tensor>& weight, int64_t objective,
+                                   double max_delta_step, double tweedie_variance_power,
+                                   double huber_slope, double scale_pos_weight) {
+  const float* wp = obj_args("gbdt_gpair_obj", margin, label, weight);
+  TORCH_CHECK(objective >= 0 && objective < wh::kObjCount, "gbdt_gpair_obj: unknown objective id ",
+              objective);
+  TORCH_CHECK(max_delta_step >= 0 && huber_slope > 0 && scale_pos_weight > 0 &&
+                  tweedie_variance_power > 1 && tweedie_variance_power < 2,
+              "gbdt_gpair_obj: max_delta_step >= 0, tweedie_variance_power in (1, 2), "
+              "huber_slope > 0 and scale_pos_weight > 0");
+  const int64_t n = margin.numel();
+  c10::DeviceGuard g(margin.device());
+  auto gp = torch::empty({n, 2}, margin.options());
+  auto st = n > 0 ? torch::empty({4}, margin.options().dtype(torch::kFloat64))  // all 4 written
+                  : torch::zeros({4}, margin.options().dtype(torch::kFloat64));
+  if (n > 0) {
+    const auto a = wh::gbdt_obj_scalars(max_delta_step, tweedie_variance_power, huber_slope,
+                                        scale_pos_weight);
+    const bool ok = wh::gbdt_gpair_obj(
+        (int)objective, n, ptr<float>(margin), ptr<float>(label), wp, a, ptr<float>(gp),
+        obj_scratch(margin, 0, wh::gbdt_gpair_scratch()), ptr<double>(st), cur_stream(margin));
+    TORCH_CHECK(ok, "gbdt_gpair_obj: no kernel for objective id ", objective);
+  }
+  return {gp, st};
+}
+
+// f64 [8] = {sum w loss_j for the wh::GbdtMetric ids j of mask (else 0), sum w}
+Tensor gbdt_obj_eval(const Tensor& margin, const Tensor& label,
+                     const c10::optional<Tensor>& weight, int64_t link, int64_t mask,
+                     double tweedie_variance_power, double huber_slope) {
+  const float* wp = obj_args("gbdt_obj_eval", margin, label, weight);
+  TORCH_CHECK(link >= 0 && link <= wh::kLinkStep, "gbdt_obj_eval: unknown link ", link);
+  TORCH_CHECK(mask >= 0 && mask < (1 << wh::kMetCount), "gbdt_obj_eval: unknown metric bits");
+  const int64_t n = margin.numel();
+  c10::DeviceGuard g(margin.device());
+  auto out = torch::zeros({wh::gbdt_obj_eval_out()}, margin.options().dtype(torch::kFloat64));
+  if (n > 0)
+    wh::gbdt_obj_eval(n, ptr<float>(margin), ptr<float>(label), wp, (int)link, (int)mask,
+                      tweedie_variance_power, huber_slope,
+                      obj_scratch(margin, 1, wh::gbdt_obj_eval_scratch()), ptr<double>(out),
+                      cur_stream(margin));
+  return out;
 }
 
 // ---- multi-class softmax: margin f32 [K, n] class-major, label f32 [n]
@@ -1091,7 +1160,8 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
                     std::vector<double> root_tot, std::vector<float> cut_vals,
                     std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
                     double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
-                    const c10::optional<Tensor>& mono, const c10::optional<Tensor>& fmask) {
+                    const c10::optional<Tensor>& mono, const c10::optional<Tensor>& fmask,
+                    double max_delta_step) {
   const GrowCtx cx(B, Bc, ridx0, gpair, qscale, valid, nbin, fgroups, max_fcnt);
   c10::DeviceGuard g(B.device());
   const auto s = cx.s;
@@ -1140,6 +1210,10 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   };
   const int root = add(-1);
   tot[root] = {root_tot[0], root_tot[1]};
+  // max_delta_step: the root's interval (the children's are cut inside it)
+  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
+              "gbdt_grow: max_delta_step >= 0, and it needs mono (all zero for no signs)");
+  if (max_delta_step > 0) bnd[root] = {-max_delta_step, max_delta_step};
   std::map<int, std::pair<int, int>> seg;  // live frontier segments (node -> [b, e))
   seg[root] = {0, (int)n};
   py::list segs;  // finished leaves: (node, b, e)
@@ -1429,7 +1503,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                         double mcw, int64_t max_depth, double rt_eps, py::object allreduce,
                         py::object reduce_scatter, py::object pick, int64_t f_lo, bool walk,
                         bool defer, const c10::optional<Tensor>& mono,
-                        const c10::optional<Tensor>& fmask) {
+                        const c10::optional<Tensor>& fmask, double max_delta_step) {
   // Multi-rank: either every level's built histograms are allreduced (all
   // features on every rank), or -- reduce_scatter / pick given
   // (models/gbdt.py HistExchange) -- each rank receives the global sums of
@@ -1458,11 +1532,14 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
   }
   const int8_t* d_mono = optptr<int8_t>(mono);
   Tensor bounds_cur;
+  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
+              "gbdt_grow_dev: max_delta_step >= 0, and it needs mono (all zero for no signs)");
   if (mono_on) {
-    const double inf = std::numeric_limits<double>::infinity();
+    // the root's interval: max_delta_step on either side of 0, else unbounded
+    const double hi = max_delta_step > 0 ? max_delta_step : std::numeric_limits<double>::infinity();
     bounds_cur = torch::empty({1, 2}, f64);
-    bounds_cur.select(1, 0).fill_(-inf);
-    bounds_cur.select(1, 1).fill_(inf);
+    bounds_cur.select(1, 0).fill_(-hi);
+    bounds_cur.select(1, 1).fill_(hi);
   }
   // interaction_constraints: fmask [F] int64 (all features, as mono) and the
   // slots' group sets, ping-ponged like the weight intervals
@@ -1670,18 +1747,27 @@ void bind_gbdt(py::module_& m) {
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
-        py::arg("allreduce"), py::arg("mono") = py::none(), py::arg("fmask") = py::none());
+        py::arg("allreduce"), py::arg("mono") = py::none(), py::arg("fmask") = py::none(),
+        py::arg("max_delta_step") = 0.0);
   m.def("gbdt_grow_dev", &gbdt_grow_dev, py::arg("B"), py::arg("Bc"), py::arg("ridx0"), py::arg("gpair"),
         py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"), py::arg("max_fcnt"),
         py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"), py::arg("eta"), py::arg("alpha"),
         py::arg("reg_lambda"), py::arg("min_child_weight"), py::arg("max_depth"), py::arg("rt_eps"),
         py::arg("allreduce"), py::arg("reduce_scatter") = py::none(), py::arg("pick") = py::none(),
         py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false,
-        py::arg("mono") = py::none(), py::arg("fmask") = py::none());
+        py::arg("mono") = py::none(), py::arg("fmask") = py::none(),
+        py::arg("max_delta_step") = 0.0);
   m.def("gbdt_tree_from_nodes", &gbdt_tree_from_nodes);
   m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
         py::arg("lds") = true);
   m.def("gbdt_gpair", &gbdt_gpair);
+  m.def("gbdt_gpair_obj", &gbdt_gpair_obj, py::arg("margin"), py::arg("label"), py::arg("weight"),
+        py::arg("objective"), py::arg("max_delta_step") = 0.0,
+        py::arg("tweedie_variance_power") = 1.5, py::arg("huber_slope") = 1.0,
+        py::arg("scale_pos_weight") = 1.0);
+  m.def("gbdt_obj_eval", &gbdt_obj_eval, py::arg("margin"), py::arg("label"), py::arg("weight"),
+        py::arg("link"), py::arg("mask"), py::arg("tweedie_variance_power") = 1.5,
+        py::arg("huber_slope") = 1.0);
   m.def("gbdt_gpair_softmax", &gbdt_gpair_softmax);
   m.def("gbdt_softmax_out", &gbdt_softmax_out);
   m.def("gbdt_multi_eval", &gbdt_multi_eval);

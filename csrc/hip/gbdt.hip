@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "host/gbdt_objective.h"
 #include "wh_common.h"
 #include "wh_kernels.h"
 #include "wh_lookback.h"
@@ -902,6 +903,189 @@ void gbdt_gpair(int64_t n, const float* margin, const float* label, const float*
   const int nb = std::max(1, std::min<int>(kGpBlocks, grid_for(n, kGpThreads)));
   hipLaunchKernelGGL(k_gpair, dim3(nb), dim3(kGpThreads), 0, s, n, margin, label, weight,
                      logistic ? 1 : 0, reinterpret_cast<float2*>(gpair), scratch, ticket, stats);
+}
+
+namespace {
+// ---- the objectives of host/gbdt_objective.h: one gradient kernel templated
+// on the objective (no branch on it in the row loop), its scalars as an
+// argument, and k_gpair's reduction: per-block partials {sum g, sum h, max|g|,
+// max|h|}, the arrival ticket, a fixed-order sum in the last block.
+// Block-wide: v = the threads' {sum, sum, max, max} -> the block's, in v of
+// thread 0 (sh: [4][kGpThreads / 64]).
+__device__ __forceinline__ void gp_block_reduce(double (&v)[4], double (*sh)[kGpThreads / 64]) {
+  v[0] = wave_sum_d(v[0]);
+  v[1] = wave_sum_d(v[1]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    v[2] = fmax(v[2], __shfl_xor(v[2], o, 64));
+    v[3] = fmax(v[3], __shfl_xor(v[3], o, 64));
+  }
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0)
+    for (int q = 0; q < 4; ++q) sh[q][wid] = v[q];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 4; ++q) v[q] = 0;
+    for (int w = 0; w < kGpThreads / 64; ++w) {
+      v[0] += sh[0][w]; v[1] += sh[1][w];
+      v[2] = fmax(v[2], sh[2][w]); v[3] = fmax(v[3], sh[3][w]);
+    }
+  }
+}
+
+template <int OBJ>
+__global__ __launch_bounds__(kGpThreads) void k_gpair_obj(
+    int64_t n, const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, GbdtObjScalars a, float2* __restrict__ out,
+    double* __restrict__ part, unsigned int* ticket, double* stats) {
+  __shared__ double sh[4][kGpThreads / 64];
+  __shared__ int last;
+  double v[4] = {0, 0, 0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * kGpThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kGpThreads) {
+    const float y = label[i];
+    const GbdtPair p = gbdt_obj_pair<OBJ>(margin[i], y, a);
+    float g = p.g, h = p.h;
+    if (!p.scaled) {
+      const float w = gbdt_obj_weight<OBJ>(weight ? weight[i] : 1.f, y, a);
+      g *= w;
+      h *= w;
+    }
+    out[i] = make_float2(g, h);
+    v[0] += g;
+    v[1] += h;
+    v[2] = fmax(v[2], (double)fabsf(g));
+    v[3] = fmax(v[3], (double)fabsf(h));
+  }
+  gp_block_reduce(v, sh);
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < 4; ++q)
+      lb_store(reinterpret_cast<unsigned long long*>(part) + blockIdx.x * 4 + q,
+               (unsigned long long)__double_as_longlong(v[q]));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = arrive_last(ticket, blockIdx.x, gridDim.x);
+  }
+  __syncthreads();
+  if (!last) return;
+  // thread t takes blocks t, t + 256, ... (as k_gpair: the same sums every run)
+  const unsigned long long* pp = reinterpret_cast<const unsigned long long*>(part);
+  for (int q = 0; q < 4; ++q) v[q] = 0;
+  for (unsigned b = threadIdx.x; b < gridDim.x; b += kGpThreads) {
+    v[0] += __longlong_as_double((long long)lb_load(pp + b * 4));
+    v[1] += __longlong_as_double((long long)lb_load(pp + b * 4 + 1));
+    v[2] = fmax(v[2], __longlong_as_double((long long)lb_load(pp + b * 4 + 2)));
+    v[3] = fmax(v[3], __longlong_as_double((long long)lb_load(pp + b * 4 + 3)));
+  }
+  gp_block_reduce(v, sh);  // (thread 0 read sh before the barrier above)
+  if (threadIdx.x == 0)
+    for (int q = 0; q < 4; ++q) stats[q] = v[q];
+}
+
+// The new metrics of a set in one read of margin / label / weight: fp64
+// {sum w loss_j} for the metrics of `mask` (bit j: GbdtMetric j; the others
+// stay 0) and sum w at [kMetCount], each loss evaluated in double from the
+// fp32 inputs, by per-block partials + arrival ticket like k_multi_eval.
+constexpr int kEvThreads = 256, kEvWaves = kEvThreads / 64, kEvBlocks = 1024;
+constexpr int kEvOut = kMetCount + 1;
+__global__ __launch_bounds__(kEvThreads) void k_obj_eval(
+    int64_t n, const float* __restrict__ margin, const float* __restrict__ label,
+    const float* __restrict__ weight, int link, int mask, double rho, double delta,
+    double* __restrict__ part, unsigned int* ticket, double* out) {
+  __shared__ double sh[kEvOut][kEvWaves];
+  __shared__ int last;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  double v[kEvOut];
+#pragma unroll
+  for (int q = 0; q < kEvOut; ++q) v[q] = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kEvThreads + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * kEvThreads) {
+    const double p = gbdt_link(link, (double)margin[i]), y = (double)label[i];
+    const double w = weight ? (double)weight[i] : 1.0;
+#pragma unroll
+    for (int q = 0; q < kMetCount; ++q)
+      if (mask >> q & 1) v[q] += w * gbdt_metric_loss(q, p, y, rho, delta);
+    v[kMetCount] += w;
+  }
+#pragma unroll
+  for (int q = 0; q < kEvOut; ++q) {
+    v[q] = wave_sum_d(v[q]);
+    if (lane == 0) sh[q][wid] = v[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int q = 0; q < kEvOut; ++q) {
+      double t = 0;
+      for (int w = 0; w < kEvWaves; ++w) t += sh[q][w];
+      lb_store(reinterpret_cast<unsigned long long*>(part) + blockIdx.x * kEvOut + q,
+               (unsigned long long)__double_as_longlong(t));
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    last = arrive_last(ticket, blockIdx.x, gridDim.x);
+  }
+  __syncthreads();
+  if (!last) return;
+  const unsigned long long* pp = reinterpret_cast<const unsigned long long*>(part);
+  for (int q = 0; q < kEvOut; ++q) {
+    double t = 0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += kEvThreads)
+      t += __longlong_as_double((long long)lb_load(pp + b * kEvOut + q));
+    t = wave_sum_d(t);
+    __syncthreads();
+    if (lane == 0) sh[q][wid] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  for (int q = 0; q < kEvOut; ++q) {
+    double t = 0;
+    for (int w = 0; w < kEvWaves; ++w) t += sh[q][w];
+    out[q] = t;
+  }
+}
+
+// scratch (doubles): the (zeroed) arrival ticket words first, then the block partials
+constexpr int64_t kEvTicketD = (kArriveWords + 1) / 2 + 1;
+}  // namespace
+
+template <int OBJ>
+static void launch_gpair_obj(int nb, hipStream_t s, int64_t n, const float* margin,
+                             const float* label, const float* weight, const GbdtObjScalars& a,
+                             float2* out, double* part, unsigned int* ticket, double* stats) {
+  hipLaunchKernelGGL(k_gpair_obj<OBJ>, dim3(nb), dim3(kGpThreads), 0, s, n, margin, label, weight,
+                     a, out, part, ticket, stats);
+}
+
+bool gbdt_gpair_obj(int obj, int64_t n, const float* margin, const float* label,
+                    const float* weight, const GbdtObjScalars& a, float* gpair, double* scratch,
+                    double* stats, hipStream_t s) {
+  if (obj < 0 || obj >= kObjCount) return false;
+  if (n <= 0) return true;
+  // scratch as gbdt_gpair's: per-block partials, then the (zeroed) ticket words
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch + 4 * kGpBlocks);
+  const int nb = std::max(1, std::min<int>(kGpBlocks, grid_for(n, kGpThreads)));
+  float2* out = reinterpret_cast<float2*>(gpair);
+  switch (obj) {
+    case kObjLogistic: launch_gpair_obj<kObjLogistic>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjPoisson: launch_gpair_obj<kObjPoisson>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjGamma: launch_gpair_obj<kObjGamma>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjTweedie: launch_gpair_obj<kObjTweedie>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjHinge: launch_gpair_obj<kObjHinge>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjPseudoHuber: launch_gpair_obj<kObjPseudoHuber>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    default: launch_gpair_obj<kObjSquaredLog>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+  }
+  return true;
+}
+
+int64_t gbdt_obj_eval_scratch() { return kEvTicketD + (int64_t)kEvOut * kEvBlocks; }
+int gbdt_obj_eval_out() { return kEvOut; }
+
+void gbdt_obj_eval(int64_t n, const float* margin, const float* label, const float* weight,
+                   int link, int mask, double rho, double delta, double* scratch, double* out,
+                   hipStream_t s) {
+  if (n <= 0) return;
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch);
+  hipLaunchKernelGGL(k_obj_eval, dim3(grid_for(n, kEvThreads, kEvBlocks)), dim3(kEvThreads), 0, s,
+                     n, margin, label, weight, link, mask, rho, delta, scratch + kEvTicketD, ticket,
+                     out);
 }
 
 namespace {

@@ -648,6 +648,23 @@ void gbdt_qscale(const float* m, double nglobal, int R, float* out, hipStream_t 
 int64_t gbdt_gpair_scratch();
 void gbdt_gpair(int64_t n, const float* margin, const float* label, const float* weight,
                 bool logistic, float* gpair, double* scratch, double* stats, hipStream_t s);
+// the objectives of host/gbdt_objective.h (obj: a GbdtObj id; false for any
+// other value, nothing launched), their scalars in `a`: the pairs and the
+// same statistics as gbdt_gpair, from the same scratch. Nothing runs for n <= 0.
+struct GbdtObjScalars;
+bool gbdt_gpair_obj(int obj, int64_t n, const float* margin, const float* label,
+                    const float* weight, const GbdtObjScalars& a, float* gpair, double* scratch,
+                    double* stats, hipStream_t s);
+// the new metrics of a set in one launch: out [gbdt_obj_eval_out()] (fp64) =
+// {sum w loss_j} for the GbdtMetric ids j whose bit is set in mask, then
+// sum w; link: a GbdtLink id (margin -> prediction). scratch:
+// gbdt_obj_eval_scratch() doubles, zeroed once (the ticket words stay
+// zeroed). Nothing runs for n <= 0.
+int64_t gbdt_obj_eval_scratch();
+int gbdt_obj_eval_out();
+void gbdt_obj_eval(int64_t n, const float* margin, const float* label, const float* weight,
+                   int link, int mask, double rho, double delta, double* scratch, double* out,
+                   hipStream_t s);
 // multi-class softmax, class-major margin [K, n] / gpair [K, n, 2]: the pairs
 // of all K trees of a round + stats [K, 4] (per class as gbdt_gpair's) in one
 // launch; predictions (arg-max ids [n], or probabilities [n, K]); evaluation

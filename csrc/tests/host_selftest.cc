@@ -29,6 +29,7 @@
 #include "host/common.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
+#include "host/gbdt_objective.h"
 #include "host/io.h"
 #include "host/json.h"
 #include "host/linear_guard_plan.h"
@@ -641,6 +642,64 @@ static void test_gbdt_level_plan() {
   }
 }
 
+// the objectives' gradient pairs and the metrics' row losses
+// (host/gbdt_objective.h: the functions the kernels call) against their
+// formulas in double, and the hinge table exactly
+static void test_gbdt_objective() {
+  const wh::GbdtObjScalars a = wh::gbdt_obj_scalars(0.7, 1.5, 2.0, 3.0);
+  EXPECT(a.max_delta_step == 0.7f && a.tw1 == -0.5f && a.tw2 == 0.5f && a.delta2 == 4.f);
+  auto near = [](float got, double want, double scale) {
+    return std::fabs((double)got - want) <= 1e-6 * scale;
+  };
+  for (float m : {-4.f, -0.75f, 0.f, 0.5f, 3.25f})
+    for (float y : {0.25f, 1.f, 3.f}) {
+      const double M = m, Y = y, e = std::exp(M);
+      auto p = wh::gbdt_obj_pair<wh::kObjPoisson>(m, y, a);
+      EXPECT(near(p.g, e - Y, e + Y) && near(p.h, std::exp(M + 0.7), std::exp(M + 0.7)));
+      p = wh::gbdt_obj_pair<wh::kObjGamma>(m, y, a);
+      EXPECT(near(p.g, 1 - Y / e, 1 + Y / e) && near(p.h, Y / e, Y / e) && !p.scaled);
+      p = wh::gbdt_obj_pair<wh::kObjTweedie>(m, y, a);
+      const double e1 = std::exp(-0.5 * M), e2 = std::exp(0.5 * M);
+      EXPECT(near(p.g, -Y * e1 + e2, Y * e1 + e2));
+      EXPECT(near(p.h, 0.5 * Y * e1 + 0.5 * e2, 0.5 * Y * e1 + 0.5 * e2));
+      p = wh::gbdt_obj_pair<wh::kObjPseudoHuber>(m, y, a);
+      const double z = M - Y, s = std::sqrt(1 + z * z / 4);
+      EXPECT(near(p.g, z / s, std::fabs(z / s)) && near(p.h, 1 / (s * s * s), 1.0));
+      p = wh::gbdt_obj_pair<wh::kObjSquaredLog>(m, y, a);
+      const double mm = std::max(M, (double)wh::kSquaredLogMinMargin);
+      const double lm = std::log1p(mm), ly = std::log1p(Y), d = mm + 1;
+      EXPECT(near(p.g, (lm - ly) / d, (std::fabs(lm) + std::fabs(ly)) / d));
+      EXPECT(near(p.h, std::max((1 - lm + ly) / (d * d), 1e-6),
+                  (1 + std::fabs(lm) + std::fabs(ly)) / (d * d)));
+      p = wh::gbdt_obj_pair<wh::kObjLogistic>(m, y, a);
+      const double q = 1 / (1 + std::exp(-M));
+      EXPECT(near(p.g, q - Y, q + Y) && near(p.h, q * (1 - q), 1.0));
+    }
+  // hinge: (y, side of the margin) -> the pair; a satisfied row is final
+  auto hinge = [&](float m, float y) { return wh::gbdt_obj_pair<wh::kObjHinge>(m, y, a); };
+  EXPECT(hinge(0.5f, 1.f).g == -1.f && hinge(0.5f, 1.f).h == 1.f && !hinge(0.5f, 1.f).scaled);
+  EXPECT(hinge(1.f, 1.f).g == 0.f && hinge(1.f, 1.f).h == FLT_MIN && hinge(1.f, 1.f).scaled);
+  EXPECT(hinge(-0.5f, 0.f).g == 1.f && hinge(-0.5f, 0.f).h == 1.f);
+  EXPECT(hinge(-1.5f, 0.f).g == 0.f && hinge(-1.5f, 0.f).h == FLT_MIN);
+  // scale_pos_weight multiplies the weight of the rows with y == 1 only
+  EXPECT(wh::gbdt_obj_weight<wh::kObjLogistic>(2.f, 1.f, a) == 6.f);
+  EXPECT(wh::gbdt_obj_weight<wh::kObjLogistic>(2.f, 0.f, a) == 2.f);
+  EXPECT(wh::gbdt_obj_weight<wh::kObjPoisson>(2.f, 1.f, a) == 2.f);
+  // links and row losses at round values
+  EXPECT(wh::gbdt_link(wh::kLinkIdentity, -2.0) == -2.0 && wh::gbdt_link(wh::kLinkExp, 0.0) == 1.0);
+  EXPECT(wh::gbdt_link(wh::kLinkSigmoid, 0.0) == 0.5);
+  EXPECT(wh::gbdt_link(wh::kLinkStep, 0.0) == 0.0 && wh::gbdt_link(wh::kLinkStep, 0.1) == 1.0);
+  auto loss = [](int k, double p, double y) { return wh::gbdt_metric_loss(k, p, y, 1.5, 2.0); };
+  EXPECT(std::fabs(loss(wh::kMetPoissonNll, 1.0, 3.0) - (std::log(6.0) + 1.0)) < 1e-12);
+  EXPECT(std::fabs(loss(wh::kMetPoissonNll, 0.0, 0.0) - 1e-16) < 1e-30);  // p clamped
+  EXPECT(std::fabs(loss(wh::kMetGammaNll, 2.0, 3.0) - (1.5 + std::log(2.0))) < 1e-12);
+  EXPECT(std::fabs(loss(wh::kMetGammaDeviance, 2.0, 2.0)) < 1e-12);
+  EXPECT(std::fabs(loss(wh::kMetTweedieNll, 4.0, 3.0) - (3.0 * 0.5 * 2.0 + 2.0 * 2.0)) < 1e-12);
+  EXPECT(loss(wh::kMetMae, 1.0, 3.5) == 2.5);
+  EXPECT(std::fabs(loss(wh::kMetMphe, 1.0, 4.0) - 4.0 * (std::sqrt(1 + 9.0 / 4) - 1)) < 1e-12);
+  EXPECT(std::fabs(loss(wh::kMetRmsle, 0.0, std::exp(1.0) - 1) - 1.0) < 1e-12);
+}
+
 // the localize job's bookkeeping (host/localize_plan.h) through the job
 // sequences the GPU tests rely on. A Job mirrors what LocalizeJob holds.
 static void test_localize_plan() {
@@ -862,6 +921,7 @@ int main() {
   test_psx_plan();
   test_gbdt_hist_plan();
   test_gbdt_level_plan();
+  test_gbdt_objective();
   test_lz4();
   test_crb();
   test_parsers();

@@ -4,13 +4,16 @@ learn/xgboost/run_yarn.sh; SURVEY §2.2 "xgboost"):
 
 tasks ``train | pred | dump | eval``; parameters booster, objective
 (binary:logistic, binary:logitraw, reg:logistic, reg:linear,
-reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg),
+reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg,
+count:poisson, reg:gamma, reg:tweedie, binary:hinge, reg:pseudohubererror,
+reg:squaredlogerror),
 num_class (the multi:
 objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
 gamma, min_child_weight, max_depth, lambda, alpha, base_score, max_bin,
-subsample, colsample_bytree, monotone_constraints, interaction_constraints, seed,
+subsample, colsample_bytree, monotone_constraints, interaction_constraints,
+max_delta_step, scale_pos_weight, tweedie_variance_power, huber_slope, seed,
 eval_metric, num_round, save_period,
 eval_train, eval[name]=path, data, test:data, model_in, model_out, model_dir,
 fmap, name_dump, name_pred, dump_stats, dsplit=row, dsparse (keep the rows CSR:
@@ -61,6 +64,23 @@ the data's feature count, unbalanced brackets or a 64th group end the run
 with an error. Composes with colsample_bytree and monotone_constraints;
 every class's trees of a multi: objective are constrained (docs/bsp_apps.md
 "Interaction constraints").
+
+Objectives and max_delta_step: count:poisson, reg:gamma and reg:tweedie
+predict exp(margin) (base_score > 0 enters as its logarithm), binary:hinge
+predicts 0 or 1, reg:pseudohubererror and reg:squaredlogerror the margin;
+labels must be >= 0 (count:poisson, reg:tweedie), > 0 (reg:gamma), 0 or 1
+(binary:hinge), > -1 (reg:squaredlogerror), else the run ends with an error.
+Their default metrics are poisson-nloglik, gamma-nloglik,
+tweedie-nloglik@<tweedie_variance_power>, error, mphe and rmsle; these, with
+gamma-deviance and mae, go with any single-output objective
+(tweedie-nloglik needs its ``@rho``, rho in (1, 2)). tweedie_variance_power
+(in (1, 2), default 1.5) and huber_slope (> 0, default 1) are not stored in
+the model: task=eval takes them from the command line or their defaults.
+max_delta_step=d (d >= 0; 0: off; 0.7 by default for count:poisson) clamps
+every node's weight to [-d, d] before eta. scale_pos_weight=s (s > 0)
+multiplies the weight of the rows with label 1 by s in the gradient pairs of
+the logistic objectives (not in the metrics); with another objective s != 1
+is an error (docs/bsp_apps.md "Objectives and max_delta_step").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -373,7 +393,8 @@ def main(argv):
     # the row's hessians summed over the classes)
     hess = None
     if dtrain.n:
-        hess = obj.gpair(margin, dtrain.label, None, dtrain.rank_groups())[..., 1]
+        hess = obj.gpair(margin, dtrain.label, None, dtrain.rank_groups(),
+                         pos_weight=False)[..., 1]
         hess = hess.sum(0) if K > 1 else hess
     cuts = G.Cuts.build(dtrain, param.max_bin, bsp, hess=hess)
     B = cuts.bin(dtrain)

@@ -29,9 +29,10 @@ from .. import _native
 # matrices and cuts, the trees and the model (every public name stays
 # reachable from this module)
 from .gbdt_objective import (GBDTParam, INTERACTION_FREE, INTERACTION_ROOT,  # noqa: F401
-                             MULTI_METRICS, NLL_MAX, Objective, RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
+                             MULTI_METRICS, NLL_MAX, OBJ_IDS, OBJ_LOGISTIC, OBJ_METRICS, Objective,
+                             RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
                              eval_metric, first_argmax, gpair_stats, interaction_child,
-                             multi_eval_sums,
+                             multi_eval_sums, obj_eval_sums, obj_gpair_torch, parse_obj_metric,
                              parse_rank_metric, rank_eval, rank_eval_torch, rank_gpair_torch,
                              rank_metric, softmax_gpair_torch)
 from .gbdt_data import MISSING_BIN, CSRMatrix, Cuts, DMatrix, make_dmatrix  # noqa: F401
@@ -336,6 +337,13 @@ class _LevelGrower:
         # is the device copy the kernels read
         self.mono = param.monotone_vector(self.F)
         self._mono_dev = None
+        # max_delta_step = d > 0: the root's weight interval is (-d, d) on the
+        # same bounds path (an all-zero sign vector when none is set), so
+        # every node's weight is clamped to it and a clamped side is scored
+        # by the bounded formula; 0: off, nothing changes
+        self.max_delta_step = param.delta_step()
+        if self.max_delta_step > 0 and self.mono is None:
+            self.mono = torch.zeros(self.F, dtype=torch.int8)
         # interaction_constraints: the features' group bit sets, int64 [F]
         # (host; gbdt_objective.py interaction_vector), None when not set
         self.fmask = param.interaction_vector(self.F)
@@ -411,8 +419,9 @@ class _LevelGrower:
         self.bsp.allreduce(tot)
         totals = {root: tot.cpu()}
         # monotone_constraints: every node's weight interval, beside its totals
-        inf = float("inf")
-        bounds = {root: (-inf, inf)} if self.mono is not None else None
+        # (the root's: max_delta_step on either side of 0, else unbounded)
+        top = self.max_delta_step if self.max_delta_step > 0 else float("inf")
+        bounds = {root: (-top, top)} if self.mono is not None else None
         # interaction_constraints: every node's set of still possible groups
         state = {root: INTERACTION_ROOT} if self.fmask is not None else None
         fmask_h = self.fmask.tolist() if self.fmask is not None else None
@@ -786,6 +795,8 @@ class TreeBuilder(_LevelGrower):
                   max_depth=int(p.max_depth), rt_eps=RT_EPS, allreduce=ar, mono=self._mono())
         if self.fmask is not None:
             kw["fmask"] = self._fmask()
+        if self.max_delta_step > 0:  # the root's weight interval (else unbounded)
+            kw["max_delta_step"] = self.max_delta_step
         # deferred: the tree stays a device node table, the margins are
         # walked from it on the device, and its host lists are built one tree
         # later (no GPU idle between trees); needs the row walk and no

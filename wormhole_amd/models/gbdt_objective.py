@@ -33,6 +33,12 @@ class GBDTParam:
         self.silent = 0
         self.monotone = []  # monotone_constraints: -1 | 0 | 1 per feature id (rest: 0)
         self.interaction = []  # interaction_constraints: groups of feature ids ([]: off)
+        # max_delta_step: every node's weight stays in [-d, d] (0: off). None:
+        # not set -- 0.7 for count:poisson, else 0 (:meth:`delta_step`)
+        self.max_delta_step = None
+        self.scale_pos_weight = 1.0  # the logistic family: the weight of rows with y == 1
+        self.tweedie_variance_power = 1.5  # reg:tweedie (and its default metric): in (1, 2)
+        self.huber_slope = 1.0  # reg:pseudohubererror and mphe: > 0
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -42,6 +48,10 @@ class GBDTParam:
             self.monotone = parse_monotone(val)
         elif name == "interaction_constraints":
             self.interaction = parse_interaction(val)
+        elif name in ("max_delta_step", "scale_pos_weight", "tweedie_variance_power",
+                      "huber_slope"):
+            setattr(self, name, float(val))
+            check_objective_scalars(self)
         elif name in ("eta", "gamma", "min_child_weight", "alpha", "base_score", "subsample",
                       "colsample_bytree"):
             setattr(self, name, float(val))
@@ -54,6 +64,13 @@ class GBDTParam:
         else:
             return False
         return True
+
+    def delta_step(self):
+        """max_delta_step in effect: as set, else xgboost's 0.7 for
+        count:poisson and 0 (off) for every other objective."""
+        if self.max_delta_step is None:
+            return 0.7 if self.objective == "count:poisson" else 0.0
+        return float(self.max_delta_step)
 
     def calc_gain(self, G, H):
         g = _threshold_l1(G, self.alpha)
@@ -143,6 +160,21 @@ def interaction_child(state, m):
     return state & m & ~INTERACTION_FREE
 
 
+def check_objective_scalars(p):
+    """The ranges of the objectives' scalar parameters (docs/bsp_apps.md
+    "Objectives and max_delta_step"); ``p``: anything that carries them."""
+    d = getattr(p, "max_delta_step", None)
+    if d is not None and not d >= 0:
+        raise SystemExit("max_delta_step=%g: must not be negative (0: off)" % d)
+    if not getattr(p, "scale_pos_weight", 1.0) > 0:
+        raise SystemExit("scale_pos_weight=%g: must be positive" % p.scale_pos_weight)
+    if not 1.0 < getattr(p, "tweedie_variance_power", 1.5) < 2.0:
+        raise SystemExit("tweedie_variance_power=%g: must lie in (1, 2)"
+                         % p.tweedie_variance_power)
+    if not getattr(p, "huber_slope", 1.0) > 0:
+        raise SystemExit("huber_slope=%g: must be positive" % p.huber_slope)
+
+
 def parse_interaction(val):
     """``[[0,1,2],[2,3]]`` (spaces and outer quotes allowed) -> [[0, 1, 2],
     [2, 3]]: sorted ids without duplicates per group; ``[]`` -> [] (off)."""
@@ -203,6 +235,19 @@ MULTI_METRICS = ("merror", "mlogloss")
 SINGLE_METRICS = ("error", "logloss", "rmse", "auc")
 RANK_OBJECTIVES = ("rank:pairwise", "rank:ndcg")
 NLL_MAX = -math.log(1e-16)
+# The objectives of csrc/host/gbdt_objective.h (GbdtObj ids): one templated
+# gradient kernel, ``gbdt_gpair_obj``; OBJ_LOGISTIC is the logistic family
+# under scale_pos_weight != 1.
+OBJ_LOGISTIC = 0
+OBJ_IDS = {"count:poisson": 1, "reg:gamma": 2, "reg:tweedie": 3, "binary:hinge": 4,
+           "reg:pseudohubererror": 5, "reg:squaredlogerror": 6}
+LOG_LINK_OBJECTIVES = ("count:poisson", "reg:gamma", "reg:tweedie")  # prediction exp(margin)
+FLT_MIN = 1.1754943508222875e-38
+SQUARED_LOG_MIN_MARGIN = -1.0 + 1e-6
+# The metrics of the one-launch evaluation kernel ``gbdt_obj_eval`` (GbdtMetric
+# ids, the slots of its sums; the last slot is sum w)
+OBJ_METRICS = ("poisson-nloglik", "gamma-nloglik", "gamma-deviance", "tweedie-nloglik", "mae",
+               "mphe", "rmsle")
 _RANK_METRIC = re.compile(r"^(ndcg|map)(?:@(\d+))?(-)?$")
 
 
@@ -215,6 +260,25 @@ def parse_rank_metric(name):
     return m.group(1), int(m.group(2)) if m.group(2) else 0, m.group(3) is not None
 
 
+def parse_obj_metric(name):
+    """``poisson-nloglik | gamma-nloglik | gamma-deviance | mae | mphe |
+    rmsle`` or ``tweedie-nloglik@rho`` with rho in (1, 2) -> (slot, rho or
+    None); None for any other name. tweedie-nloglik without ``@rho``, or with
+    a rho outside (1, 2), is a ValueError."""
+    base, at, arg = name.partition("@")
+    if base not in OBJ_METRICS:
+        return None
+    if base != "tweedie-nloglik":
+        return None if at else (OBJ_METRICS.index(base), None)
+    try:
+        rho = float(arg)
+    except ValueError:
+        rho = float("nan")
+    if not at or not 1.0 < rho < 2.0:
+        raise ValueError("eval_metric %s: write tweedie-nloglik@rho with rho in (1, 2)" % name)
+    return OBJ_METRICS.index(base), rho
+
+
 class Objective:
     """Single-output objectives keep one margin per row; multi:softmax and
     multi:softprob keep ``num_class`` margins per row, class-major
@@ -224,9 +288,13 @@ class Objective:
     one margin per row (the prediction is the margin) and need the rows'
     query groups (``DMatrix.group``) for their gradient pairs."""
 
-    def __init__(self, name, num_class=0):
+    def __init__(self, name, num_class=0, param=None):
+        """param: what carries max_delta_step (``delta_step()``),
+        scale_pos_weight, tweedie_variance_power and huber_slope (a
+        :class:`GBDTParam`); None: their defaults."""
         if name not in ("binary:logistic", "reg:logistic", "reg:linear", "reg:squarederror",
-                        "binary:logitraw", "multi:softmax", "multi:softprob") + RANK_OBJECTIVES:
+                        "binary:logitraw", "multi:softmax", "multi:softprob") + RANK_OBJECTIVES \
+                and name not in OBJ_IDS:
             raise ValueError("unknown objective " + name)
         self.name = name
         self.rank = name in RANK_OBJECTIVES
@@ -235,6 +303,24 @@ class Objective:
         if self.multi and int(num_class) < 2:
             raise ValueError("objective %s needs num_class >= 2 (got %d)" % (name, num_class))
         self.num_class = int(num_class) if self.multi else 0
+        self.log_link = name in LOG_LINK_OBJECTIVES
+        if param is not None:
+            check_objective_scalars(param)
+        self.rho = float(getattr(param, "tweedie_variance_power", 1.5))
+        self.delta = float(getattr(param, "huber_slope", 1.0))
+        self.pos_weight = float(getattr(param, "scale_pos_weight", 1.0))
+        # (count:poisson's hessian is exp(m + max_delta_step); the rule of
+        # GBDTParam.delta_step)
+        d = getattr(param, "max_delta_step", None)
+        self.max_delta_step = float(d) if d is not None else (
+            0.7 if name == "count:poisson" else 0.0)
+        if self.pos_weight != 1.0 and not self.logistic:
+            raise ValueError("scale_pos_weight=%g does not fit objective %s (the logistic family "
+                             "only)" % (self.pos_weight, name))
+        # the gradient kernel's id: a new objective's, or the logistic
+        # family's under scale_pos_weight (else the existing entry points)
+        self.obj_id = OBJ_IDS.get(name, OBJ_LOGISTIC if self.logistic and self.pos_weight != 1.0
+                                  else None)
 
     @property
     def n_group(self):
@@ -245,6 +331,16 @@ class Objective:
         """Multi-class labels must be integers in [0, num_class): decided on
         every rank together (the flag is allreduced before anyone raises, so
         no rank is left waiting in a collective)."""
+        rule = {"count:poisson": (lambda y: y < 0, "label must be non-negative"),
+                "reg:tweedie": (lambda y: y < 0, "label must be non-negative"),
+                "reg:gamma": (lambda y: y <= 0, "label must be positive"),
+                "binary:hinge": (lambda y: (y != 0) & (y != 1), "label must be 0 or 1"),
+                "reg:squaredlogerror": (lambda y: y <= -1, "label must be greater than -1"),
+                }.get(self.name)
+        if rule is not None:  # (a NaN label fails every rule's complement too)
+            bad = bool((rule[0](label) | (label != label)).any()) if label.numel() else False
+            if bsp.allreduce_scalar(1.0 if bad else 0.0, "max") > 0:
+                raise ValueError("objective %s: %s" % (self.name, rule[1]))
         if not self.multi:
             return
         bad = bool(((label < 0) | (label >= self.num_class) | (label != label.floor())).any()) \
@@ -254,7 +350,8 @@ class Objective:
 
     def check_metrics(self, names):
         for m in names:
-            if parse_rank_metric(m) is not None:  # any single-output objective, as in xgboost
+            # the ranking and the one-launch metrics: any single-output objective
+            if parse_rank_metric(m) is not None or parse_obj_metric(m) is not None:
                 if self.multi:
                     raise ValueError("eval_metric %s does not fit objective %s" % (m, self.name))
                 continue
@@ -270,15 +367,24 @@ class Objective:
             if not 0.0 < base < 1.0:
                 raise ValueError("base_score must be in (0,1) for logistic loss")
             return -math.log(1.0 / base - 1.0)
+        if self.log_link:
+            if not base > 0.0:
+                raise ValueError("base_score must be positive for objective " + self.name)
+            return math.log(base)
         return base
 
-    def gpair(self, margin, label, weight, group=None):
+    def gpair(self, margin, label, weight, group=None, pos_weight=True):
         """group: the rank objectives' query groups, a :class:`RankGroups`
-        (``DMatrix.group``) or the int32 offsets [Q + 1]."""
+        (``DMatrix.group``) or the int32 offsets [Q + 1]. pos_weight=False
+        leaves scale_pos_weight out, as weight=None leaves the instance
+        weights out (the hessians of the quantile sketch)."""
         if self.rank:
             return self._gpair_rank(margin, label, weight, group)
         if self.multi:
             return self._gpair_softmax(margin, label, weight)
+        oid = self.obj_id if pos_weight or self.obj_id != OBJ_LOGISTIC else None
+        if oid is not None:
+            return self._gpair_obj(oid, margin, label, weight)
         if margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32:
             # one launch; the root statistics ride along (gpair_stats)
             gp, st = _native.hip().gbdt_gpair(margin.contiguous(), label.contiguous(),
@@ -296,6 +402,23 @@ class Objective:
         if weight is not None:
             g, h = g * weight, h * weight
         return torch.stack([g, h], 1).float().contiguous()
+
+    def _gpair_obj(self, oid, margin, label, weight):
+        """The objectives of ``OBJ_IDS`` and the logistic family under
+        scale_pos_weight: on the GPU one launch of the gradient kernel
+        templated on the objective, with the root statistics; the fp32 torch
+        form (:func:`obj_gpair_torch`) is its reference and the CPU path."""
+        if (margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32
+                and (weight is None or weight.dtype == torch.float32)):
+            gp, st = _native.hip().gbdt_gpair_obj(
+                margin=margin.contiguous(), label=label.contiguous(),
+                weight=weight.contiguous() if weight is not None else None, objective=oid,
+                max_delta_step=self.max_delta_step, tweedie_variance_power=self.rho,
+                huber_slope=self.delta, scale_pos_weight=self.pos_weight)
+            gp._wh_stats = st
+            return gp
+        return obj_gpair_torch(oid, margin.float(), label.float(), weight, self.max_delta_step,
+                               self.rho, self.delta, self.pos_weight)
 
     def _gpair_rank(self, margin, label, weight, group):
         """The expectation of xgboost's random partner draw over a row's
@@ -344,6 +467,10 @@ class Objective:
             return torch.softmax(margin, 0).t().contiguous()
         if self.name in ("binary:logistic", "reg:logistic"):
             return torch.sigmoid(margin)
+        if self.log_link:
+            return torch.exp(margin)
+        if self.name == "binary:hinge":
+            return (margin > 0).to(margin.dtype)
         return margin
 
     def default_metric(self):
@@ -351,7 +478,47 @@ class Objective:
             return "merror"
         if self.rank:
             return "map"
+        own = {"count:poisson": "poisson-nloglik", "reg:gamma": "gamma-nloglik",
+               "reg:tweedie": "tweedie-nloglik@%g" % self.rho, "binary:hinge": "error",
+               "reg:pseudohubererror": "mphe", "reg:squaredlogerror": "rmsle"}.get(self.name)
+        if own is not None:
+            return own
         return "error" if self.name == "binary:logistic" else "rmse"
+
+    @property
+    def link(self):
+        """How a margin becomes the prediction (a GbdtLink id of
+        csrc/host/gbdt_objective.h)."""
+        if self.log_link:
+            return 1
+        if self.name in ("binary:logistic", "reg:logistic"):
+            return 2
+        return 3 if self.name == "binary:hinge" else 0
+
+    def _obj_metrics(self, parsed, margin, label, weight, bsp):
+        """{name: value} of the one-launch metrics ``parsed`` = {name: (slot,
+        rho)} of a set: per distinct rho (one, unless a set asks for several
+        tweedie-nloglik@rho) one evaluation -- on the GPU one launch,
+        ``gbdt_obj_eval`` -- and one allreduce of its sums and sum w."""
+        out = {}
+        rhos = sorted({rho for _, rho in parsed.values() if rho is not None}) or [None]
+        for k, rho in enumerate(rhos):
+            # (the metrics without a rho ride with the first one)
+            names = [m for m, (_, r) in parsed.items() if r == rho or (r is None and k == 0)]
+            mask = 0
+            for m in names:
+                mask |= 1 << parsed[m][0]
+            v = obj_eval_sums(margin, label, weight, self.link, mask,
+                              rho if rho is not None else self.rho, self.delta)
+            bsp.allreduce(v)
+            v = v.tolist()
+            den = v[-1] if v[-1] > 0 else 1.0
+            for m in names:
+                x = v[parsed[m][0]] / den
+                base = m.partition("@")[0]
+                out[m] = 2.0 * x if base == "gamma-deviance" else (
+                    math.sqrt(x) if base == "rmsle" else x)
+        return out
 
     def metrics(self, names, margin, label, weight, bsp, group=None):
         """Globally reduced metrics of a set from its margins. The ranking
@@ -366,14 +533,98 @@ class Objective:
         nll = -log(1e-16)."""
         self.check_metrics(names)
         if not self.multi:
-            p = self.pred(margin)
-            return [rank_metric(m, margin, label, group, bsp) if parse_rank_metric(m)
+            parsed = {m: parse_obj_metric(m) for m in names}
+            parsed = {m: v for m, v in parsed.items() if v is not None}
+            own = self._obj_metrics(parsed, margin, label, weight, bsp) if parsed else {}
+            p = self.pred(margin) if len(own) < len(names) else None
+            return [own[m] if m in own else
+                    rank_metric(m, margin, label, group, bsp) if parse_rank_metric(m)
                     else eval_metric(m, p, label, weight, bsp) for m in names]
         v = multi_eval_sums(margin, label, weight)
         bsp.allreduce(v)
         v = v.tolist()
         den = v[2] if v[2] > 0 else 1.0
         return [v[0] / den if m == "merror" else v[1] / den for m in names]
+
+
+def obj_gpair_torch(oid, margin, label, weight, max_delta_step=0.0, rho=1.5, delta=1.0,
+                    pos_weight=1.0):
+    """The gradient pairs [n, 2] of objective id ``oid`` (``OBJ_IDS``,
+    ``OBJ_LOGISTIC``) in plain torch, in the margins' precision and the
+    operation order of csrc/host/gbdt_objective.h: the CPU path and the
+    reference of ``gbdt_gpair_obj`` (docs/bsp_apps.md "Objectives and
+    max_delta_step" has the table)."""
+    m, y = margin, label.to(margin.dtype)
+    w = weight.to(m.dtype) if weight is not None else None
+    final = None  # rows whose pair the weight does not multiply
+    if oid == OBJ_LOGISTIC:
+        p = torch.sigmoid(m)
+        g, h = p - y, torch.clamp(p * (1.0 - p), min=1e-16)
+        if pos_weight != 1.0:
+            s = torch.where(y == 1, torch.full_like(y, pos_weight), torch.ones_like(y))
+            w = s if w is None else w * s
+    elif oid == OBJ_IDS["count:poisson"]:
+        g, h = torch.exp(m) - y, torch.exp(m + max_delta_step)
+    elif oid == OBJ_IDS["reg:gamma"]:
+        r = y / torch.exp(m)
+        g, h = 1.0 - r, r
+    elif oid == OBJ_IDS["reg:tweedie"]:
+        c1, c2 = 1.0 - rho, 2.0 - rho
+        e1, e2 = torch.exp(c1 * m), torch.exp(c2 * m)
+        g, h = -y * e1 + e2, -y * c1 * e1 + c2 * e2
+    elif oid == OBJ_IDS["binary:hinge"]:
+        ys = 2.0 * y - 1.0
+        final = ~(m * ys < 1.0)
+        g = torch.where(final, torch.zeros_like(m), -ys)
+        h = torch.where(final, torch.full_like(m, FLT_MIN), torch.ones_like(m))
+    elif oid == OBJ_IDS["reg:pseudohubererror"]:
+        z, d2 = m - y, delta * delta
+        s = torch.sqrt(1.0 + z * z / d2)
+        g, h = z / s, d2 / ((d2 + z * z) * s)
+    elif oid == OBJ_IDS["reg:squaredlogerror"]:
+        mm = torch.clamp(m, min=SQUARED_LOG_MIN_MARGIN)
+        lm, ly, d = torch.log1p(mm), torch.log1p(y), mm + 1.0
+        g, h = (lm - ly) / d, torch.clamp((1.0 - lm + ly) / (d * d), min=1e-6)
+    else:
+        raise ValueError("unknown objective id %r" % (oid,))
+    if w is not None:
+        gw, hw = g * w, h * w
+        g, h = (gw, hw) if final is None else (torch.where(final, g, gw), torch.where(final, h, hw))
+    return torch.stack([g, h], 1).float().contiguous()
+
+
+def obj_eval_sums(margin, label, weight, link, mask, rho=1.5, delta=1.0):
+    """fp64 [8]: {sum w loss_j} of this rank's rows for the ``OBJ_METRICS``
+    slots j of ``mask`` (the others 0), then sum w; link: 0 the margin is the
+    prediction, 1 exp, 2 sigmoid, 3 [margin > 0]. On the GPU one launch
+    (``gbdt_obj_eval``: every loss in double from the fp32 inputs); the torch
+    form on ``margin.double()`` is its reference and the CPU path."""
+    if (margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32
+            and (weight is None or weight.dtype == torch.float32)):
+        return _native.hip().gbdt_obj_eval(
+            margin=margin.contiguous(), label=label.contiguous(),
+            weight=weight.contiguous() if weight is not None else None, link=link, mask=mask,
+            tweedie_variance_power=rho, huber_slope=delta)
+    out = torch.zeros(len(OBJ_METRICS) + 1, dtype=torch.float64, device=margin.device)
+    if label.numel() == 0:
+        return out
+    m, y = margin.double(), label.double()
+    w = weight.double() if weight is not None else torch.ones_like(y)
+    p = (m, torch.exp(m), torch.sigmoid(m), (m > 0).double())[link]
+    q = p.clamp(min=1e-16)
+    d2 = delta * delta
+    loss = (lambda: torch.lgamma(y + 1.0) + q - y * torch.log(q),
+            lambda: y / q + torch.log(q),
+            lambda: torch.log((p + 1e-16) / (y + 1e-16)) + (y + 1e-16) / (p + 1e-16) - 1.0,
+            lambda: -y * torch.pow(p, 1.0 - rho) / (1.0 - rho) + torch.pow(p, 2.0 - rho) / (2.0 - rho),
+            lambda: (p - y).abs(),
+            lambda: d2 * (torch.sqrt(1.0 + (p - y) ** 2 / d2) - 1.0),
+            lambda: (torch.log1p(y) - torch.log1p(p)) ** 2)
+    for j, f in enumerate(loss):
+        if mask >> j & 1:
+            out[j] = (w * f()).sum()
+    out[-1] = w.sum()
+    return out
 
 
 def first_argmax(margin):

@@ -260,7 +260,7 @@ class Booster:
         self.param = param
         self.num_feature = int(num_feature)
         self.trees = []
-        self.obj = Objective(param.objective, param.num_class)
+        self.obj = Objective(param.objective, param.num_class, param)
         self.base_margin = self.obj.prob_to_margin(param.base_score)
 
     # Trees from which a GPU matrix is predicted by the forest kernels (one
