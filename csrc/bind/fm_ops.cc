@@ -853,6 +853,9 @@ void bind_fm(py::module_& m) {
   m.def("set_fm_bwd_pack", [](bool on) { wh::fm_set_bwd_pack(on); },
         "FM backward: pack small single-chunk keys, one lane group per key (default on)");
   m.def("fm_bwd_pack", []() { return wh::fm_bwd_pack(); });
+  m.def("set_fm_fwd_depth", [](int64_t d) { wh::fm_set_fwd_depth((int)d); },
+        "FM forward: 10 = a headline row's gathers in one batch; anything else = batches of 4 (default)");
+  m.def("fm_fwd_depth", []() { return (int64_t)wh::fm_fwd_depth(); });
   m.def("fm_backward", &fm_backward);
   m.def("fm_backward_plan", &fm_backward_plan, py::arg("csc_off"), py::arg("csc_row"),
         py::arg("hdr"), py::arg("vc_rows"), py::arg("nrows"), py::arg("vstride"),

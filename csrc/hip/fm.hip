@@ -38,7 +38,8 @@ namespace {
 
 constexpr int kThreads = 256;
 // cap of the persistent forward grid; resident_blocks sizes it to what fits
-// (k_fm_fwd<16>: 116 VGPRs, 4 waves per SIMD = 4 blocks per CU)
+// the deep instantiation (k_fm_fwd<16, 10>: 126 VGPRs, 4 waves per SIMD = 4
+// blocks per CU; k_fm_fwd<16, 4> needs 94 and runs on the same grid)
 constexpr int kFwdBlocks = 2048;
 
 // Memory-level parallelism decides both FM kernels: every V / xv row is a
@@ -49,7 +50,8 @@ constexpr int kFwdBlocks = 2048;
 // issuing 8 rows at a time vs 65 us with ONE WAVE PER ROW issuing all its rows
 // at once (15 TB/s), so both kernels use the wave-per-item shape:
 //   lanes = SUB sub-groups x G lanes (G = vstride/4, a float4 slice each);
-//   one wave-instruction gathers SUB rows; up to TI instructions in flight.
+//   one wave-instruction gathers SUB rows; up to TI (backward) / FwdDepth
+//   (forward) instructions in flight.
 template <int G>
 struct Shape {
   static constexpr int SUB = 64 / G;             // rows per wave-instruction
@@ -65,8 +67,28 @@ struct Shape {
   static constexpr int VS = 4 * G;               // row stride in floats (= vstride)
 };
 
-// A gather slot without a row reads this zero row instead of branching
-// around the load (a predicated load costs an exec-mask branch per gather).
+// Instructions per gather batch of the forward's DEEP schedule
+// (WH_FM_FWD_DEPTH=10; the default is Shape::TI, as in k_bwd_v). At G = 16 it
+// covers 40 compacted slots, a whole headline row (37 embedded ids on average):
+// one wait per row instead of three. What makes it fit 4 waves per SIMD: one
+// base pointer with 32-bit element offsets, dead slots gathering the pass's
+// first row, the scalars re-read from the LDS stage at accumulate time
+// (126 VGPRs; with a per-slot pointer pair and the scalars held in registers
+// 8-deep batches took 154 VGPRs and 3 waves). Measured
+// (profiles/fm_fwd_rowbatch.txt): alone k_fm_fwd<16> runs 121.6 us deep
+// against 136.7 us 4-deep (133.6 us before the register diet); inside the
+// headline step, beside the localize and AUC streams, the deep schedule is
+// level or behind (587.8-596.5 against 579.9-590.0 us per step), so it is not
+// the default. The other widths keep TI: they are not the headline and their
+// occupancy must not fall.
+template <int G>
+struct FwdDepth {
+  static constexpr int kDeep = G == 16 ? 10 : Shape<G>::TI;
+};
+
+// A backward gather slot without a row reads this zero row instead of
+// branching around the load (a predicated load costs an exec-mask branch per
+// gather). The forward has one base and zeroes a dead slot's value instead.
 __device__ float kZeroRow[256];
 
 // Per-wave LDS staging of the 64 (row index, scalar) pairs of a pass, stored
@@ -101,7 +123,7 @@ __device__ __forceinline__ int stage_pairs_compact(int2* st, int lane, int vid, 
   return nv;
 }
 
-template <int G>
+template <int G, int FI>
 __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_t* __restrict__ off,
                                                      const int32_t* __restrict__ lid,
                                                      const float* __restrict__ val,
@@ -117,7 +139,10 @@ __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_
   // four: while row i's embedding rows are gathered, the headers of row i+1,
   // the ids of row i+2 and the CSR bounds of row i+3 are in flight. The
   // gathers are issued first and the prefetches after them, so the in-order
-  // vmcnt wait before the accumulation covers the gathers only.
+  // vmcnt wait before the accumulation covers the gathers only. A pass of 64
+  // ids gathers its compacted slots in batches of SUB x FI (FI: Shape::TI,
+  // or FwdDepth::kDeep behind WH_FM_FWD_DEPTH=10), one wait per batch; the
+  // per-lane sums run over the slots in ascending order whatever FI is.
   using S = Shape<G>;
   __shared__ double sh[kThreads / 64];
   __shared__ int2 stage[kThreads / 64][64];
@@ -147,26 +172,36 @@ __global__ __launch_bounds__(kThreads) void k_fm_fwd(int64_t nrows, const int64_
   auto gather = [&](int vid, float x, float4& s, float4& q2, bool prefetch_first,
                     auto&& prefetch) {
     const int n = stage_pairs_compact<G>(st, lane, vid, x);
+    if (n == 0) return;
+    // a dead slot gathers the pass's first row (always live, and one base
+    // serves every slot); its value is zeroed below, never multiplied: 0 x Inf
+    const uint32_t row0 = (uint32_t)st[0].x;
 #pragma unroll
-    for (int t0 = 0; t0 < S::NI; t0 += S::TI) {
+    for (int b = 0; b < (S::NI + FI - 1) / FI; ++b) {
+      const int t0 = b * FI;
       if (t0 * S::SUB >= n) break;
-      float4 v[S::TI];
-      float xs[S::TI];
+      float4 v[FI];
 #pragma unroll
-      for (int t = 0; t < S::TI; ++t) {
-        const int2 e = st[sub * S::NI + t0 + t];
+      for (int t = 0; t < FI; ++t) {
+        if (t0 + t >= S::NI) continue;                  // (the last batch of a pass is shorter)
         const bool live = (t0 + t) * S::SUB + sub < n;  // compacted slots only
-        xs[t] = live ? __int_as_float(e.y) : 0.f;
-        const float* src = live ? vc + (uint32_t)e.x * (uint32_t)S::VS : kZeroRow;
-        v[t] = reinterpret_cast<const float4*>(src)[gl];
+        const uint32_t row = live ? (uint32_t)st[sub * S::NI + t0 + t].x : row0;
+        v[t] = reinterpret_cast<const float4*>(vc + row * (uint32_t)S::VS)[gl];
       }
       if (t0 == 0 && prefetch_first) prefetch();
+      // the scalars are read from the stage again here, not held in registers
+      // beside the gathers in flight (the barrier keeps the two reads apart)
+      asm volatile("" ::: "memory");
 #pragma unroll
-      for (int t = 0; t < S::TI; ++t) {
-        const float xu = xs[t], xx = xu * xu;
-        s.x += xu * v[t].x; s.y += xu * v[t].y; s.z += xu * v[t].z; s.w += xu * v[t].w;
-        q2.x += xx * v[t].x * v[t].x; q2.y += xx * v[t].y * v[t].y;
-        q2.z += xx * v[t].z * v[t].z; q2.w += xx * v[t].w * v[t].w;
+      for (int t = 0; t < FI; ++t) {
+        if (t0 + t >= S::NI) continue;
+        const bool live = (t0 + t) * S::SUB + sub < n;
+        const float xu = live ? __int_as_float(st[sub * S::NI + t0 + t].y) : 0.f;
+        const float xx = xu * xu;
+        const float4 u = live ? v[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+        s.x += xu * u.x; s.y += xu * u.y; s.z += xu * u.z; s.w += xu * u.w;
+        q2.x += xx * u.x * u.x; q2.y += xx * u.y * u.y;
+        q2.z += xx * u.z * u.z; q2.w += xx * u.w * u.w;
       }
     }
   };
@@ -421,64 +456,90 @@ __global__ __launch_bounds__(kThreads) void k_vchunk_hist(const int64_t* __restr
   for (int i = threadIdx.x; i < D; i += kThreads) hist[blockIdx.x * D + i] = h[i];
 }
 
-// one block of 1024: hist[block][digit] -> digit-major exclusive offsets in
-// place. 1024 / D threads per digit each own a share of the blocks, so every
-// load is independent (the serial per-digit walk took ~15-20 us of load
-// latency); the D digit totals are scanned by the first D / 64 waves. A
-// thread keeps up to 32 counts in registers; with 64 (D = 512: 1024 threads
-// leave 128 VGPRs each, which 64 counts and their addresses exceed) it reads
-// them again from L2 for the second pass.
+// hist[block][digit] -> each count's exclusive offset WITHIN its digit, in
+// place, plus the D digit totals in tot[]. kScanBlocks blocks of 1024 own
+// D / kScanBlocks digits each; a thread loads kBucketBlocks / kParts counts
+// (4 at D = 512, 2 at D = 256: coalesced over the digits, all in flight
+// together), and the kParts partial sums of a digit are scanned by shuffles
+// in one wave after a transpose through LDS. The scan over the digit totals
+// is left to the scatter (digit_bases). One block of 1024 with 64 counts per
+// thread spilled at D = 512 (128 VGPRs, 128 bytes of scratch per lane) and
+// took 20.0 us where D = 256 took 4.8 (profiles/fm_bwd_packed.txt); this one:
+// 21 / 16 VGPRs, no scratch, 2.9 / 2.7 us (profiles/fm_fwd_rowbatch.txt).
 constexpr int kScanThreads = 1024;
+constexpr int kScanBlocks = 16;
 
 template <int D>
-__global__ __launch_bounds__(kScanThreads) void k_vchunk_scan(int32_t* hist) {
-  constexpr int kParts = kScanThreads / D, kPer = kBucketBlocks / kParts;
-  constexpr int kKeep = kPer <= 32 ? kPer : 32;
-  __shared__ int32_t part[kParts][D];
-  __shared__ int32_t excl[D];
-  __shared__ int32_t wtot[D / 64];
-  const int b = threadIdx.x & (D - 1), q = threadIdx.x / D;
-  int32_t v[kKeep];
+__global__ __launch_bounds__(kScanThreads) void k_vchunk_scan(int32_t* hist, int32_t* tot) {
+  constexpr int kOwn = D / kScanBlocks;          // digits of this block: 32 / 16
+  constexpr int kParts = kScanThreads / kOwn;    // threads per digit: 32 / 64
+  constexpr int kPer = kBucketBlocks / kParts;   // counts per thread: 4 / 2
+  static_assert(kParts <= 64 && kPer * kParts == kBucketBlocks, "one wave scans a digit");
+  __shared__ int32_t part[kParts][kOwn + 1];
+  const int dl = threadIdx.x % kOwn, q = threadIdx.x / kOwn;
+  const int d = blockIdx.x * kOwn + dl;
+  int32_t v[kPer];
   int32_t sum = 0;
 #pragma unroll
-  for (int i0 = 0; i0 < kPer; i0 += kKeep) {
+  for (int i = 0; i < kPer; ++i) v[i] = hist[(q * kPer + i) * D + d];
 #pragma unroll
-    for (int i = 0; i < kKeep; ++i) v[i] = hist[(q * kPer + i0 + i) * D + b];
-#pragma unroll
-    for (int i = 0; i < kKeep; ++i) sum += v[i];
-  }
-  part[q][b] = sum;
+  for (int i = 0; i < kPer; ++i) sum += v[i];
+  part[q][dl] = sum;
   __syncthreads();
-  if (q == 0) {  // digit totals -> wave-local inclusive scans
-    int32_t t = 0;
-#pragma unroll
-    for (int r = 0; r < kParts; ++r) t += part[r][b];
-    const int lane = b & 63;
+  {  // transposed: the kParts lanes of a digit side by side in one wave
+    const int tq = threadIdx.x % kParts, td = threadIdx.x / kParts;
+    const int32_t t = part[tq][td];
     int32_t x = t;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int32_t y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
+    for (int o = 1; o < kParts; o <<= 1) {
+      const int32_t y = __shfl_up(x, o, kParts);
+      if (tq >= o) x += y;
     }
-    if (lane == 63) wtot[b >> 6] = x;
-    excl[b] = x - t;
+    part[tq][td] = x - t;
+    if (tq == kParts - 1) tot[blockIdx.x * kOwn + td] = x;
   }
   __syncthreads();
-  int32_t base = excl[b];
-  for (int w = 0; w < (b >> 6); ++w) base += wtot[w];
-  for (int r = 0; r < q; ++r) base += part[r][b];
+  int32_t base = part[q][dl];
 #pragma unroll
-  for (int i0 = 0; i0 < kPer; i0 += kKeep) {
-    if (kPer > kKeep) {
-#pragma unroll
-      for (int i = 0; i < kKeep; ++i) v[i] = hist[(q * kPer + i0 + i) * D + b];
-    }
-#pragma unroll
-    for (int i = 0; i < kKeep; ++i) {
-      hist[(q * kPer + i0 + i) * D + b] = base;
-      base += v[i];
-    }
+  for (int i = 0; i < kPer; ++i) {
+    hist[(q * kPer + i) * D + d] = base;
+    base += v[i];
   }
+}
+
+// base[digit] (LDS) = exclusive scan of the D digit totals + this block's
+// offset within the digit: every scatter block scans the totals for itself
+template <int D>
+__device__ __forceinline__ void digit_bases(const int32_t* __restrict__ tot,
+                                            const int32_t* __restrict__ within, int32_t* base,
+                                            int32_t* wsum) {
+  constexpr int kPer = D / kThreads;
+  static_assert(kPer * kThreads == D, "digits split evenly over the block");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t t[kPer], w[kPer];
+  int32_t sum = 0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    t[j] = tot[threadIdx.x * kPer + j];
+    w[j] = within[threadIdx.x * kPer + j];
+    sum += t[j];
+  }
+  int32_t x = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  int32_t off = x - sum;
+  for (int k = 0; k < wave; ++k) off += wsum[k];
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    base[threadIdx.x * kPer + j] = off + w[j];
+    off += t[j];
+  }
+  __syncthreads();
 }
 
 template <int D>
@@ -487,10 +548,11 @@ __global__ __launch_bounds__(kThreads) void k_vchunk_scatter(const int64_t* __re
                                                              const int32_t* __restrict__ csc_row,
                                                              int shift, int small_n,
                                                              const int32_t* __restrict__ hist,
+                                                             const int32_t* __restrict__ tot,
                                                              int4* out) {
   __shared__ int32_t base[D];
-  for (int i = threadIdx.x; i < D; i += kThreads) base[i] = hist[blockIdx.x * D + i];
-  __syncthreads();
+  __shared__ int32_t wsum[kThreads / 64];
+  digit_bases<D>(tot, hist + blockIdx.x * D, base, wsum);
   const int64_t n = *nchunk_p;
   const int64_t per = (n + gridDim.x - 1) / gridDim.x;
   const int64_t c0 = per * blockIdx.x, c1 = c0 + per < n ? c0 + per : n;
@@ -989,6 +1051,23 @@ bool fm_bwd_pack() {
   return g_bwd_pack == 1;
 }
 
+// k_fm_fwd issues Shape<G>::TI gather instructions per batch, as k_bwd_v does
+// (4, the default). WH_FM_FWD_DEPTH=10 / fm_set_fwd_depth(10): batches of
+// FwdDepth<G>::kDeep, a headline row's 40 slots at once -- the same bits for
+// every input (per-lane sums run over the slots in the same order). Alone the
+// deep kernel is 15 us faster, inside the step it is not (FwdDepth, above);
+// kept for A/B and the tests.
+static int g_fwd_depth = -1;
+
+void fm_set_fwd_depth(int depth) { g_fwd_depth = depth == 10 ? 10 : 4; }
+int fm_fwd_depth() {
+  if (g_fwd_depth < 0) {
+    const char* e = std::getenv("WH_FM_FWD_DEPTH");
+    g_fwd_depth = e && std::string(e) == "10" ? 10 : 4;
+  }
+  return g_fwd_depth;
+}
+
 static int device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -1028,10 +1107,17 @@ void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const 
   const float2* hdr = reinterpret_cast<const float2*>(w_or_hdr);
   dispatch_g(vstride / 4, [&](auto g) {
     constexpr int G = decltype(g)::value;
-    const int nblk =
-        grid_for(nrows * 64, kThreads, resident_blocks(k_fm_fwd<G>, kFwdBlocks));
-    hipLaunchKernelGGL(k_fm_fwd<G>, dim3(nblk), dim3(kThreads), 0, s, nrows, offset, lid, val,
-                       hdr, vc, vstride, label, loss, py, dual, xv, part, met, ticket, acc5);
+    // one grid for both depths (the deep kernel's, the larger register count):
+    // the rows of a wave, and with them the order of the metric sums, do not
+    // depend on the switch
+    const int nblk = grid_for(nrows * 64, kThreads,
+                              resident_blocks(k_fm_fwd<G, FwdDepth<G>::kDeep>, kFwdBlocks));
+    auto run = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nblk), dim3(kThreads), 0, s, nrows, offset, lid, val, hdr,
+                         vc, vstride, label, loss, py, dual, xv, part, met, ticket, acc5);
+    };
+    if (fm_fwd_depth() == 10) run(k_fm_fwd<G, FwdDepth<G>::kDeep>);
+    else run(k_fm_fwd<G, Shape<G>::TI>);
   });
 }
 
@@ -1071,7 +1157,8 @@ int64_t fm_bwd_layout(int64_t nuniq, int64_t nnz, int vstride, bool deterministi
   l.key_s = carve(cap_s * 4);
   l.beg_s = carve(cap_s * 4);
   l.meta_v = carve(2 * cap_v * 16);
-  l.hist = carve(vstride > 0 ? (int64_t)kDigits * kBucketBlocks * 4 : 0);
+  // block histograms, then the digit totals
+  l.hist = carve(vstride > 0 ? (int64_t)kDigits * (kBucketBlocks + 1) * 4 : 0);
   l.det_s = carve(deterministic ? cap_s * 4 : 0);
   l.det_vw = carve(deterministic ? cap_v * 4 : 0);
   l.det_v = carve(deterministic ? cap_v * vstride * 4 : 0);
@@ -1137,6 +1224,7 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
   }
   if (phase != FmBwdPhase::kRun && bucket) {
     int32_t* hist = reinterpret_cast<int32_t*>(base + l.hist);
+    int32_t* tot = hist + kDigits * kBucketBlocks;
     const int shift = bucket_shift(std::max<int64_t>(p.nrows, 1));
     // the chunks k_bwd_v packs: <= TI occurrences, where a wave holds 2+ keys
     const int G = vstride / 4;
@@ -1145,9 +1233,11 @@ void fm_backward(const FmBwdProblem& p, void* scratch, const Lookback* lb, hipSt
       constexpr int D = decltype(d)::value;
       hipLaunchKernelGGL(k_vchunk_hist<D>, dim3(kBucketBlocks), dim3(kThreads), 0, s,
                          off_v + nuniq, meta_v, p.csc_row, shift, small_n, hist);
-      hipLaunchKernelGGL(k_vchunk_scan<D>, dim3(1), dim3(kScanThreads), 0, s, hist);
+      hipLaunchKernelGGL(k_vchunk_scan<D>, dim3(kScanBlocks), dim3(kScanThreads), 0, s, hist,
+                         tot);
       hipLaunchKernelGGL(k_vchunk_scatter<D>, dim3(kBucketBlocks), dim3(kThreads), 0, s,
-                         off_v + nuniq, meta_v, p.csc_row, shift, small_n, hist, meta_sorted);
+                         off_v + nuniq, meta_v, p.csc_row, shift, small_n, hist, tot,
+                         meta_sorted);
     };
     // the class bit only where there are small chunks to put side by side
     if (small_n > 0) sort(std::integral_constant<int, kDigits>());

@@ -331,6 +331,12 @@ int fm_cu_reserve();
 // per key (default; WH_FM_BWD_PACK=0 or false here: one iteration per chunk)
 void fm_set_bwd_pack(bool on);
 bool fm_bwd_pack();
+// The forward gathers in batches of min(vstride / 4, 4) instructions
+// (fm_fwd_depth() == 4, the default). WH_FM_FWD_DEPTH=10 or 10 here: a whole
+// headline row's gathers per batch (vstride 64: 10 instructions, 40 slots),
+// the same bits
+void fm_set_fwd_depth(int depth);
+int fm_fwd_depth();
 void fm_forward(int64_t nrows, const int64_t* offset, const int32_t* lid, const float* val,
                 const float* w_or_hdr, const float* vc, int vstride, const float* label, int loss,
                 float* py, float* dual, float* xv, double* met, double* part,

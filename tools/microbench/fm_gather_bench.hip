@@ -7,6 +7,11 @@
 //   D  one wave per row, 4 V rows per wave-instruction, all 39 rows issued
 //      before any use (max MLP)
 //   E  like A but rows of a wave sorted so that G-groups read the SAME field
+//   P4 / P10  the shape of k_fm_fwd<16>: persistent waves, one row at a time,
+//      the next row's ids and headers in flight behind the gathers, the
+//      (row, scalar) pairs compacted into an LDS stage, s and q2 accumulated;
+//      4 or 10 gather instructions (16 / 40 rows) per batch. The grid sets the
+//      occupancy: W blocks of 256 per CU = W waves per SIMD.
 // Build: hipcc -O3 --offload-arch=gfx950 -o /tmp/fmgb tools/microbench/fm_gather_bench.hip
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -88,6 +93,80 @@ __global__ __launch_bounds__(256) void k_d(int nrows, const int* lid, const floa
   if (sub == 0) reinterpret_cast<float4*>(out + (size_t)row * DIM)[gl] = s;
 }
 
+// k_fm_fwd<16>'s loop with FI gather instructions per batch (see fm.hip)
+template <int FI>
+__global__ __launch_bounds__(256) void k_p(int nrows, const int* lid, const float2* hdr,
+                                           const float* vc, float* out) {
+  constexpr int SUB = 4, NI = 16;
+  __shared__ int2 stage[4][64];
+  int2* st = stage[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63, gl = lane & 15, sub = lane >> 4;
+  const int nw = gridDim.x * 4;
+  int r = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * 256 + threadIdx.x) >> 6));
+  auto load_l = [&](int row) { return row < nrows && lane < NF ? lid[row * NF + lane] : -1; };
+  auto load_h = [&](int l) { return l >= 0 ? hdr[l] : make_float2(0.f, __int_as_float(-1)); };
+  float2 hc = load_h(load_l(r)), hn = hc;
+  int ln = load_l(r + nw), l2 = -1;
+  for (; r < nrows; r += nw) {
+    const int vid = __float_as_int(hc.y);
+    const float x = 1.f;
+    const bool has = vid >= 0;
+    const unsigned long long m = __ballot(has);
+    const int n = __popcll(m), pos = __popcll(m & ((1ull << lane) - 1ull));
+    if (has) st[(pos % SUB) * NI + pos / SUB] = make_int2(vid, __float_as_int(x));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q2 = s;
+    const unsigned row0 = (unsigned)st[0].x;
+    bool fetched = false;
+#pragma unroll
+    for (int b = 0; b < (NI + FI - 1) / FI; ++b) {
+      const int t0 = b * FI;
+      if (t0 * SUB >= n) break;
+      float4 v[FI];
+#pragma unroll
+      for (int t = 0; t < FI; ++t) {
+        if (t0 + t >= NI) continue;
+        const bool live = (t0 + t) * SUB + sub < n;
+        const unsigned row = live ? (unsigned)st[sub * NI + t0 + t].x : row0;
+        v[t] = reinterpret_cast<const float4*>(vc + row * (unsigned)DIM)[gl];
+      }
+      if (t0 == 0) {
+        hn = load_h(ln);
+        l2 = load_l(r + 2 * nw);
+        fetched = true;
+      }
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int t = 0; t < FI; ++t) {
+        if (t0 + t >= NI) continue;
+        const bool live = (t0 + t) * SUB + sub < n;
+        const float xu = live ? __int_as_float(st[sub * NI + t0 + t].y) : 0.f, xx = xu * xu;
+        const float4 u = live ? v[t] : make_float4(0.f, 0.f, 0.f, 0.f);
+        s.x += xu * u.x; s.y += xu * u.y; s.z += xu * u.z; s.w += xu * u.w;
+        q2.x += xx * u.x * u.x; q2.y += xx * u.y * u.y;
+        q2.z += xx * u.z * u.z; q2.w += xx * u.w * u.w;
+      }
+    }
+    if (!fetched) {
+      hn = load_h(ln);
+      l2 = load_l(r + 2 * nw);
+    }
+    for (int o = 16; o < 64; o <<= 1) {
+      s.x += __shfl_xor(s.x, o, 64); s.y += __shfl_xor(s.y, o, 64);
+      s.z += __shfl_xor(s.z, o, 64); s.w += __shfl_xor(s.w, o, 64);
+      q2.x += __shfl_xor(q2.x, o, 64); q2.y += __shfl_xor(q2.y, o, 64);
+      q2.z += __shfl_xor(q2.z, o, 64); q2.w += __shfl_xor(q2.w, o, 64);
+    }
+    const float pt = (s.x * s.x - q2.x) + (s.y * s.y - q2.y) + (s.z * s.z - q2.z) + (s.w * s.w - q2.w);
+    if (sub == 0)
+      reinterpret_cast<float4*>(out + (size_t)r * DIM)[gl] = make_float4(s.x + pt + hc.x, s.y, s.z, s.w);
+    hc = hn;
+    ln = l2;
+  }
+}
+
 int main() {
   const int nrows = 100000;
   const long card[NF] = {64, 3000, 2000, 500, 200000, 10000, 3000, 500, 6000, 20, 200, 1000, 600,
@@ -147,5 +226,11 @@ int main() {
   run("B  no V gathers", [&] { k_a<1><<<gA, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
   run("C  V index & 1023 (L2 resident)", [&] { k_a<2><<<gA, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
   run("D  wave/row, 10 instr (40 rows) in flight", [&] { k_d<<<gD, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
+  int cus = 0;
+  CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+  run("P4   k_fm_fwd shape, 4 instr/batch, 4 waves/SIMD", [&] { k_p<4><<<4 * cus, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
+  run("P10  k_fm_fwd shape, 10 instr/batch, 3 waves/SIMD", [&] { k_p<10><<<3 * cus, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
+  run("P10  k_fm_fwd shape, 10 instr/batch, 4 waves/SIMD", [&] { k_p<10><<<4 * cus, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
+  run("P4   k_fm_fwd shape, 4 instr/batch, 5 waves/SIMD", [&] { k_p<4><<<5 * cus, 256>>>(nrows, d_lid, d_hdr, d_vc, d_out); });
   return 0;
 }
