@@ -11,9 +11,10 @@ Two shared objects are produced next to the Python sources:
 * ``bin/native/{convert,text2crb}`` -- standalone C++ data conversion tools
   (reference learn/tool/), wrapped by ``bin/convert.dmlc`` / ``bin/text2crb.dmlc``.
 * ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test,
-  gbdt_shap_inter_test}`` -- stand-alone tests of host code (``--sanitize`` /
-  ``--sanitize-rank-plan`` / ``--sanitize-shap-plan`` / ``--sanitize-shap-inter``
-  build them under sanitizers).
+  gbdt_shap_inter_test,gbdt_dart_plan_test}`` -- stand-alone tests of host code
+  (``--sanitize`` / ``--sanitize-rank-plan`` / ``--sanitize-shap-plan`` /
+  ``--sanitize-shap-inter`` / ``--sanitize-dart-plan`` build them under
+  sanitizers).
 * ``wormhole_amd/_host.so`` -- the native C++ runtime (``csrc/host/*.cc``):
   proto-text config parser, data parsers (libsvm / criteo / adfea / crb),
   CityHash64, LZ4 block codec, RecordIO, workload pool, control-plane
@@ -150,6 +151,11 @@ def gen_ninja():
     lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, SHAP_INTER_TEST_SRC)))
     lines.append("build %s: link_tool %s" % (
         os.path.join(ROOT, "bin", "native", "gbdt_shap_inter_test"), obj))
+    # DART tree table and walk plan test (header only): bin/native/gbdt_dart_plan_test
+    obj = os.path.join(BUILD, "tool", "gbdt_dart_plan_test.o")
+    lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, DART_PLAN_TEST_SRC)))
+    lines.append("build %s: link_tool %s" % (
+        os.path.join(ROOT, "bin", "native", "gbdt_dart_plan_test"), obj))
     lines.append("build %s: link_hip %s" % (os.path.join(PKG, "_hip.so"), " ".join(hip_objs)))
     lines.append("build %s: link_host %s" % (os.path.join(PKG, "_host.so"), " ".join(host_objs)))
     os.makedirs(BUILD, exist_ok=True)
@@ -160,6 +166,7 @@ def gen_ninja():
 RANK_PLAN_TEST_SRC = "csrc/tests/gbdt_rank_plan_test.cc"
 SHAP_PLAN_TEST_SRC = "csrc/tests/gbdt_shap_plan_test.cc"
 SHAP_INTER_TEST_SRC = "csrc/tests/gbdt_shap_inter_test.cc"
+DART_PLAN_TEST_SRC = "csrc/tests/gbdt_dart_plan_test.cc"
 SELFTEST_SRCS = ("csrc/tests/host_selftest.cc", "csrc/host/parsers.cc", "csrc/host/io.cc",
                  "csrc/host/remote_fs.cc", "csrc/host/lz4.cc", "csrc/host/cityhash.cc", "csrc/host/workload_pool.cc",
                  "csrc/host/conf_parser.cc", "csrc/host/van.cc", "csrc/host/json.cc")
@@ -218,6 +225,14 @@ def build_shap_inter_sanitized():
     return _build_plan_test_sanitized("shap-inter", SHAP_INTER_TEST_SRC)
 
 
+def build_dart_plan_sanitized():
+    """The DART tree table and walk plan test (csrc/host/gbdt_dart_plan.h, its
+    own main) under -fsanitize=address,undefined:
+    build/san-dart-plan/gbdt_dart_plan_test. The plain build is
+    bin/native/gbdt_dart_plan_test."""
+    return _build_plan_test_sanitized("dart-plan", DART_PLAN_TEST_SRC)
+
+
 def build(jobs=None, clean=False, verbose=False):
     if clean and os.path.isdir(BUILD):
         shutil.rmtree(BUILD)
@@ -244,7 +259,12 @@ if __name__ == "__main__":
                     help="build the contribution plan test under address,undefined instead")
     ap.add_argument("--sanitize-shap-inter", action="store_true",
                     help="build the interaction references test under address,undefined instead")
+    ap.add_argument("--sanitize-dart-plan", action="store_true",
+                    help="build the DART plan test under address,undefined instead")
     a = ap.parse_args()
+    if a.sanitize_dart_plan:
+        print(build_dart_plan_sanitized())
+        sys.exit(0)
     if a.sanitize_shap_inter:
         print(build_shap_inter_sanitized())
         sys.exit(0)

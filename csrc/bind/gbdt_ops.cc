@@ -12,6 +12,7 @@
 #include <tuple>
 #include <utility>
 
+#include "host/gbdt_dart_plan.h"
 #include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
@@ -658,6 +659,94 @@ void gbdt_predict_forest_csr(const Tensor& row_off, const Tensor& fid,
                wh::gbdt_predict_forest_csr(ptr<int64_t>(row_off), ptr<int32_t>(fid),
                                            optptr<float>(val), n, c, o, s);
              });
+}
+
+// ------------------------------------------------------ DART dropout walk
+// booster=dart (host/gbdt_dart_plan.h, gbdt_dart.hip). A tree's 8-byte nodes
+// int32 [nn, 2] on the host, or None when the table does not admit it. bin:
+// the split bins where known, else None (recovered from cond and the cuts).
+py::object gbdt_dart_pack(std::vector<int64_t> feat, c10::optional<std::vector<int64_t>> bin,
+                          std::vector<double> cond, std::vector<int64_t> left,
+                          std::vector<int64_t> right, std::vector<int64_t> defl,
+                          std::vector<double> leaf, const std::vector<double>& cut_vals,
+                          const std::vector<int64_t>& cut_off) {
+  TORCH_CHECK(!cut_off.empty(), "gbdt_dart_pack: cut_off must be [F + 1]");
+  wh::GbdtDartTree t{std::move(feat), bin ? std::move(*bin) : std::vector<int64_t>(),
+                     std::move(left), std::move(right), std::move(defl), std::move(cond),
+                     std::move(leaf)};
+  std::vector<wh::GbdtDartNode> nodes;
+  if (!wh::gbdt_dart_pack(t, cut_vals, cut_off, &nodes)) return py::none();
+  auto tn = torch::empty({(int64_t)nodes.size(), 2}, torch::kInt32);
+  std::memcpy(tn.data_ptr(), nodes.data(), nodes.size() * sizeof(nodes[0]));
+  return py::cast(tn);
+}
+
+// (first, count, nnode, staged, stage_off) per chunk of the selection
+using DartChunks = std::vector<std::tuple<int64_t, int64_t, int64_t, bool, std::vector<int64_t>>>;
+
+DartChunks gbdt_dart_plan(const std::vector<int64_t>& tree_sizes, const std::vector<int64_t>& sel,
+                          int64_t lds_nodes) {
+  DartChunks out;  // (std::invalid_argument -> ValueError)
+  for (auto& c : wh::gbdt_dart_plan(tree_sizes, sel, lds_nodes))
+    out.emplace_back(c.first, c.count, c.nnode, c.staged, c.stage_off);
+  return out;
+}
+
+int64_t dart_rows(int64_t rows) {
+  TORCH_CHECK(rows >= 64 && rows <= 1024 && rows % 64 == 0,
+              "gbdt_dart: rows per tile must be a multiple of 64, at most 1024");
+  return rows;
+}
+
+int64_t gbdt_dart_grid(int64_t n, int64_t f, int64_t ntree, int64_t nnode, int64_t rows) {
+  return wh::gbdt_dart_grid(n, (int)f, (int)ntree, (int)nnode, (int)dart_rows(rows));
+}
+
+// One staged chunk: tree j is nodes [tree_off[j], tree_off[j] + tree_nn[j]) of
+// `table` (int32 [N, 2], device), staged at stage_off[j], weighted coef[j];
+// out float32 [n] (may be a view) is added to.
+void gbdt_dart_walk(const Tensor& B, const Tensor& table, const std::vector<int64_t>& tree_off,
+                    const std::vector<int64_t>& tree_nn, const std::vector<int64_t>& stage_off,
+                    const std::vector<double>& coef, const Tensor& out, int64_t rows) {
+  CHECK_IN(B, torch::kUInt8);
+  CHECK_IN(table, torch::kInt32);
+  CHECK_DEV(out);
+  CHECK_DT(out, torch::kFloat32);
+  dart_rows(rows);
+  TORCH_CHECK(B.dim() == 2 && B.size(1) >= 1 && B.size(1) <= wh::kDartMaxF &&
+                  reinterpret_cast<uintptr_t>(B.data_ptr()) % 4 == 0,
+              "gbdt_dart_walk: B must be a 4-byte aligned [n, f] with f <= ", wh::kDartMaxF);
+  const int64_t n = B.size(0), f = B.size(1);
+  TORCH_CHECK(out.dim() == 1 && out.size(0) == n && (n <= 1 || out.stride(0) == 1) &&
+                  out.device() == B.device() && table.device() == B.device(),
+              "gbdt_dart_walk: out must be [n] with unit stride on B's device");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == 2, "gbdt_dart_walk: table must be int32 [N, 2]");
+  const int64_t T = (int64_t)tree_off.size();
+  TORCH_CHECK((int64_t)tree_nn.size() == T && (int64_t)stage_off.size() == T &&
+                  (int64_t)coef.size() == T && T <= wh::kDartMaxTrees,
+              "gbdt_dart_walk: the chunk's lists differ or it has too many trees");
+  if (n == 0 || T == 0) return;
+  // the staging ranges tile [0, nnode) in list order, each tree inside the table
+  int64_t nnode = 0;
+  auto mh = torch::empty({T, 4}, torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
+  int32_t* m = mh.data_ptr<int32_t>();
+  for (int64_t j = 0; j < T; ++j) {
+    TORCH_CHECK(tree_nn[j] >= 1 && tree_nn[j] <= 65535 && tree_off[j] >= 0 &&
+                    tree_off[j] + tree_nn[j] <= table.size(0) && stage_off[j] == nnode,
+                "gbdt_dart_walk: tree ", j, " lies outside the table or its staging range");
+    nnode += tree_nn[j];
+    const float c = (float)coef[j];
+    m[4 * j] = (int32_t)tree_off[j], m[4 * j + 1] = (int32_t)tree_nn[j];
+    m[4 * j + 2] = (int32_t)stage_off[j];
+    std::memcpy(&m[4 * j + 3], &c, 4);
+  }
+  TORCH_CHECK(nnode <= wh::kDartLdsNodesMax &&
+                  wh::gbdt_dart_lds_bytes((int)f, (int)T, (int)nnode, (int)rows) <= 160 * 1024,
+              "gbdt_dart_walk: the chunk does not fit the LDS");
+  c10::DeviceGuard g(B.device());
+  auto md = mh.to(B.device(), /*non_blocking=*/true);
+  wh::gbdt_dart_walk(ptr<uint8_t>(B), n, (int)f, table.data_ptr(), md.data_ptr(), (int)T,
+                     (int)nnode, (int)rows, ptr<float>(out), cur_stream(B));
 }
 
 // ------------------------------------------------- feature contributions
@@ -1791,6 +1880,20 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_predict_forest_csr", &gbdt_predict_forest_csr, py::arg("row_off"), py::arg("fid"),
         py::arg("val"), py::arg("nodes"), py::arg("tree_off"), py::arg("chunks"), py::arg("out"),
         py::arg("leaf") = false);
+  // DART dropout walk: pack, plan and the budget need no GPU
+  m.def("gbdt_dart_pack", &gbdt_dart_pack, py::arg("feat"), py::arg("bin"), py::arg("cond"),
+        py::arg("left"), py::arg("right"), py::arg("defl"), py::arg("leaf"), py::arg("cut_vals"),
+        py::arg("cut_off"));
+  m.def("gbdt_dart_plan", &gbdt_dart_plan, py::arg("tree_sizes"), py::arg("sel"),
+        py::arg("lds_nodes"));
+  m.def("gbdt_dart_lds_nodes", &wh::gbdt_dart_lds_nodes);
+  m.def("gbdt_dart_max_f", [] { return (int64_t)wh::kDartMaxF; });
+  m.def("gbdt_dart_max_trees", [] { return (int64_t)wh::kDartMaxTrees; });
+  m.def("gbdt_dart_grid", &gbdt_dart_grid, py::arg("n"), py::arg("f"), py::arg("ntree"),
+        py::arg("nnode"), py::arg("rows"));
+  m.def("gbdt_dart_walk", &gbdt_dart_walk, py::arg("B"), py::arg("table"), py::arg("tree_off"),
+        py::arg("tree_nn"), py::arg("stage_off"), py::arg("coef"), py::arg("out"),
+        py::arg("rows"));
   // feature contributions: pack, plan, capacities and the host references
   // need no GPU
   m.def("gbdt_shap_pack", &gbdt_shap_pack, py::arg("feat"), py::arg("cond"), py::arg("left"),

@@ -719,6 +719,21 @@ void gbdt_predict_forest(const float* X, int64_t n, int f, const ForestChunk& c,
 void gbdt_predict_forest_csr(const int64_t* row_off, const int32_t* fid, const float* val,
                              int64_t n, const ForestChunk& c, const ForestOut& o, hipStream_t s);
 
+// ---------------------------------------------------------- gbdt_dart.hip
+// DART dropout walk over the resident bin matrix B [n, f] (u8, 255 = missing,
+// 4-byte aligned, f <= kDartMaxF): out[i] = out[i] + coef_j * leaf_j(row i)
+// for the ntree trees of `meta`, in its order, each product and sum rounded
+// to fp32. table: the device tree table of 8-byte nodes (host/
+// gbdt_dart_plan.h); meta [ntree] uint4 {first node in the table, nodes,
+// staging offset in the chunk, coef fp32 bits} on the device, the staging
+// ranges disjoint within nnode <= kDartLdsNodesMax nodes; rows: the block's
+// lanes = rows per tile (a multiple of 64, <= 1024);
+// gbdt_dart_lds_bytes(...) <= 160 KB. Nothing runs for n <= 0 or ntree <= 0.
+size_t gbdt_dart_lds_bytes(int f, int ntree, int nnode, int rows);
+int gbdt_dart_grid(int64_t n, int f, int ntree, int nnode, int rows);  // blocks of a launch
+void gbdt_dart_walk(const uint8_t* B, int64_t n, int f, const void* table, const void* meta,
+                    int ntree, int nnode, int rows, float* out, hipStream_t s);
+
 // ---------------------------------------------------------- gbdt_shap.hip
 // Per-feature contributions of a packed forest (host/gbdt_shap_plan.h), in
 // compact columns: out rows are [U1] = the model's used features and the

@@ -2,7 +2,9 @@
 xgboost CLI surface the reference drives (learn/xgboost/mushroom.hadoop.conf,
 learn/xgboost/run_yarn.sh; SURVEY §2.2 "xgboost"):
 
-tasks ``train | pred | dump | eval``; parameters booster, objective
+tasks ``train | pred | dump | eval``; parameters booster (gbtree | dart),
+rate_drop, skip_drop, one_drop, sample_type, normalize_type (booster=dart,
+below), objective
 (binary:logistic, binary:logitraw, reg:logistic, reg:linear,
 reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg,
 count:poisson, reg:gamma, reg:tweedie, binary:hinge, reg:pseudohubererror,
@@ -81,6 +83,23 @@ every node's weight to [-d, d] before eta. scale_pos_weight=s (s > 0)
 multiplies the weight of the rows with label 1 by s in the gradient pairs of
 the logistic objectives (not in the metrics); with another objective s != 1
 is an error (docs/bsp_apps.md "Objectives and max_delta_step").
+
+DART: ``booster=dart`` (task=train) drops earlier boosting rounds before it
+grows the next one. rate_drop (in [0, 1], default 0) is a round's chance of
+being dropped, skip_drop (in [0, 1], default 0) a round's chance of dropping
+nothing, one_drop=1 (0 | 1) drops one round when the draw chose none,
+sample_type=uniform | weighted (chances in proportion to the rounds' weights),
+normalize_type=tree | forest (with k dropped rounds the dropped weights are
+scaled by k / (k + eta) and the new trees weigh 1 / (k + eta); forest: both
+1 / (1 + eta)). An out-of-range or unknown value ends the run with an error
+that names the parameter; under booster=gbtree they are accepted and ignored.
+The unit of dropout is a round: the K trees of a multi: objective's round are
+dropped together (xgboost drops single trees across classes). The draw
+depends on seed and the round alone, so every rank drops the same rounds. A
+dart model stores one weight per tree after the trees; task=pred, eval and
+dump need no booster=, and task=dump prints the effective leaf values
+(weight x leaf; xgboost prints the unweighted ones). model_in continues a
+gbtree model with dart and a dart model with gbtree (docs/bsp_apps.md "DART").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -203,8 +222,6 @@ def main(argv):
             pass
         else:
             bsp.tracker_print("Warning: unknown parameter %s=%s ignored" % (k, v))
-    if param.booster != "gbtree":
-        raise SystemExit("only booster=gbtree is supported")
     if ntree_limit < 0:
         raise SystemExit("ntree_limit must not be negative")
     if pred_leaf and pred_margin:
@@ -400,15 +417,25 @@ def main(argv):
     B = cuts.bin(dtrain)
     builder = G.make_builder(param, bsp, dtrain, cuts, B)
     emargins = [booster.predict_margin(d) for _, d in deval]
+    dart = None
+    if param.booster == "dart":
+        dart = G.DartTrainer(booster, builder, dtrain, [(d, em) for (_, d), em in
+                                                        zip(deval, emargins)])
+        if start:  # (a continued dart model: its kept margins, replayed)
+            margin = dart.start_margin()
     gen = torch.Generator().manual_seed(param.seed + 17 * bsp.rank)
     fgen = torch.Generator().manual_seed(param.seed)
     for r in range(start, num_round):
-        new = G.boost_round(obj, builder, dtrain, margin, gen, fgen)  # K trees
-        booster.trees += new
+        if dart is not None:  # (appends the trees, updates the eval margins)
+            new = dart.round(r, margin, gen, fgen)
+        else:
+            new = G.boost_round(obj, builder, dtrain, margin, gen, fgen)  # K trees
+            booster.trees += new
         msg = "[%d]" % r
         for (name, d), em in zip(deval, emargins):
-            for k, tree in enumerate(new):
-                d.predict_tree(tree, em[k] if K > 1 else em)
+            if dart is None:
+                for k, tree in enumerate(new):
+                    d.predict_tree(tree, em[k] if K > 1 else em)
             for m, v in zip(metrics, obj.metrics(metrics, em, d.label, d.weight, bsp,
                                                  d.rank_groups())):
                 msg += "\t%s-%s:%f" % (name, m, v)
@@ -478,7 +505,10 @@ def _booster_state(b):
     for t in b.trees:
         trees.append({k: torch.tensor(getattr(t, k), dtype=torch.float64)
                       for k in ("feat", "cond", "left", "right", "defl", "leaf", "gain", "cover")})
-    return {"num_feature": b.num_feature, "num_class": b.param.num_class, "trees": trees}
+    state = {"num_feature": b.num_feature, "num_class": b.param.num_class, "trees": trees}
+    if b.weighted():  # (booster=dart: the trees' weights; none: all 1)
+        state["tree_w"] = torch.tensor(b.weights(), dtype=torch.float64)
+    return state
 
 
 def _booster_from_state(G, s, param):
@@ -495,6 +525,8 @@ def _booster_from_state(G, s, param):
         t.bin = [0] * n
         t.base_weight = [0.0] * n
         b.trees.append(t)
+    if "tree_w" in s:
+        b.tree_w = [float(x) for x in s["tree_w"].tolist()]
     return b
 
 

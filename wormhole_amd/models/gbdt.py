@@ -46,6 +46,7 @@ HIST32 = True  # int32 LDS histogram passes (False: int64 sums throughout)
 LEAF_WALK_LDS = True  # the LDS-resident tree walk when it fits (False: global walk)
 DEFER_TREES = True  # device trees: host lists one tree later (False: read every tree at once)
 HOST_GROWER = False  # the per-level host grower instead of the device level loop
+DART_BIN_WALK = True  # booster=dart: dropped trees walked on the bins from LDS (False: forest kernels)
 
 
 def _h2d(t, dev):
@@ -920,13 +921,21 @@ def boost_round(obj, builder, dm, margin, gen=None, fgen=None):
     (rows, from ``gen``) and ``colsample_bytree`` (features, from ``fgen``)
     are drawn per tree. A rank objective takes the rows' query groups from
     ``dm.group``. Returns the new trees in class order."""
+    return grow_round(obj, builder, dm, margin, margin, gen, fgen)
+
+
+def grow_round(obj, builder, dm, at, into, gen=None, fgen=None):
+    """:func:`boost_round` with the gradients taken at the margins ``at`` and
+    the new trees' outputs added to ``into`` (the same tensor for gbtree; the
+    dart round takes them at the margins without the dropped trees and has
+    the outputs added to a scratch)."""
     p = builder.p
     K = obj.n_group
     # (a rank objective's query groups: the matrix's, with their cached task plan)
-    gp = obj.gpair(margin, dm.label, dm.weight, dm.rank_groups())
+    gp = obj.gpair(at, dm.label, dm.weight, dm.rank_groups())
     new = []
     for k in range(K):
-        gk, mk = (class_gpair(gp, k), margin[k]) if K > 1 else (gp, margin)
+        gk, mk = (class_gpair(gp, k), into[k]) if K > 1 else (gp, into)
         if p.subsample < 1.0:
             keep = (torch.rand(dm.n, generator=gen) < p.subsample).to(dm.device)
             gk = gk * keep[:, None].float()
@@ -934,4 +943,10 @@ def boost_round(obj, builder, dm, margin, gen=None, fgen=None):
             builder.sample_features(fgen)
         new.append(builder.build(gk, mk))
     return new
+
+
+# booster=dart: the draw, the weight update, the tree table and the round
+# (imported last: the module reads this one's switches and growers when called)
+from .gbdt_dart import (DartForest, DartTrainer, dart_add, dart_draw, dart_scales,  # noqa: E402,F401
+                        dart_seed, dart_update, forest_add)
 

@@ -39,6 +39,12 @@ class GBDTParam:
         self.scale_pos_weight = 1.0  # the logistic family: the weight of rows with y == 1
         self.tweedie_variance_power = 1.5  # reg:tweedie (and its default metric): in (1, 2)
         self.huber_slope = 1.0  # reg:pseudohubererror and mphe: > 0
+        # booster=dart (models/gbdt_dart.py); read by no one under gbtree
+        self.rate_drop = 0.0  # a round's chance of being dropped, in [0, 1]
+        self.skip_drop = 0.0  # a round's chance of dropping nothing, in [0, 1]
+        self.one_drop = 0  # 1: a round that chose nothing drops one round
+        self.sample_type = "uniform"  # | weighted: chances in proportion to the weights
+        self.normalize_type = "tree"  # | forest
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -57,7 +63,28 @@ class GBDTParam:
             setattr(self, name, float(val))
         elif name in ("max_depth", "max_bin", "seed", "silent", "num_class"):
             setattr(self, name, int(val))
-        elif name in ("objective", "booster"):
+        elif name == "booster":
+            if val not in ("gbtree", "dart"):
+                raise SystemExit("booster=%s is not supported: booster is gbtree or dart" % val)
+            self.booster = val
+        elif name in ("rate_drop", "skip_drop"):
+            try:
+                x = float(val)
+            except ValueError:
+                x = float("nan")
+            if not 0.0 <= x <= 1.0:
+                raise SystemExit("%s must be in [0, 1], got %s" % (name, val))
+            setattr(self, name, x)
+        elif name == "one_drop":
+            if str(val).strip() not in ("0", "1"):
+                raise SystemExit("one_drop must be 0 or 1, got %s" % val)
+            self.one_drop = int(val)
+        elif name in ("sample_type", "normalize_type"):
+            allowed = {"sample_type": ("uniform", "weighted"), "normalize_type": ("tree", "forest")}
+            if val not in allowed[name]:
+                raise SystemExit("%s must be %s or %s, got %s" % ((name,) + allowed[name] + (val,)))
+            setattr(self, name, val)
+        elif name == "objective":
             setattr(self, name, val)
         elif name == "eval_metric":
             self.eval_metric.append(val)

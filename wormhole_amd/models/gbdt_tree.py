@@ -198,13 +198,16 @@ class Forest:
     gbdt_forest_plan.h): one node table and the trees' offsets on the device,
     and the chunks of whole trees, each walked by every row in one launch."""
 
-    def __init__(self, trees, device):
+    def __init__(self, trees, device, leaves=None):
         hip = _native.hip()
+        # leaves: the trees' leaf lists where they are not the stored ones
+        # (a weighted tree's effective leaves, Booster.eff_leaf)
+        leaves = [t.leaf for t in trees] if leaves is None else leaves
         # (a tree a walk could leave or spin in: ValueError "malformed tree t")
         nodes, tree_off, self.max_feat = hip.gbdt_forest_pack(
             feat=[t.feat for t in trees], cond=[t.cond for t in trees],
             left=[t.left for t in trees], right=[t.right for t in trees],
-            defl=[t.defl for t in trees], leaf=[t.leaf for t in trees])
+            defl=[t.defl for t in trees], leaf=leaves)
         self.ntree = len(trees)
         self.chunks = hip.gbdt_forest_plan(tree_sizes=[len(t.feat) for t in trees],
                                            lds_nodes=hip.gbdt_forest_lds_nodes())
@@ -221,11 +224,12 @@ class ShapForest:
     raises ValueError for a tree without usable cover statistics and for a
     path of more than 63 distinct features."""
 
-    def __init__(self, trees, K, base_margin, device):
+    def __init__(self, trees, K, base_margin, device, leaves=None):
         hip = _native.hip()
+        leaves = [t.leaf for t in trees] if leaves is None else leaves  # (as Forest)
         kw = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
                   left=[t.left for t in trees], right=[t.right for t in trees],
-                  defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                  defl=[t.defl for t in trees], leaf=leaves,
                   cover=[t.cover for t in trees])
         (used, tree_E, paths, elems, ecol, self.chunks, nodes, tree_off, node_m,
          node_col) = hip.gbdt_shap_pack(num_class=K, **kw)
@@ -260,6 +264,9 @@ class Booster:
         self.param = param
         self.num_feature = int(num_feature)
         self.trees = []
+        # booster=dart: one fp32 weight per tree (the K trees of a round share
+        # theirs); trees beyond the list weigh 1, as every gbtree tree does
+        self.tree_w = []
         self.obj = Objective(param.objective, param.num_class, param)
         self.base_margin = self.obj.prob_to_margin(param.base_score)
 
@@ -275,15 +282,55 @@ class Booster:
             raise ValueError("ntree_limit must not be negative")
         return min(ntree_limit, len(self.trees)) if ntree_limit else len(self.trees)
 
+    # ------------------------------------------------------ tree weights
+    def weights(self, ntree=None):
+        """The first ``ntree`` trees' weights (default: all), as floats that
+        are fp32 values; 1.0 where none was set."""
+        ntree = len(self.trees) if ntree is None else ntree
+        w = [float(np.float32(x)) for x in self.tree_w[:ntree]]
+        return w + [1.0] * (ntree - len(w))
+
+    def weighted(self):
+        """True when some tree's weight is not 1 (a dart-trained model)."""
+        return any(w != 1.0 for w in self.weights())
+
+    def eff_leaf(self, i, coef=None):
+        """Tree i's effective leaf values, what every consumer of the model's
+        trees adds: float32(w_i) * float32(leaf), one fp32 multiply per leaf
+        (as Python floats). A weight of 1 returns the stored list itself.
+        coef: another fp32 factor in place of the tree's weight."""
+        t = self.trees[i]
+        if coef is None:
+            coef = self.tree_w[i] if i < len(self.tree_w) else 1.0
+        w = float(np.float32(coef))
+        if w == 1.0:
+            return t.leaf
+        return (np.float32(w) * np.asarray(t.leaf, dtype=np.float32)).astype(np.float64).tolist()
+
+    def eff_leaves(self, ntree):
+        return [self.eff_leaf(i) for i in range(ntree)]
+
+    def eff_tree(self, i, coef=None):
+        """Tree i with its effective leaves in place of the stored ones (the
+        tree itself at weight 1)."""
+        t = self.trees[i]
+        leaf = self.eff_leaf(i, coef)
+        if leaf is t.leaf:
+            return t
+        v = RegTree()
+        v.__dict__.update(t.__dict__)  # (eff_leaf has built a pending device tree)
+        v.leaf = leaf
+        return v
+
     def forest(self, device, ntree=0):
         """The first ``ntree`` trees (0: all) packed for the forest kernels on
         ``device``; kept until the model's tree count or the limit changes.
         Packing reads the trees' lists (a pending device tree is built here);
         a tree that a walk could leave raises ValueError."""
         ntree = self._ntree(ntree)
-        key = (torch.device(device), len(self.trees), ntree)
+        key = (torch.device(device), len(self.trees), ntree, tuple(self.weights(ntree)))
         if self.__dict__.get("_forest_key") != key:
-            self._forest = Forest(self.trees[:ntree], device)
+            self._forest = Forest(self.trees[:ntree], device, self.eff_leaves(ntree))
             self._forest_key = key
         return self._forest
 
@@ -296,8 +343,8 @@ class Booster:
         if torch.device(dm.device).type == "cuda" and ntree >= self.FOREST_MIN_TREES:
             dm.predict_forest(self.forest(dm.device, ntree), margin)
             return margin
-        for i, t in enumerate(self.trees[:ntree]):
-            dm.predict_tree(t, margin if K == 1 else margin[i % K])
+        for i in range(ntree):
+            dm.predict_tree(self.eff_tree(i), margin if K == 1 else margin[i % K])
         return margin
 
     def predict_leaf(self, dm, ntree_limit=0):
@@ -317,9 +364,10 @@ class Booster:
         """The first ``ntree`` trees (0: all) packed for the contribution
         kernels on ``device``; kept as ``forest`` keeps its table."""
         ntree = self._ntree(ntree)
-        key = (torch.device(device), len(self.trees), ntree)
+        key = (torch.device(device), len(self.trees), ntree, tuple(self.weights(ntree)))
         if self.__dict__.get("_shap_key") != key:
-            self._shap = ShapForest(self.trees[:ntree], self.obj.n_group, self.base_margin, device)
+            self._shap = ShapForest(self.trees[:ntree], self.obj.n_group, self.base_margin, device,
+                                    self.eff_leaves(ntree))
             self._shap_key = key
         return self._shap
 
@@ -348,7 +396,7 @@ class Booster:
             trees = self.trees[:ntree]
             model = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
                          left=[t.left for t in trees], right=[t.right for t in trees],
-                         defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                         defl=[t.defl for t in trees], leaf=self.eff_leaves(ntree),
                          cover=[t.cover for t in trees], num_class=K, base=self.base_margin)
             phi, used = dm.predict_contribs_host(model, approx=approx, rows=(a, b))
         used = used.long()
@@ -383,7 +431,7 @@ class Booster:
             trees = self.trees[:ntree]
             model = dict(feat=[t.feat for t in trees], cond=[t.cond for t in trees],
                          left=[t.left for t in trees], right=[t.right for t in trees],
-                         defl=[t.defl for t in trees], leaf=[t.leaf for t in trees],
+                         defl=[t.defl for t in trees], leaf=self.eff_leaves(ntree),
                          cover=[t.cover for t in trees], num_class=K, base=self.base_margin)
             phi, used = dm.predict_interactions_host(model, rows=(a, b))
         used = used.long()
@@ -415,6 +463,9 @@ class Booster:
                 for k in ("feat", "cond", "left", "right", "defl", "leaf", "gain", "cover"):
                     arr[k] = getattr(t, k)
                 f.write(arr.tobytes())
+            if self.weighted():  # (a model of unit weights keeps the gbtree bytes)
+                w = np.asarray(self.weights(), dtype="<f4")
+                f.write(b"DART" + struct.pack("<I", w.size) + w.tobytes())
 
     @staticmethod
     def load(path, param):
@@ -446,8 +497,16 @@ class Booster:
                 t.bin = [0] * n
                 t.base_weight = [0.0] * n
                 b.trees.append(t)
+            tag = f.read(4)
+            if tag == b"DART":  # the trees' weights (no trailer: all 1)
+                (cnt,) = struct.unpack("<I", f.read(4))
+                w = np.frombuffer(f.read(4 * cnt), dtype="<f4")
+                if w.size != cnt or cnt != len(b.trees):
+                    raise ValueError("invalid weight trailer in " + path)
+                b.tree_w = [float(x) for x in w]
         return b
 
     def dump(self, fmap=None, with_stats=False):
-        return "".join("booster[%d]:\n%s" % (i, t.dump(fmap, with_stats))
-                       for i, t in enumerate(self.trees))
+        """(leaf values: the effective ones, :meth:`eff_leaf`)"""
+        return "".join("booster[%d]:\n%s" % (i, self.eff_tree(i).dump(fmap, with_stats))
+                       for i in range(len(self.trees)))
