@@ -24,6 +24,12 @@ reg:squaredlogerror), on labels of the same synthetic score that fit it
 (counts for count:poisson and reg:tweedie, positive reals for reg:gamma and
 reg:squaredlogerror). count:poisson brings max_delta_step = 0.7, so it takes
 the bounded split kernels. train_error is the objective's default metric.
+reg:squarederror, reg:absoluteerror and reg:quantileerror (--quantile-alpha, a
+number or a list as the app takes it; default 0.5) train on the score plus
+unit noise. The last two refresh every tree's leaves with residual quantiles
+(the radix select) and give up the deferred-tree path; --gamma G > 0 takes it
+from any objective too, which makes reg:squarederror --gamma 1e-9 their fair
+comparison.
 """
 import argparse
 import json
@@ -41,7 +47,7 @@ from wormhole_amd.parallel.comm import env_local_rank  # noqa: E402
 from wormhole_amd.parallel import launch  # noqa: E402
 
 
-OBJECTIVES = ("binary:logistic",) + tuple(G.OBJ_IDS)
+OBJECTIVES = ("binary:logistic",) + tuple(G.OBJ_IDS) + ("reg:squarederror",) + G.ADAPTIVE_OBJECTIVES
 
 
 def higgs_like(n, f, seed, dev, num_class=0, objective="binary:logistic"):
@@ -59,7 +65,7 @@ def higgs_like(n, f, seed, dev, num_class=0, objective="binary:logistic"):
         y = torch.poisson(torch.exp(0.5 * logit.clamp(-3, 3)), generator=g)
     elif objective in ("reg:gamma", "reg:squaredlogerror"):  # positive reals around it
         y = torch.exp(0.5 * logit.clamp(-3, 3)) * (0.5 + torch.rand(n, device=dev, generator=g))
-    elif objective == "reg:pseudohubererror":
+    elif objective in ("reg:pseudohubererror", "reg:squarederror") + G.ADAPTIVE_OBJECTIVES:
         y = logit + torch.randn(n, device=dev, generator=g)
     return X, y
 
@@ -95,6 +101,10 @@ def main():
                     help="K > 1: multi:softprob, K trees per round (--trees counts trees)")
     ap.add_argument("--objective", default="binary:logistic", choices=OBJECTIVES,
                     help="a single-output objective (not with --num-class); labels are drawn to fit")
+    ap.add_argument("--quantile-alpha", default="0.5",
+                    help="reg:quantileerror: one alpha or a list, K trees per round")
+    ap.add_argument("--gamma", type=float, default=0.0,
+                    help="min_split_loss; > 0 prunes and turns the deferred-tree path off")
     ap.add_argument("--monotone", default="",
                     help='monotone_constraints as a pattern of + - 0 cycled over the features')
     ap.add_argument("--interaction", default="",
@@ -121,13 +131,17 @@ def main():
     K = a.num_class if a.num_class > 1 else 1
     if K > 1 and a.objective != "binary:logistic":
         ap.error("--objective and --num-class exclude each other")
+    p = G.GBDTParam()
+    if a.objective == "reg:quantileerror":
+        p.set("quantile_alpha", a.quantile_alpha)
+        K = len(p.quantile_alpha)
     X, y = higgs_like(n, a.features, 7 + bsp.rank, dev, a.num_class, a.objective)
     dm = G.DMatrix.from_dense(X, y, dev)
-    p = G.GBDTParam()
-    p.objective = a.objective if K == 1 else "multi:softprob"
+    p.objective = "multi:softprob" if a.num_class > 1 else a.objective
     p.num_class = a.num_class if K > 1 else 0
     p.max_depth = a.depth
     p.eta = 0.1
+    p.gamma = a.gamma
     p.max_bin = a.max_bin
     if a.monotone:
         if set(a.monotone) - set("+-0"):
@@ -147,7 +161,7 @@ def main():
     B = cuts.bin(dm)
     sync()
     t_prep = time.perf_counter() - t_prep
-    obj = G.Objective(p.objective, p.num_class, p)
+    obj = G.make_objective(p.objective, p.num_class, p)
     tb = G.TreeBuilder(p, bsp, dm, cuts, B)
     margin = torch.zeros(n, device=dev) if K == 1 else torch.zeros(K, n, device=dev)
     rounds = max(1, a.trees // K)
@@ -176,7 +190,9 @@ def main():
     hb = bsp.allreduce_scalar((tb.hist_bytes() - b0) / max(ntree, 1), "max")
     err = obj.metrics([obj.default_metric()], margin, dm.label, None, bsp)[0]
     extra = {}
-    if K > 1:
+    if a.objective == "reg:quantileerror":
+        extra = {"quantile_alpha": p.quantile_alpha, "rounds": rounds}
+    elif K > 1:
         extra = {"num_class": K, "rounds": rounds, "rounds_per_s": rounds / dt}
         if dev.type == "cuda":
             ms_k, ms_t = time_gpair(obj, margin, dm.label, dev)
@@ -188,7 +204,7 @@ def main():
                           "value": ntree / dt, "unit": "trees/s", "n_gpus": bsp.world if dev.type == "cuda" else 0, "ranks": bsp.world, "device": dev.type,
                           "ms_per_tree": 1000 * dt / ntree,
                           "trees": ntree, **extra, "objective": p.objective,
-                          "monotone": a.monotone or None,
+                          "gamma": a.gamma, "monotone": a.monotone or None,
                           "interaction": p.interaction or None,
                           "sketch_bin_s": t_prep,
                           "hist_exchange": ("feature-reduce-scatter" if tb.xchg is not None

@@ -11,10 +11,10 @@ Two shared objects are produced next to the Python sources:
 * ``bin/native/{convert,text2crb}`` -- standalone C++ data conversion tools
   (reference learn/tool/), wrapped by ``bin/convert.dmlc`` / ``bin/text2crb.dmlc``.
 * ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test,
-  gbdt_shap_inter_test,gbdt_dart_plan_test}`` -- stand-alone tests of host code
-  (``--sanitize`` / ``--sanitize-rank-plan`` / ``--sanitize-shap-plan`` /
-  ``--sanitize-shap-inter`` / ``--sanitize-dart-plan`` build them under
-  sanitizers).
+  gbdt_shap_inter_test,gbdt_dart_plan_test,gbdt_quantile_plan_test}`` --
+  stand-alone tests of host code (``--sanitize`` / ``--sanitize-rank-plan`` /
+  ``--sanitize-shap-plan`` / ``--sanitize-shap-inter`` / ``--sanitize-dart-plan``
+  / ``--sanitize-quantile-plan`` build them under sanitizers).
 * ``wormhole_amd/_host.so`` -- the native C++ runtime (``csrc/host/*.cc``):
   proto-text config parser, data parsers (libsvm / criteo / adfea / crb),
   CityHash64, LZ4 block codec, RecordIO, workload pool, control-plane
@@ -156,6 +156,11 @@ def gen_ninja():
     lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, DART_PLAN_TEST_SRC)))
     lines.append("build %s: link_tool %s" % (
         os.path.join(ROOT, "bin", "native", "gbdt_dart_plan_test"), obj))
+    # quantile select plan test (header only): bin/native/gbdt_quantile_plan_test
+    obj = os.path.join(BUILD, "tool", "gbdt_quantile_plan_test.o")
+    lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, QUANTILE_PLAN_TEST_SRC)))
+    lines.append("build %s: link_tool %s" % (
+        os.path.join(ROOT, "bin", "native", "gbdt_quantile_plan_test"), obj))
     lines.append("build %s: link_hip %s" % (os.path.join(PKG, "_hip.so"), " ".join(hip_objs)))
     lines.append("build %s: link_host %s" % (os.path.join(PKG, "_host.so"), " ".join(host_objs)))
     os.makedirs(BUILD, exist_ok=True)
@@ -167,6 +172,7 @@ RANK_PLAN_TEST_SRC = "csrc/tests/gbdt_rank_plan_test.cc"
 SHAP_PLAN_TEST_SRC = "csrc/tests/gbdt_shap_plan_test.cc"
 SHAP_INTER_TEST_SRC = "csrc/tests/gbdt_shap_inter_test.cc"
 DART_PLAN_TEST_SRC = "csrc/tests/gbdt_dart_plan_test.cc"
+QUANTILE_PLAN_TEST_SRC = "csrc/tests/gbdt_quantile_plan_test.cc"
 SELFTEST_SRCS = ("csrc/tests/host_selftest.cc", "csrc/host/parsers.cc", "csrc/host/io.cc",
                  "csrc/host/remote_fs.cc", "csrc/host/lz4.cc", "csrc/host/cityhash.cc", "csrc/host/workload_pool.cc",
                  "csrc/host/conf_parser.cc", "csrc/host/van.cc", "csrc/host/json.cc")
@@ -233,6 +239,14 @@ def build_dart_plan_sanitized():
     return _build_plan_test_sanitized("dart-plan", DART_PLAN_TEST_SRC)
 
 
+def build_quantile_plan_sanitized():
+    """The quantile select plan test (csrc/host/gbdt_quantile_plan.h, its own
+    main) under -fsanitize=address,undefined:
+    build/san-quantile-plan/gbdt_quantile_plan_test. The plain build is
+    bin/native/gbdt_quantile_plan_test."""
+    return _build_plan_test_sanitized("quantile-plan", QUANTILE_PLAN_TEST_SRC)
+
+
 def build(jobs=None, clean=False, verbose=False):
     if clean and os.path.isdir(BUILD):
         shutil.rmtree(BUILD)
@@ -261,7 +275,12 @@ if __name__ == "__main__":
                     help="build the interaction references test under address,undefined instead")
     ap.add_argument("--sanitize-dart-plan", action="store_true",
                     help="build the DART plan test under address,undefined instead")
+    ap.add_argument("--sanitize-quantile-plan", action="store_true",
+                    help="build the quantile select plan test under address,undefined instead")
     a = ap.parse_args()
+    if a.sanitize_quantile_plan:
+        print(build_quantile_plan_sanitized())
+        sys.exit(0)
     if a.sanitize_dart_plan:
         print(build_dart_plan_sanitized())
         sys.exit(0)

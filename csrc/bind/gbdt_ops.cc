@@ -17,6 +17,7 @@
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
 #include "host/gbdt_objective.h"
+#include "host/gbdt_quantile_plan.h"
 #include "host/gbdt_rank_plan.h"
 #include "host/gbdt_shap_plan.h"
 
@@ -305,10 +306,13 @@ double* obj_scratch(const Tensor& like, int slot, int64_t need) {
 std::vector<Tensor> gbdt_gpair_obj(const Tensor& margin, const Tensor& label,
                                    const c10::optional<Tensor>& weight, int64_t objective,
                                    double max_delta_step, double tweedie_variance_power,
-                                   double huber_slope, double scale_pos_weight) {
+                                   double huber_slope, double scale_pos_weight,
+                                   double quantile_alpha) {
   const float* wp = obj_args("gbdt_gpair_obj", margin, label, weight);
-  TORCH_CHECK(objective >= 0 && objective < wh::kObjCount, "gbdt_gpair_obj: unknown objective id ",
-              objective);
+  TORCH_CHECK(objective >= 0 && objective < wh::kObjCount && objective != 7,
+              "gbdt_gpair_obj: unknown objective id ", objective);
+  TORCH_CHECK(quantile_alpha > 0 && quantile_alpha < 1,
+              "gbdt_gpair_obj: quantile_alpha in (0, 1)");
   TORCH_CHECK(max_delta_step >= 0 && huber_slope > 0 && scale_pos_weight > 0 &&
                   tweedie_variance_power > 1 && tweedie_variance_power < 2,
               "gbdt_gpair_obj: max_delta_step >= 0, tweedie_variance_power in (1, 2), "
@@ -320,7 +324,7 @@ std::vector<Tensor> gbdt_gpair_obj(const Tensor& margin, const Tensor& label,
                   : torch::zeros({4}, margin.options().dtype(torch::kFloat64));
   if (n > 0) {
     const auto a = wh::gbdt_obj_scalars(max_delta_step, tweedie_variance_power, huber_slope,
-                                        scale_pos_weight);
+                                        scale_pos_weight, quantile_alpha);
     const bool ok = wh::gbdt_gpair_obj(
         (int)objective, n, ptr<float>(margin), ptr<float>(label), wp, a, ptr<float>(gp),
         obj_scratch(margin, 0, wh::gbdt_gpair_scratch()), ptr<double>(st), cur_stream(margin));
@@ -344,6 +348,133 @@ Tensor gbdt_obj_eval(const Tensor& margin, const Tensor& label,
                       tweedie_variance_power, huber_slope,
                       obj_scratch(margin, 1, wh::gbdt_obj_eval_scratch()), ptr<double>(out),
                       cur_stream(margin));
+  return out;
+}
+
+// ---- the `quantile` metric: margin f32 [K, n] (or [n]: K = 1), alphas f64 [K]
+// on the margins' device -> f64 [2] = {sum w sum_k pinball_k, sum w}
+Tensor gbdt_quantile_eval(const Tensor& margin, const Tensor& label,
+                          const c10::optional<Tensor>& weight, const Tensor& alphas) {
+  CHECK_IN(margin, torch::kFloat32);
+  CHECK_IN(label, torch::kFloat32);
+  CHECK_IN(alphas, torch::kFloat64);
+  const int64_t n = label.numel(), K = alphas.numel();
+  TORCH_CHECK(K >= 1 && K <= 64 && margin.numel() == K * n,
+              "gbdt_quantile_eval: margin must be [K, n] for 1 <= K <= 64 alphas");
+  const float* wp = nullptr;
+  if (weight.has_value() && weight->defined()) {
+    CHECK_IN((*weight), torch::kFloat32);
+    TORCH_CHECK(weight->numel() == n, "gbdt_quantile_eval: weight size mismatch");
+    wp = ptr<float>(*weight);
+  }
+  c10::DeviceGuard g(margin.device());
+  auto out = torch::zeros({2}, margin.options().dtype(torch::kFloat64));
+  if (n > 0) {
+    auto scratch = torch::empty({wh::gbdt_quantile_eval_scratch()}, out.options());
+    wh::gbdt_quantile_eval(n, (int)K, ptr<float>(margin), ptr<float>(label), wp,
+                           ptr<double>(alphas), ptr<double>(scratch), ptr<double>(out),
+                           cur_stream(margin));
+  }
+  return out;
+}
+
+// ---- the adaptive objectives' leaf refresh: the radix select of
+// host/gbdt_quantile_plan.h, pass by pass (models/gbdt_quantile.py drives it
+// and adds the ranks' histograms between hist and pick)
+// (key i32 [npos] holding the uint32 keys, u i64 [npos]) of the ridx positions
+std::vector<Tensor> gbdt_qsel_key(const Tensor& ridx, const Tensor& label, const Tensor& at,
+                                  const c10::optional<Tensor>& weight,
+                                  const c10::optional<Tensor>& keep,
+                                  const c10::optional<Tensor>& scale) {
+  CHECK_IN(ridx, torch::kInt32);
+  CHECK_IN(label, torch::kFloat32);
+  CHECK_IN(at, torch::kFloat32);
+  const int64_t npos = ridx.numel(), nrow = label.numel();
+  TORCH_CHECK(at.numel() == nrow, "gbdt_qsel_key: label and margin sizes differ");
+  const float* wp = nullptr;
+  const uint8_t* kp = nullptr;
+  const double* sp = nullptr;
+  if (weight.has_value() && weight->defined()) {
+    CHECK_IN((*weight), torch::kFloat32);
+    TORCH_CHECK(weight->numel() == nrow, "gbdt_qsel_key: weight size mismatch");
+    wp = ptr<float>(*weight);
+  }
+  if (keep.has_value() && keep->defined()) {
+    TORCH_CHECK(keep->is_cuda() && keep->is_contiguous() && keep->numel() == nrow &&
+                    (keep->scalar_type() == torch::kUInt8 || keep->scalar_type() == torch::kBool),
+                "gbdt_qsel_key: keep must be a contiguous bool / uint8 [n] on the device");
+    kp = ptr<uint8_t>(*keep);
+  }
+  if (scale.has_value() && scale->defined()) {
+    CHECK_IN((*scale), torch::kFloat64);
+    TORCH_CHECK(scale->numel() == 1, "gbdt_qsel_key: scale is one double");
+    sp = ptr<double>(*scale);
+  }
+  c10::DeviceGuard g(ridx.device());
+  auto key = torch::empty({npos}, ridx.options());
+  auto u = torch::empty({npos}, ridx.options().dtype(torch::kInt64));
+  wh::gbdt_qsel_key(ptr<int32_t>(ridx), npos, nrow, ptr<float>(label), ptr<float>(at), wp, kp, sp,
+                    ptr<uint32_t>(key), ptr<int64_t>(u), cur_stream(ridx));
+  return {key, u};
+}
+
+// hist i64 [L, 256]: this rank's bins of pass `radix_pass` for the L segments
+// [seg_beg[l], seg_end[l]) of the key positions, each cut into tasks of
+// `chunk` positions (qsel_plan; the task lists go down in one pinned copy);
+// zero for an empty segment
+Tensor gbdt_qsel_hist(const Tensor& key, const Tensor& u, const std::vector<int64_t>& seg_beg,
+                      const std::vector<int64_t>& seg_end, int64_t chunk, const Tensor& state,
+                      int64_t radix_pass) {
+  CHECK_IN(key, torch::kInt32);
+  CHECK_IN(u, torch::kInt64);
+  CHECK_IN(state, torch::kInt64);
+  TORCH_CHECK(u.numel() == key.numel(), "gbdt_qsel_hist: key and u sizes differ");
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == wh::kQselState && state.size(0) <= INT32_MAX &&
+                  state.size(0) == (int64_t)seg_beg.size(),
+              "gbdt_qsel_hist: state must be [L, 2] for L segments");
+  TORCH_CHECK(radix_pass >= 0 && radix_pass < wh::kQselPasses, "gbdt_qsel_hist: pass in [0, 4)");
+  std::vector<int32_t> plan, red;
+  TORCH_CHECK(wh::qsel_plan(seg_beg, seg_end, key.numel(), chunk, &plan, &red),
+              "gbdt_qsel_hist: segments must lie within the keys with begin <= end, chunk >= 1");
+  c10::DeviceGuard g(key.device());
+  const int64_t L = state.size(0), T = (int64_t)plan.size() / 3, R = (int64_t)red.size() / 3;
+  auto hist = torch::zeros({L, wh::kQselBins}, u.options());
+  if (T > 0 && L > 0) {
+    plan.insert(plan.end(), red.begin(), red.end());
+    auto host = torch::empty({(int64_t)plan.size()},
+                             torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
+    std::memcpy(host.data_ptr(), plan.data(), plan.size() * 4);
+    auto dev = host.to(key.device(), /*non_blocking=*/true);
+    auto part = torch::empty({T, wh::kQselBins}, u.options());
+    wh::gbdt_qsel_hist(ptr<uint32_t>(key), ptr<int64_t>(u), key.numel(), ptr<int32_t>(dev), T,
+                       ptr<int32_t>(dev) + 3 * T, R, (int)L, ptr<int64_t>(state), (int)radix_pass,
+                       ptr<int64_t>(part), ptr<int64_t>(hist), cur_stream(key));
+  }
+  return hist;
+}
+
+void gbdt_qsel_pick(const Tensor& hist, const Tensor& state, int64_t pass, double alpha) {
+  CHECK_IN(hist, torch::kInt64);
+  CHECK_IN(state, torch::kInt64);
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == wh::kQselState && state.size(0) <= INT32_MAX &&
+                  hist.dim() == 2 && hist.size(0) == state.size(0) &&
+                  hist.size(1) == wh::kQselBins,
+              "gbdt_qsel_pick: hist [L, 256] and state [L, 2]");
+  TORCH_CHECK(pass >= 0 && pass < wh::kQselPasses, "gbdt_qsel_pick: pass in [0, 4)");
+  TORCH_CHECK(alpha > 0 && alpha < 1, "gbdt_qsel_pick: alpha in (0, 1)");
+  c10::DeviceGuard g(hist.device());
+  wh::gbdt_qsel_pick(ptr<int64_t>(hist), (int)state.size(0), (int)pass, alpha,
+                     ptr<int64_t>(state), cur_stream(hist));
+}
+
+// f32 [2, L]: the selected residuals, then 1 where the leaf has no weight
+Tensor gbdt_qsel_value(const Tensor& state) {
+  CHECK_IN(state, torch::kInt64);
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == wh::kQselState && state.size(0) <= INT32_MAX,
+              "gbdt_qsel_value: state must be [L, 2]");
+  c10::DeviceGuard g(state.device());
+  auto out = torch::zeros({2, state.size(0)}, state.options().dtype(torch::kFloat32));
+  wh::gbdt_qsel_value(ptr<int64_t>(state), (int)state.size(0), ptr<float>(out), cur_stream(state));
   return out;
 }
 
@@ -1853,7 +1984,18 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_gpair_obj", &gbdt_gpair_obj, py::arg("margin"), py::arg("label"), py::arg("weight"),
         py::arg("objective"), py::arg("max_delta_step") = 0.0,
         py::arg("tweedie_variance_power") = 1.5, py::arg("huber_slope") = 1.0,
-        py::arg("scale_pos_weight") = 1.0);
+        py::arg("scale_pos_weight") = 1.0, py::arg("quantile_alpha") = 0.5);
+  m.def("gbdt_quantile_eval", &gbdt_quantile_eval, py::arg("margin"), py::arg("label"),
+        py::arg("weight"), py::arg("alphas"));
+  // the adaptive objectives' leaf refresh, pass by pass
+  m.def("gbdt_qsel_key", &gbdt_qsel_key, py::arg("ridx"), py::arg("label"), py::arg("at"),
+        py::arg("weight") = py::none(), py::arg("keep") = py::none(),
+        py::arg("scale") = py::none());
+  m.def("gbdt_qsel_hist", &gbdt_qsel_hist, py::arg("key"), py::arg("u"), py::arg("seg_beg"),
+        py::arg("seg_end"), py::arg("chunk"), py::arg("state"), py::arg("radix_pass"));
+  m.def("gbdt_qsel_pick", &gbdt_qsel_pick, py::arg("hist"), py::arg("state"), py::arg("radix_pass"),
+        py::arg("alpha"));
+  m.def("gbdt_qsel_value", &gbdt_qsel_value, py::arg("state"));
   m.def("gbdt_obj_eval", &gbdt_obj_eval, py::arg("margin"), py::arg("label"), py::arg("weight"),
         py::arg("link"), py::arg("mask"), py::arg("tweedie_variance_power") = 1.5,
         py::arg("huber_slope") = 1.0);

@@ -1057,7 +1057,7 @@ static void launch_gpair_obj(int nb, hipStream_t s, int64_t n, const float* marg
 bool gbdt_gpair_obj(int obj, int64_t n, const float* margin, const float* label,
                     const float* weight, const GbdtObjScalars& a, float* gpair, double* scratch,
                     double* stats, hipStream_t s) {
-  if (obj < 0 || obj >= kObjCount) return false;
+  if (obj < 0 || obj >= kObjCount || obj == 7) return false;
   if (n <= 0) return true;
   // scratch as gbdt_gpair's: per-block partials, then the (zeroed) ticket words
   unsigned int* ticket = reinterpret_cast<unsigned int*>(scratch + 4 * kGpBlocks);
@@ -1070,6 +1070,8 @@ bool gbdt_gpair_obj(int obj, int64_t n, const float* margin, const float* label,
     case kObjTweedie: launch_gpair_obj<kObjTweedie>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
     case kObjHinge: launch_gpair_obj<kObjHinge>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
     case kObjPseudoHuber: launch_gpair_obj<kObjPseudoHuber>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjAbsolute: launch_gpair_obj<kObjAbsolute>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
+    case kObjQuantile: launch_gpair_obj<kObjQuantile>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
     default: launch_gpair_obj<kObjSquaredLog>(nb, s, n, margin, label, weight, a, out, scratch, ticket, stats); break;
   }
   return true;

@@ -719,6 +719,36 @@ void gbdt_predict_forest(const float* X, int64_t n, int f, const ForestChunk& c,
 void gbdt_predict_forest_csr(const int64_t* row_off, const int32_t* fid, const float* val,
                              int64_t n, const ForestChunk& c, const ForestOut& o, hipStream_t s);
 
+// ------------------------------------------------------ gbdt_quantile.hip
+// The adaptive objectives' leaf refresh: an MSD radix select (8-bit digits,
+// four passes; host/gbdt_quantile_plan.h) of every leaf's weighted quantile.
+// key: per ridx position p < npos the key of label[row] - at[row] and the
+// fixed-point weight u = round(weight[row] * keep[row] * scale[0]) (weight,
+// keep, scale: nullptr = 1; a row outside [0, nrow) weighs 0). hist: tasks
+// int32 [ntask, 3] {leaf, begin, end} and red int32 [nred, 3] {leaf, first
+// task, chunks} (qsel_plan); state int64 [L, 2] {prefix, rem}; part int64
+// [ntask, 256] scratch; hist int64 [L, 256], written for the leaves of red
+// only. pick: one pass's digit per leaf from the (global) hist; pass 0 sets
+// rem from alpha and the bins' total. value: out fp32 [2, L] = the selected
+// residuals, then 1 for a leaf without weight. Positions, leaves and task
+// ranges outside their arrays are skipped. Nothing runs for empty inputs.
+void gbdt_qsel_key(const int32_t* ridx, int64_t npos, int64_t nrow, const float* label,
+                   const float* at, const float* weight, const uint8_t* keep, const double* scale,
+                   uint32_t* key, int64_t* u, hipStream_t s);
+void gbdt_qsel_hist(const uint32_t* key, const int64_t* u, int64_t npos, const int32_t* tasks,
+                    int64_t ntask, const int32_t* red, int64_t nred, int L, const int64_t* state,
+                    int pass, int64_t* part, int64_t* hist, hipStream_t s);
+void gbdt_qsel_pick(const int64_t* hist, int L, int pass, double alpha, int64_t* state,
+                    hipStream_t s);
+void gbdt_qsel_value(const int64_t* state, int L, float* out, hipStream_t s);
+// the `quantile` metric of margin [K, n]: out [2] (fp64) = {sum_i w_i sum_k
+// pinball_{alphas[k]}(y_i, m_ki), sum_i w_i}; alphas: K doubles on the device;
+// scratch: gbdt_quantile_eval_scratch() doubles
+int64_t gbdt_quantile_eval_scratch();
+void gbdt_quantile_eval(int64_t n, int K, const float* margin, const float* label,
+                        const float* weight, const double* alphas, double* scratch, double* out,
+                        hipStream_t s);
+
 // ---------------------------------------------------------- gbdt_dart.hip
 // DART dropout walk over the resident bin matrix B [n, f] (u8, 255 = missing,
 // 4-byte aligned, f <= kDartMaxF): out[i] = out[i] + coef_j * leaf_j(row i)

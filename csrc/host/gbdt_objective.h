@@ -31,7 +31,10 @@ enum GbdtObj : int {
   kObjHinge = 4,
   kObjPseudoHuber = 5,
   kObjSquaredLog = 6,
-  kObjCount = 7
+  // (7 stays unassigned: the first id the gradient kernel refuses)
+  kObjAbsolute = 8,  // reg:absoluteerror
+  kObjQuantile = 9,  // reg:quantileerror, one output (its alpha in the scalars)
+  kObjCount = 10
 };
 
 // the objectives' scalars, as they travel to the kernel
@@ -40,14 +43,15 @@ struct GbdtObjScalars {
   float tw1, tw2;          // reg:tweedie: 1 - rho and 2 - rho (tweedie_variance_power in (1, 2))
   float delta2;            // reg:pseudohubererror: huber_slope squared (> 0)
   float scale_pos_weight;  // the logistic family: rows with y == 1 weigh this much more
+  float alpha = 0.5f;      // reg:quantileerror: the output's quantile, in (0, 1)
 };
 
 // (the differences and the square are taken in double and rounded once, as
 // torch rounds a Python scalar that meets an fp32 tensor)
 inline GbdtObjScalars gbdt_obj_scalars(double max_delta_step, double rho, double delta,
-                                       double scale_pos_weight) {
+                                       double scale_pos_weight, double alpha = 0.5) {
   return {(float)max_delta_step, (float)(1.0 - rho), (float)(2.0 - rho), (float)(delta * delta),
-          (float)scale_pos_weight};
+          (float)scale_pos_weight, (float)alpha};
 }
 
 struct GbdtPair {
@@ -78,6 +82,11 @@ WH_OBJ_FN GbdtPair gbdt_obj_pair(float m, float y, const GbdtObjScalars& a) {
     const float z = m - y, d2 = a.delta2;
     const float s = sqrtf(1.f + z * z / d2);
     return {z / s, d2 / ((d2 + z * z) * s), false};
+  } else if constexpr (OBJ == kObjAbsolute) {  // h = w: no curvature, the leaves are refreshed
+    const float d = m - y;
+    return {d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f), 1.f, false};
+  } else if constexpr (OBJ == kObjQuantile) {
+    return {m - y >= 0.f ? 1.f - a.alpha : -a.alpha, 1.f, false};
   } else {
     static_assert(OBJ == kObjSquaredLog, "unknown objective id");
     const float mm = fmaxf(m, kSquaredLogMinMargin);

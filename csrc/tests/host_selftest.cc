@@ -681,6 +681,14 @@ static void test_gbdt_objective() {
   EXPECT(hinge(1.f, 1.f).g == 0.f && hinge(1.f, 1.f).h == FLT_MIN && hinge(1.f, 1.f).scaled);
   EXPECT(hinge(-0.5f, 0.f).g == 1.f && hinge(-0.5f, 0.f).h == 1.f);
   EXPECT(hinge(-1.5f, 0.f).g == 0.f && hinge(-1.5f, 0.f).h == FLT_MIN);
+  // the adaptive objectives: h = 1 per unit weight; sign(0) = 0, d = 0 on the d >= 0 side
+  auto mae = [&](float m, float y) { return wh::gbdt_obj_pair<wh::kObjAbsolute>(m, y, a); };
+  EXPECT(mae(2.f, 1.f).g == 1.f && mae(0.f, 1.f).g == -1.f && mae(1.f, 1.f).g == 0.f);
+  EXPECT(mae(2.f, 1.f).h == 1.f && !mae(2.f, 1.f).scaled);
+  const auto aq = wh::gbdt_obj_scalars(0.0, 1.5, 1.0, 1.0, 0.125);
+  auto pin = [&](float m, float y) { return wh::gbdt_obj_pair<wh::kObjQuantile>(m, y, aq); };
+  EXPECT(pin(2.f, 1.f).g == 0.875f && pin(1.f, 1.f).g == 0.875f && pin(0.f, 1.f).g == -0.125f);
+  EXPECT(pin(0.f, 1.f).h == 1.f && a.alpha == 0.5f);
   // scale_pos_weight multiplies the weight of the rows with y == 1 only
   EXPECT(wh::gbdt_obj_weight<wh::kObjLogistic>(2.f, 1.f, a) == 6.f);
   EXPECT(wh::gbdt_obj_weight<wh::kObjLogistic>(2.f, 0.f, a) == 2.f);

@@ -8,7 +8,7 @@ below), objective
 (binary:logistic, binary:logitraw, reg:logistic, reg:linear,
 reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg,
 count:poisson, reg:gamma, reg:tweedie, binary:hinge, reg:pseudohubererror,
-reg:squaredlogerror),
+reg:squaredlogerror, reg:absoluteerror, reg:quantileerror), quantile_alpha,
 num_class (the multi:
 objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
@@ -83,6 +83,24 @@ every node's weight to [-d, d] before eta. scale_pos_weight=s (s > 0)
 multiplies the weight of the rows with label 1 by s in the gradient pairs of
 the logistic objectives (not in the metrics); with another objective s != 1
 is an error (docs/bsp_apps.md "Objectives and max_delta_step").
+
+Absolute and quantile error: reg:absoluteerror (metric mae) and
+reg:quantileerror with ``quantile_alpha=0.5`` or a list,
+``quantile_alpha=[0.1,0.5,0.9]`` (brackets optional, spaces allowed, quoted in
+a conf file; every entry strictly inside (0, 1), at most 64, kept in the order
+given; any other value, or reg:quantileerror at task=train without it, ends
+the run with an error; other objectives ignore it). K = the number of alphas
+(1 for reg:absoluteerror) takes num_class's place: K trees per round, tree t
+belongs to output t % K, task=pred writes n x K row-major values. The
+prediction is the margin; base_score enters as it is and is not fitted. After
+a tree is grown and pruned, each leaf becomes eta x the exact weighted
+alpha-quantile (lower-bound rule) of the residuals of the training rows that
+reach it, over all ranks: the model does not depend on the rank count. The
+alphas are not stored in the model: task=eval with the ``quantile`` metric
+(the mean pinball loss over rows and alphas; reg:quantileerror only, its
+default, and the only metric when K > 1) takes them from the command line.
+monotone_constraints and max_delta_step > 0 are refused with either objective
+(docs/bsp_apps.md "Absolute and quantile error").
 
 DART: ``booster=dart`` (task=train) drops earlier boosting rounds before it
 grows the next one. rate_drop (in [0, 1], default 0) is a round's chance of
@@ -377,6 +395,11 @@ def main(argv):
         raise SystemExit("unknown task " + task)
     if data is None:
         raise SystemExit("need data=<path> for task=train")
+    # (the same answer on every rank, before the first collective: the alphas
+    # were validated as they were parsed; here their absence and what an
+    # adaptive objective refuses)
+    if param.objective in G.ADAPTIVE_OBJECTIVES and not model_in:
+        G.make_objective(param.objective, 0, param).check_combination(param)
     train_raw = load(data)
     eval_raw = [(name, load(path)) for name, path in evals]
     ncol = max([int(r[0].max().item()) + 1 if r[0].numel() else 0
@@ -395,6 +418,9 @@ def main(argv):
     if version > 0:
         booster = _booster_from_state(G, gstate, param)
     obj = booster.obj
+    obj.check_combination(param)
+    if obj.adaptive:  # (a continued model: as many alphas as it has outputs)
+        obj._alphas("training")
     K = obj.n_group  # trees per round: tree t of the flat list belongs to class t % K
     start = len(booster.trees) // K
     if version > 0:

@@ -28,15 +28,21 @@ from .. import _native
 # the family's other modules: parameters / objectives / metrics, the data
 # matrices and cuts, the trees and the model (every public name stays
 # reachable from this module)
-from .gbdt_objective import (GBDTParam, INTERACTION_FREE, INTERACTION_ROOT,  # noqa: F401
-                             MULTI_METRICS, NLL_MAX, OBJ_IDS, OBJ_LOGISTIC, OBJ_METRICS, Objective,
-                             RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, class_gpair,
+from .gbdt_objective import (ADAPTIVE_OBJECTIVES, AdaptiveObjective, GBDTParam,  # noqa: F401
+                             INTERACTION_FREE, make_objective,
+                             INTERACTION_ROOT, MULTI_METRICS, NLL_MAX, OBJ_ABSOLUTE, OBJ_IDS,
+                             OBJ_LOGISTIC, OBJ_METRICS, OBJ_QUANTILE, Objective,
+                             RANK_OBJECTIVES, RankGroups, SINGLE_METRICS, adaptive_gpair_torch,
+                             class_gpair,
                              eval_metric, first_argmax, gpair_stats, interaction_child,
                              multi_eval_sums, obj_eval_sums, obj_gpair_torch, parse_obj_metric,
                              parse_rank_metric, rank_eval, rank_eval_torch, rank_gpair_torch,
                              rank_metric, softmax_gpair_torch)
 from .gbdt_data import MISSING_BIN, CSRMatrix, Cuts, DMatrix, make_dmatrix  # noqa: F401
 from .gbdt_tree import Booster, RegTree, _DeviceTree, load_fmap  # noqa: F401
+from .gbdt_quantile import (leaf_quantiles, leaf_quantiles_ref, parse_quantile_alpha,  # noqa: F401
+                            pinball_sums, refresh_leaves, round_weights, select_torch,
+                            weight_scale)
 
 RT_EPS = 1e-6
 _HIST32_ROWS = 8192  # rows per int32 LDS pass of the GPU histogram
@@ -399,17 +405,21 @@ class _LevelGrower:
         return scale.float()
 
     # ----------------------------------------------------------------- build
-    def build(self, gpair, margin):
+    def build(self, gpair, margin, refresh=None):
+        """refresh: an adaptive objective's residual inputs (dict(label, at,
+        weight, keep, alpha), :func:`grow_round`): the pruned tree's leaves
+        become eta x the weighted quantile of their rows' residuals before
+        the tree is added to the margins. None: no refresh."""
         if self._native is None:
             # every rank must take the same grower (their allreduce sequences
             # differ): native only if every rank can, decided once, together
             ok = self.gpu and self.dm.n > 0 and not self.dm.sparse
             self._native = bool(self.bsp.allreduce_scalar(1.0 if ok else 0.0, "min") > 0)
         if self._native:
-            return self._build_native(gpair, margin)
-        return self._build_py(gpair, margin)
+            return self._build_native(gpair, margin, refresh)
+        return self._build_py(gpair, margin, refresh)
 
-    def _build_py(self, gpair, margin):
+    def _build_py(self, gpair, margin, refresh=None):
         p = self.p
         n = self.dm.n
         dev = self.device
@@ -533,7 +543,7 @@ class _LevelGrower:
             frontier = new_frontier
         # margins of the training rows from the final leaf segments
         done.update(seg)
-        self._finish(tree, ridx, margin, n, done)
+        self._finish(tree, ridx, margin, n, done, refresh)
         return tree
 
     def _reduce_hist(self, h):
@@ -616,12 +626,20 @@ class _LevelGrower:
         row's bins (the dense GPU matrix ``self.B``)."""
         return False
 
-    def _finish(self, tree, ridx, margin, n, leaf_segs):
-        """Prune, then add the leaf values to the training margins from the
+    def _finish(self, tree, ridx, margin, n, leaf_segs, refresh=None):
+        """Prune; refresh the leaves when an adaptive objective asks for it
+        (``refresh``, :meth:`build`); then add the leaf values to the training
+        margins and renumber."""
+        self._prune_mark(tree)
+        if refresh is not None:
+            refresh_leaves(tree, ridx, leaf_segs, n, refresh, self.p.eta, self.bsp)
+        self._add_leaves(tree, ridx, margin, n, leaf_segs)
+
+    def _add_leaves(self, tree, ridx, margin, n, leaf_segs):
+        """Add the (pruned) tree's leaf values to the training margins from the
         final (pre-prune) leaf segments, then renumber: a pruned-away
         subtree's rows take the value of its nearest ancestor that is a leaf
         after pruning, looked up BEFORE the BFS renumbering changes ids."""
-        self._prune_mark(tree)
         if self._walks(n):
             # walk the pruned tree per row on its bins (a pruned-away
             # subtree's rows stop at its collapsed root, whose leaf value
@@ -773,7 +791,7 @@ class TreeBuilder(_LevelGrower):
             cand[:, 0] = -float("inf")
         return x.pick(cand.to(self.device)).cpu()
 
-    def _build_native(self, gpair, margin):
+    def _build_native(self, gpair, margin, refresh=None):
         """The level loop in C++ (``_hip.gbdt_grow``): one host sync per
         level, device-derived child segments, fused sibling subtraction.
         Same tree as :meth:`_build_py` (which stays the CPU path and the
@@ -802,7 +820,11 @@ class TreeBuilder(_LevelGrower):
         # walked from it on the device, and its host lists are built one tree
         # later (no GPU idle between trees); needs the row walk and no
         # pruning (gamma <= 0: every accepted split has gain > RT_EPS)
-        defer = not host and self._walks(n) and p.gamma <= 0 and DEFER_TREES
+        # A leaf refresh needs every final leaf's rows as a ridx segment and
+        # the tree's lists at once: the last level is partitioned too (walk
+        # off) and nothing is deferred.
+        defer = (not host and self._walks(n) and p.gamma <= 0 and DEFER_TREES
+                 and refresh is None)
         # both return (the tree as ``gbdt_tree_from_nodes`` lists it, the final
         # ridx); deferred: (the device node table, ridx)
         if host:  # (the per-level host grower allreduces whole histograms)
@@ -813,7 +835,7 @@ class TreeBuilder(_LevelGrower):
                 root_tot=tot.contiguous(), **kw,
                 reduce_scatter=x.reduce_scatter if x is not None else None,
                 pick=x.pick if x is not None else None, f_lo=x.lo if x is not None else 0,
-                walk=self._walks(n), defer=defer)
+                walk=self._walks(n) and refresh is None, defer=defer)
         if defer:
             _native.hip().gbdt_walk_heap(self.B, grown, margin, lds=LEAF_WALK_LDS)
             tree = _DeviceTree(grown, self._cut_lists)
@@ -822,7 +844,7 @@ class TreeBuilder(_LevelGrower):
                 prev.materialize()  # (its copy finished during this tree's levels)
             return tree
         tree = RegTree.from_lists(grown)
-        self._finish(tree, ridx, margin, n, {nd: (b, e) for nd, b, e in grown[11]})
+        self._finish(tree, ridx, margin, n, {nd: (b, e) for nd, b, e in grown[11]}, refresh)
         return tree
 
     def _iota(self, n):
@@ -931,17 +953,26 @@ def grow_round(obj, builder, dm, at, into, gen=None, fgen=None):
     the outputs added to a scratch)."""
     p = builder.p
     K = obj.n_group
+    obj.check_combination(p)
     # (a rank objective's query groups: the matrix's, with their cached task plan)
     gp = obj.gpair(at, dm.label, dm.weight, dm.rank_groups())
     new = []
     for k in range(K):
         gk, mk = (class_gpair(gp, k), into[k]) if K > 1 else (gp, into)
+        keep = None
         if p.subsample < 1.0:
             keep = (torch.rand(dm.n, generator=gen) < p.subsample).to(dm.device)
             gk = gk * keep[:, None].float()
         if p.colsample_bytree < 1.0:  # (else the builder's mask stays all-features)
             builder.sample_features(fgen)
-        new.append(builder.build(gk, mk))
+        if not obj.adaptive:
+            new.append(builder.build(gk, mk))
+            continue
+        # the leaves become quantiles of the residuals at the margins the
+        # gradients were taken at (dart: those without the dropped rounds)
+        rf = dict(label=dm.label, at=at[k] if K > 1 else at, weight=dm.weight, keep=keep,
+                  alpha=obj.alphas[k])
+        new.append(builder.build(gk, mk, rf))
     return new
 
 

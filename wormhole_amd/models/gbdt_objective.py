@@ -45,6 +45,9 @@ class GBDTParam:
         self.one_drop = 0  # 1: a round that chose nothing drops one round
         self.sample_type = "uniform"  # | weighted: chances in proportion to the weights
         self.normalize_type = "tree"  # | forest
+        # reg:quantileerror: the outputs' quantiles, in the order given ([]:
+        # not set); any other objective ignores them
+        self.quantile_alpha = []
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -54,6 +57,9 @@ class GBDTParam:
             self.monotone = parse_monotone(val)
         elif name == "interaction_constraints":
             self.interaction = parse_interaction(val)
+        elif name == "quantile_alpha":
+            from .gbdt_quantile import parse_quantile_alpha
+            self.quantile_alpha = parse_quantile_alpha(val)
         elif name in ("max_delta_step", "scale_pos_weight", "tweedie_variance_power",
                       "huber_slope"):
             setattr(self, name, float(val))
@@ -268,6 +274,11 @@ NLL_MAX = -math.log(1e-16)
 OBJ_LOGISTIC = 0
 OBJ_IDS = {"count:poisson": 1, "reg:gamma": 2, "reg:tweedie": 3, "binary:hinge": 4,
            "reg:pseudohubererror": 5, "reg:squaredlogerror": 6}
+# The adaptive objectives (their own ids of the same kernel): h = w carries no
+# curvature, so a grown tree's leaves are refreshed with the weighted quantile
+# of the residuals (models/gbdt_quantile.py)
+OBJ_ABSOLUTE, OBJ_QUANTILE = 8, 9
+ADAPTIVE_OBJECTIVES = ("reg:absoluteerror", "reg:quantileerror")
 LOG_LINK_OBJECTIVES = ("count:poisson", "reg:gamma", "reg:tweedie")  # prediction exp(margin)
 FLT_MIN = 1.1754943508222875e-38
 SQUARED_LOG_MIN_MARGIN = -1.0 + 1e-6
@@ -313,17 +324,39 @@ class Objective:
     contiguous tensors a tree builder takes: one round grows K trees, tree t
     of the flat list belongs to class t % K. rank:pairwise and rank:ndcg keep
     one margin per row (the prediction is the margin) and need the rows'
-    query groups (``DMatrix.group``) for their gradient pairs."""
+    query groups (``DMatrix.group``) for their gradient pairs.
+    reg:quantileerror keeps one margin per alpha of ``quantile_alpha`` in the
+    same [K, n] layout (reg:absoluteerror: one, alpha 0.5); both are
+    ``adaptive``: their trees' leaves are refreshed with residual quantiles
+    (models/gbdt_quantile.py), for which :func:`grow_round` hands the growers
+    the residual inputs."""
 
-    def __init__(self, name, num_class=0, param=None):
+    # the names a subclass adds to the ones this class takes
+    EXTRA_NAMES = ()
+
+    def __init__(self, name, num_class=0, param=None, n_out=None):
         """param: what carries max_delta_step (``delta_step()``),
-        scale_pos_weight, tweedie_variance_power and huber_slope (a
-        :class:`GBDTParam`); None: their defaults."""
+        scale_pos_weight, tweedie_variance_power, huber_slope and
+        quantile_alpha (a :class:`GBDTParam`); None: their defaults. n_out:
+        the outputs per row of a reg:quantileerror model that is loaded (its
+        file's; the alphas are not stored and may be absent)."""
         if name not in ("binary:logistic", "reg:logistic", "reg:linear", "reg:squarederror",
                         "binary:logitraw", "multi:softmax", "multi:softprob") + RANK_OBJECTIVES \
-                and name not in OBJ_IDS:
+                + self.EXTRA_NAMES and name not in OBJ_IDS:
             raise ValueError("unknown objective " + name)
         self.name = name
+        # the adaptive objectives: alphas [K] (0.5 for reg:absoluteerror; None
+        # for a loaded reg:quantileerror model without quantile_alpha)
+        self.adaptive = name in ADAPTIVE_OBJECTIVES
+        self.alphas, self.n_out = None, 1
+        if name == "reg:absoluteerror":
+            self.alphas = [0.5]
+        elif name == "reg:quantileerror":
+            given = [float(a) for a in (getattr(param, "quantile_alpha", None) or [])]
+            if n_out is None and not given:
+                raise SystemExit("objective reg:quantileerror needs quantile_alpha")
+            self.alphas = given or None
+            self.n_out = int(n_out) if n_out is not None else len(given)
         self.rank = name in RANK_OBJECTIVES
         self.logistic = name in ("binary:logistic", "reg:logistic", "binary:logitraw")
         self.multi = name.startswith("multi:")
@@ -352,7 +385,29 @@ class Objective:
     @property
     def n_group(self):
         """Margins per row = trees per boosting round."""
-        return self.num_class if self.multi else 1
+        return self.num_class if self.multi else self.n_out
+
+    def _alphas(self, what):
+        """reg:quantileerror's alphas where they are needed."""
+        if self.alphas is None:
+            raise SystemExit("%s of objective reg:quantileerror needs quantile_alpha" % what)
+        if len(self.alphas) != self.n_out:
+            raise SystemExit("quantile_alpha has %d entries, the model has %d outputs per row"
+                             % (len(self.alphas), self.n_out))
+        return self.alphas
+
+    def check_combination(self, param):
+        """What an adaptive objective refuses: a refreshed leaf honours
+        neither monotone bounds nor max_delta_step."""
+        if not self.adaptive:
+            return
+        if any(getattr(param, "monotone", None) or []):
+            raise SystemExit("monotone_constraints does not go with objective %s (its leaves are "
+                             "refreshed with residual quantiles, outside the bounds)" % self.name)
+        if param.delta_step() > 0:
+            raise SystemExit("max_delta_step=%g does not go with objective %s (its leaves are "
+                             "refreshed with residual quantiles, outside the bound)"
+                             % (param.delta_step(), self.name))
 
     def check_labels(self, label, bsp):
         """Multi-class labels must be integers in [0, num_class): decided on
@@ -364,6 +419,8 @@ class Objective:
                 "binary:hinge": (lambda y: (y != 0) & (y != 1), "label must be 0 or 1"),
                 "reg:squaredlogerror": (lambda y: y <= -1, "label must be greater than -1"),
                 }.get(self.name)
+        if self.adaptive:  # (the residuals' keys have no place for NaN)
+            rule = (lambda y: ~torch.isfinite(y), "label must be finite")
         if rule is not None:  # (a NaN label fails every rule's complement too)
             bad = bool((rule[0](label) | (label != label)).any()) if label.numel() else False
             if bsp.allreduce_scalar(1.0 if bad else 0.0, "max") > 0:
@@ -377,6 +434,13 @@ class Objective:
 
     def check_metrics(self, names):
         for m in names:
+            if m == "quantile":
+                if self.name != "reg:quantileerror":
+                    raise ValueError("eval_metric quantile does not fit objective %s" % self.name)
+                continue
+            if self.n_out > 1:
+                raise ValueError("eval_metric %s does not fit objective %s with %d outputs per "
+                                 "row (quantile only)" % (m, self.name, self.n_out))
             # the ranking and the one-launch metrics: any single-output objective
             if parse_rank_metric(m) is not None or parse_obj_metric(m) is not None:
                 if self.multi:
@@ -409,6 +473,8 @@ class Objective:
             return self._gpair_rank(margin, label, weight, group)
         if self.multi:
             return self._gpair_softmax(margin, label, weight)
+        if self.adaptive:
+            return self._gpair_adaptive(margin, label, weight)
         oid = self.obj_id if pos_weight or self.obj_id != OBJ_LOGISTIC else None
         if oid is not None:
             return self._gpair_obj(oid, margin, label, weight)
@@ -446,6 +512,42 @@ class Objective:
             return gp
         return obj_gpair_torch(oid, margin.float(), label.float(), weight, self.max_delta_step,
                                self.rho, self.delta, self.pos_weight)
+
+    def _gpair_adaptive(self, margin, label, weight):
+        """reg:absoluteerror: g = w sign(m - y), h = w. reg:quantileerror,
+        output k: g = w (1 - alpha_k) where m_k >= y, else -w alpha_k, h = w;
+        margin [K, n] -> gpair [K, n, 2] for K > 1, one launch of the
+        gradient kernel per output, each with its root statistics."""
+        absolute = self.name == "reg:absoluteerror"
+        alphas = self._alphas("training") if not absolute else [0.5]
+        K = self.n_out
+        if K > 1 and (margin.dim() != 2 or margin.shape[0] != K):
+            raise ValueError("reg:quantileerror margins must be [len(quantile_alpha), n]")
+        gpu = (margin.is_cuda and margin.dtype == torch.float32 and label.dtype == torch.float32
+               and (weight is None or weight.dtype == torch.float32))
+        oid = OBJ_ABSOLUTE if absolute else OBJ_QUANTILE
+        gps, sts = [], []
+        for k, a in enumerate(alphas):
+            mk = margin[k] if K > 1 else margin
+            if gpu:
+                gp, st = _native.hip().gbdt_gpair_obj(
+                    margin=mk.contiguous(), label=label.contiguous(),
+                    weight=weight.contiguous() if weight is not None else None, objective=oid,
+                    quantile_alpha=a)
+                sts.append(st)
+            else:
+                gp = adaptive_gpair_torch(mk.float(), label.float(), weight,
+                                          None if absolute else a)
+            gps.append(gp)
+        if K == 1:
+            gp = gps[0]
+            if sts:
+                gp._wh_stats = sts[0]
+            return gp
+        gp = torch.stack(gps)
+        if sts:
+            gp._wh_stats = torch.stack(sts)
+        return gp
 
     def _gpair_rank(self, margin, label, weight, group):
         """The expectation of xgboost's random partner draw over a row's
@@ -498,6 +600,8 @@ class Objective:
             return torch.exp(margin)
         if self.name == "binary:hinge":
             return (margin > 0).to(margin.dtype)
+        if self.n_out > 1:  # reg:quantileerror: n x K row-major, as multi:softprob
+            return margin.t().contiguous()
         return margin
 
     def default_metric(self):
@@ -505,6 +609,8 @@ class Objective:
             return "merror"
         if self.rank:
             return "map"
+        if self.adaptive:
+            return "mae" if self.name == "reg:absoluteerror" else "quantile"
         own = {"count:poisson": "poisson-nloglik", "reg:gamma": "gamma-nloglik",
                "reg:tweedie": "tweedie-nloglik@%g" % self.rho, "binary:hinge": "error",
                "reg:pseudohubererror": "mphe", "reg:squaredlogerror": "rmsle"}.get(self.name)
@@ -559,6 +665,18 @@ class Objective:
         of the three doubles. A label outside [0, K) counts as an error with
         nll = -log(1e-16)."""
         self.check_metrics(names)
+        if "quantile" in names:
+            from .gbdt_quantile import pinball_sums
+            alphas = self._alphas("eval_metric quantile")
+            v = pinball_sums(alphas, margin, label, weight)
+            bsp.allreduce(v)
+            v = v.tolist()
+            qv = v[0] / (len(alphas) * (v[1] if v[1] > 0 else 1.0))
+            if self.n_out > 1:
+                return [qv for _ in names]
+            rest = [m for m in names if m != "quantile"]
+            vals = iter(self.metrics(rest, margin, label, weight, bsp, group) if rest else [])
+            return [qv if m == "quantile" else next(vals) for m in names]
         if not self.multi:
             parsed = {m: parse_obj_metric(m) for m in names}
             parsed = {m: v for m, v in parsed.items() if v is not None}
@@ -575,12 +693,14 @@ class Objective:
 
 
 def obj_gpair_torch(oid, margin, label, weight, max_delta_step=0.0, rho=1.5, delta=1.0,
-                    pos_weight=1.0):
+                    pos_weight=1.0, alpha=0.5):
     """The gradient pairs [n, 2] of objective id ``oid`` (``OBJ_IDS``,
     ``OBJ_LOGISTIC``) in plain torch, in the margins' precision and the
     operation order of csrc/host/gbdt_objective.h: the CPU path and the
     reference of ``gbdt_gpair_obj`` (docs/bsp_apps.md "Objectives and
     max_delta_step" has the table)."""
+    if oid in (OBJ_ABSOLUTE, OBJ_QUANTILE):
+        return adaptive_gpair_torch(margin, label, weight, None if oid == OBJ_ABSOLUTE else alpha)
     m, y = margin, label.to(margin.dtype)
     w = weight.to(m.dtype) if weight is not None else None
     final = None  # rows whose pair the weight does not multiply
@@ -617,6 +737,48 @@ def obj_gpair_torch(oid, margin, label, weight, max_delta_step=0.0, rho=1.5, del
     if w is not None:
         gw, hw = g * w, h * w
         g, h = (gw, hw) if final is None else (torch.where(final, g, gw), torch.where(final, h, hw))
+    return torch.stack([g, h], 1).float().contiguous()
+
+
+class AdaptiveObjective(Objective):
+    """reg:absoluteerror and reg:quantileerror: the objectives whose trees'
+    leaves are refreshed after growing (``adaptive``, ``alphas``). They are a
+    class of their own because the growers must be handed the residual inputs
+    (:func:`grow_round` does): :class:`Objective` itself, which any builder
+    can be driven with, does not take their names. :func:`make_objective`
+    picks the class by name."""
+
+    EXTRA_NAMES = ADAPTIVE_OBJECTIVES
+
+    def __init__(self, name, num_class=0, param=None, n_out=None):
+        if name not in ADAPTIVE_OBJECTIVES:
+            raise ValueError("objective %s is not an adaptive one" % name)
+        super().__init__(name, num_class, param, n_out=n_out)
+
+
+def make_objective(name, num_class=0, param=None, n_out=None):
+    """The objective of a name: an :class:`AdaptiveObjective` for
+    reg:absoluteerror and reg:quantileerror, else an :class:`Objective`."""
+    cls = AdaptiveObjective if name in ADAPTIVE_OBJECTIVES else Objective
+    return cls(name, num_class, param, n_out=n_out)
+
+
+def adaptive_gpair_torch(margin, label, weight, alpha=None):
+    """The gradient pairs [n, 2] of reg:absoluteerror (alpha None) or of one
+    output of reg:quantileerror in fp32 torch, in the kernel's operation
+    order: d = m - y, g = sign(d) or (d >= 0 ? 1 - alpha : -alpha) with alpha
+    rounded to fp32 first, h = 1, both times w."""
+    m, y = margin, label.to(margin.dtype)
+    d = m - y
+    if alpha is None:
+        g = torch.sign(d)
+    else:
+        a = torch.tensor(alpha, dtype=m.dtype, device=m.device)
+        g = torch.where(d >= 0, 1.0 - a, -a)
+    h = torch.ones_like(m)
+    if weight is not None:
+        w = weight.to(m.dtype)
+        g, h = g * w, h * w
     return torch.stack([g, h], 1).float().contiguous()
 
 

@@ -8,7 +8,7 @@ import torch
 
 from .. import _native
 from ..utils.fs import open_uri  # noqa: E402
-from .gbdt_objective import Objective
+from .gbdt_objective import make_objective
 
 
 # ------------------------------------------------------------------- tree
@@ -260,14 +260,16 @@ class ShapForest:
 class Booster:
     MAGIC = b"WHGB"
 
-    def __init__(self, param, num_feature):
+    def __init__(self, param, num_feature, n_out=None):
+        """n_out: the outputs per row of a loaded reg:quantileerror model
+        (:func:`make_objective`)."""
         self.param = param
         self.num_feature = int(num_feature)
         self.trees = []
         # booster=dart: one fp32 weight per tree (the K trees of a round share
         # theirs); trees beyond the list weigh 1, as every gbtree tree does
         self.tree_w = []
-        self.obj = Objective(param.objective, param.num_class, param)
+        self.obj = make_objective(param.objective, param.num_class, param, n_out=n_out)
         self.base_margin = self.obj.prob_to_margin(param.base_score)
 
     # Trees from which a GPU matrix is predicted by the forest kernels (one
@@ -480,7 +482,9 @@ class Booster:
             param.objective = objective
             param.base_score = float(base)
             param.num_class = int(fields[4]) if len(fields) == 5 else 0
-            b = Booster(param, int(nf))
+            # (a reg:quantileerror file's fifth field is its outputs per row)
+            n_out = max(1, param.num_class) if objective == "reg:quantileerror" else None
+            b = Booster(param, int(nf), n_out=n_out)
             for _ in range(int(ntree)):
                 (n,) = struct.unpack("<I", f.read(4))
                 arr = np.frombuffer(f.read(32 * n), dtype=[
