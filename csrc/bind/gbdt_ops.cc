@@ -13,6 +13,7 @@
 #include <utility>
 
 #include "host/gbdt_dart_plan.h"
+#include "host/gbdt_leaf_plan.h"
 #include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
@@ -821,6 +822,24 @@ DartChunks gbdt_dart_plan(const std::vector<int64_t>& tree_sizes, const std::vec
   for (auto& c : wh::gbdt_dart_plan(tree_sizes, sel, lds_nodes))
     out.emplace_back(c.first, c.count, c.nnode, c.staged, c.stage_off);
   return out;
+}
+
+// grow_policy=lossguide (host/gbdt_leaf_plan.h): the (leaves, depth) limits in
+// effect, ValueError with the reason when the pair is refused
+std::pair<int64_t, int64_t> gbdt_leaf_limits(int64_t max_leaves, int64_t max_depth) {
+  const auto l = wh::gbdt_leaf_limits(max_leaves, max_depth);
+  if (l.error) throw std::invalid_argument(l.error);
+  return {l.leaves, l.depth};
+}
+
+// The open leaf to split next: its index in the three lists, or -1
+int64_t gbdt_leaf_pick(const std::vector<int64_t>& node, const std::vector<int64_t>& depth,
+                       const std::vector<double>& gain, double rt_eps, int64_t depth_cap) {
+  TORCH_CHECK(node.size() == depth.size() && node.size() == gain.size(),
+              "gbdt_leaf_pick: node, depth and gain must be of one length");
+  std::vector<wh::GbdtOpenLeaf> open(node.size());
+  for (size_t i = 0; i < node.size(); ++i) open[i] = {node[i], depth[i], gain[i]};
+  return wh::gbdt_leaf_pick(open, rt_eps, depth_cap);
 }
 
 int64_t dart_rows(int64_t rows) {
@@ -1941,6 +1960,166 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
   return py::make_tuple(gbdt_tree_from_nodes(nodes.cpu(), cut_vals, cut_off), ridx);
 }
 
+// A leaf loop's node table (host float64 [NN, REC], explicit child ids) as
+// the growers' tuple, renumbered breadth-first (host/gbdt_leaf_plan.h)
+py::tuple gbdt_leaf_tree_from_nodes(const Tensor& hn, const std::vector<float>& cut_vals,
+                                    const std::vector<int64_t>& cut_off) {
+  const int REC = wh::gbdt_node_rec();
+  TORCH_CHECK(!hn.is_cuda() && hn.scalar_type() == torch::kFloat64 && hn.is_contiguous() &&
+                  hn.dim() == 2 && hn.size(1) == REC && hn.size(0) >= 1,
+              "gbdt_leaf_tree_from_nodes: a host float64 node table");
+  wh::GbdtLeafTree lt;
+  TORCH_CHECK(wh::gbdt_leaf_tree_lists(hn.data_ptr<double>(), hn.size(0), REC, &lt),
+              "gbdt_leaf_tree_from_nodes: the node table is no tree");
+  const int64_t F = (int64_t)cut_off.size() - 1;
+  for (size_t i = 0; i < lt.feat.size(); ++i)
+    TORCH_CHECK(lt.feat[i] < 0 || (lt.feat[i] < F && lt.bin[i] >= 0 &&
+                                   cut_off[lt.feat[i]] + lt.bin[i] < cut_off[lt.feat[i] + 1]),
+                "gbdt_leaf_tree_from_nodes: a split outside the cuts");
+  TreeLists t;
+  t.feat = lt.feat, t.bin = lt.bin, t.defl = lt.defl, t.left = lt.left, t.right = lt.right;
+  t.parent = lt.parent, t.gain = lt.gain, t.cover = lt.cover, t.bw = lt.bw, t.leaf = lt.leaf;
+  py::list segs;
+  for (auto& sg : lt.segs) segs.append(py::make_tuple(sg[0], sg[1], sg[2]));
+  return t.pack(cut_vals, cut_off, segs);
+}
+
+// grow_policy=lossguide on the device (gbdt.hip "the best-first leaf loop"):
+// max_leaves - 1 steps of pick-and-apply, segment partition, children,
+// smaller-child histogram with the fused sibling step and a two-slot split
+// search, all enqueued without a host wait; the node table is read once. One
+// rank, the dense matrix. walk_margin: when given, the leaf values are added
+// to it by a row walk from the device table before that read (the caller
+// neither prunes nor refreshes). Returns (the tree's lists, the final ridx:
+// every leaf's rows contiguous).
+py::tuple gbdt_grow_leaf(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, const Tensor& gpair,
+                         const Tensor& qscale, const Tensor& valid, int64_t nbin,
+                         std::vector<std::pair<int64_t, int64_t>> fgroups, int64_t max_fcnt,
+                         const Tensor& root_tot, std::vector<float> cut_vals,
+                         std::vector<int64_t> cut_off, double eta, double alpha, double lambda,
+                         double mcw, int64_t max_leaves, int64_t depth_cap, double rt_eps,
+                         const c10::optional<Tensor>& mono, const c10::optional<Tensor>& fmask,
+                         double max_delta_step, const c10::optional<Tensor>& walk_margin,
+                         bool lds) {
+  CHECK_IN(root_tot, torch::kFloat64);
+  TORCH_CHECK(root_tot.numel() == 2, "gbdt_grow_leaf: root totals are {sum g, sum h}");
+  const GrowCtx cx(B, Bc, ridx0, gpair, qscale, valid, nbin, fgroups, max_fcnt);
+  TORCH_CHECK(max_leaves >= 1 && max_leaves <= wh::kLeafMaxLeaves && depth_cap >= 1 &&
+                  depth_cap <= wh::kLeafDepthCap,
+              "gbdt_grow_leaf: max_leaves in [1, 32768], depth_cap in [1, ", wh::kLeafDepthCap, "]");
+  c10::DeviceGuard g(B.device());
+  const auto s = cx.s;
+  const int64_t n = cx.n;
+  const int F = cx.F, G = cx.G, chunk = cx.chunk;
+  const auto &f64 = cx.f64, &i32 = cx.i32;
+  TORCH_CHECK(n > 0 && B.size(0) == n && G >= 1, "gbdt_grow_leaf: B must be [n, f], n > 0");
+  const bool mono_on = present(mono);
+  if (mono_on) {
+    CHECK_IN(*mono, torch::kInt8);
+    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(),
+                "gbdt_grow_leaf: mono must be [F] on B's device");
+  }
+  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
+              "gbdt_grow_leaf: max_delta_step >= 0, and it needs mono (all zero for no signs)");
+  const int8_t* d_mono = optptr<int8_t>(mono);
+  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
+  const bool inter_on = d_fmask != nullptr;
+  const int L = (int)max_leaves, NN = (int)wh::gbdt_leaf_pool_slots(L), REC = wh::gbdt_node_rec();
+  const int WS = wh::gbdt_leaf_ws();
+  const int64_t per = (int64_t)F * nbin * 2;
+  // feature groups and the root histogram's task list: the same for every
+  // tree of a model, uploaded once per (device, rows, groups)
+  std::vector<int32_t> hw;
+  for (auto& fg : fgroups) hw.push_back((int32_t)fg.first), hw.push_back((int32_t)fg.second);
+  std::vector<int32_t> root_tasks, root_red;
+  wh::gbdt_hist_plan({n}, fgroups, chunk, &root_tasks, &root_red);
+  const int64_t nt_root = (int64_t)root_tasks.size() / 5;
+  hw.insert(hw.end(), root_tasks.begin(), root_tasks.end());
+  hw.insert(hw.end(), root_red.begin(), root_red.end());
+  static auto& upload_cache = *new std::map<std::vector<int32_t>, Tensor>();
+  std::vector<int32_t> ukey = hw;
+  ukey.push_back((int32_t)B.device().index());
+  ukey.push_back((int32_t)n);
+  auto uit = upload_cache.find(ukey);
+  if (uit == upload_cache.end()) {
+    if (upload_cache.size() > 16) upload_cache.clear();
+    uit = upload_cache
+              .emplace(ukey, torch::from_blob(hw.data(), {(int64_t)hw.size()}, torch::kInt32)
+                                 .to(B.device()))
+              .first;
+  }
+  const int32_t* d_fg = ptr<int32_t>(uit->second);
+  const int32_t* d_root_tasks = d_fg + 2 * G;
+  const int32_t* d_root_red = d_root_tasks + nt_root * 5;
+  // the tables, indexed by node id; so starts at -inf so that a node nobody
+  // searched can never be picked
+  auto nodes = torch::zeros({NN, REC}, f64);
+  auto so = torch::full({NN, 6}, -std::numeric_limits<double>::infinity(), f64);
+  auto tot = torch::zeros({NN, 2}, f64);
+  auto meta = torch::zeros({NN, 4}, i32);
+  auto ws = torch::zeros({WS}, i32);
+  Tensor bnd = mono_on ? torch::zeros({NN, 2}, f64) : Tensor();
+  Tensor state = inter_on ? torch::zeros({NN}, f64.dtype(torch::kInt64)) : Tensor();
+  auto pool = torch::empty({NN, F, nbin, 2}, f64);  // a node's histogram: slot = node id
+  double* d_bnd = mono_on ? ptr<double>(bnd) : nullptr;
+  uint64_t* d_state = inter_on ? ptr<uint64_t>(state) : nullptr;
+  const double top = max_delta_step > 0 ? max_delta_step : std::numeric_limits<double>::infinity();
+  wh::gbdt_leaf_root(ptr<double>(root_tot), (int)n, top, (uint64_t)wh::kGbdtInterRoot, eta, alpha,
+                     lambda, mcw, ptr<double>(tot), d_bnd, d_state, ptr<int32_t>(meta),
+                     ptr<double>(nodes), s);
+  const uint8_t* vp = reinterpret_cast<const uint8_t*>(valid.data_ptr());
+  Tensor ridx = ridx0.clone();  // partitioned in place, segment by segment
+  auto search = [&](int node0, int S) {
+    TORCH_CHECK(split_search(pool.narrow(0, node0, S), ptr<double>(tot) + 2 * node0, vp, S, alpha,
+                             lambda, mcw, so.narrow(0, node0, S), s, d_mono,
+                             mono_on ? d_bnd + 2 * node0 : nullptr, d_fmask,
+                             inter_on ? d_state + node0 : nullptr),
+                "gbdt_split failed");
+  };
+  if (L > 1) {
+    // (the root's {begin, end} = {0, n}: its meta entry, written by gbdt_leaf_root)
+    cx.run(ridx, d_root_tasks, nt_root, d_root_red, G, cx.part(nt_root), pool.narrow(0, 0, 1),
+           ptr<int32_t>(meta) + 2);
+    search(0, 1);
+  }
+  // a step's built child has at most ceil(n / chunk) + 1 chunks
+  const int64_t ub = ((n + chunk - 1) / chunk + 1) * G;
+  auto scratch = torch::empty_like(ridx);
+  auto tasks = torch::empty({ub * 5}, i32);
+  auto red = torch::empty({(int64_t)G * 6}, i32);
+  auto part = L > 1 ? cx.part(ub) : Tensor();
+  int32_t* d_ws = ptr<int32_t>(ws);
+  for (int k = 0; k + 1 < L; ++k) {
+    const bool last = k + 2 == L;  // the tree is full after this step
+    wh::gbdt_leaf_pick(k, (int)depth_cap, last, ptr<double>(so), ptr<double>(tot),
+                       ptr<int32_t>(meta), eta, alpha, lambda, mcw, rt_eps, ptr<double>(nodes),
+                       d_ws, s, d_mono, d_bnd, d_fmask, d_state);
+    wh::gbdt_leaf_partition(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F, ptr<int32_t>(ridx), n,
+                            d_ws, ptr<int32_t>(scratch), s);
+    wh::gbdt_leaf_children(d_ws, ptr<int32_t>(meta), ptr<double>(nodes), d_fg, G, chunk,
+                           ptr<int32_t>(tasks), ptr<int32_t>(red), s);
+    if (last) break;  // nothing reads the children's histograms or splits
+    const int l = (int)wh::gbdt_leaf_left(k);
+    cx.run(ridx, ptr<int32_t>(tasks), ub, ptr<int32_t>(red), G, part, pool.narrow(0, l, 2),
+           d_ws + 18, d_ws + 17, ptr<double>(pool), d_ws + 12, d_ws + 16);
+    search(l, 2);
+  }
+  if (present(walk_margin)) {
+    const Tensor& margin = *walk_margin;
+    CHECK_IN(margin, torch::kFloat32);
+    TORCH_CHECK(margin.numel() == n, "gbdt_grow_leaf: walk_margin must be [n]");
+    auto buf = torch::empty({6 * (int64_t)NN}, i32);
+    int32_t* b = ptr<int32_t>(buf);
+    int32_t *feat = b, *bin = b + NN, *left = b + 2 * NN, *right = b + 3 * NN;
+    float* leaf = reinterpret_cast<float*>(b + 4 * NN);
+    uint8_t* defl = reinterpret_cast<uint8_t*>(b + 5 * NN);
+    wh::gbdt_leaf_tree(ptr<double>(nodes), NN, feat, bin, defl, left, right, leaf, s);
+    wh::gbdt_leaf_walk(ptr<uint8_t>(B), n, F, NN, feat, bin, defl, left, right, leaf,
+                       ptr<float>(margin), s, lds);
+  }
+  return py::make_tuple(gbdt_leaf_tree_from_nodes(nodes.cpu(), cut_vals, cut_off), ridx);
+}
+
 }  // namespace
 
 void bind_gbdt(py::module_& m) {
@@ -1977,6 +2156,16 @@ void bind_gbdt(py::module_& m) {
         py::arg("f_lo") = 0, py::arg("walk") = false, py::arg("defer") = false,
         py::arg("mono") = py::none(), py::arg("fmask") = py::none(),
         py::arg("max_delta_step") = 0.0);
+  m.def("gbdt_grow_leaf", &gbdt_grow_leaf, py::arg("B"), py::arg("Bc"), py::arg("ridx0"),
+        py::arg("gpair"), py::arg("qscale"), py::arg("valid"), py::arg("nbin"), py::arg("fgroups"),
+        py::arg("max_fcnt"), py::arg("root_tot"), py::arg("cut_vals"), py::arg("cut_off"),
+        py::arg("eta"), py::arg("alpha"), py::arg("reg_lambda"), py::arg("min_child_weight"),
+        py::arg("max_leaves"), py::arg("depth_cap"), py::arg("rt_eps"),
+        py::arg("mono") = py::none(), py::arg("fmask") = py::none(),
+        py::arg("max_delta_step") = 0.0, py::arg("walk_margin") = py::none(),
+        py::arg("lds") = true);
+  m.def("gbdt_leaf_tree_from_nodes", &gbdt_leaf_tree_from_nodes, py::arg("nodes"),
+        py::arg("cut_vals"), py::arg("cut_off"));
   m.def("gbdt_tree_from_nodes", &gbdt_tree_from_nodes);
   m.def("gbdt_walk_heap", &gbdt_walk_heap, py::arg("B"), py::arg("nodes"), py::arg("margin"),
         py::arg("lds") = true);
@@ -2031,6 +2220,13 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_dart_lds_nodes", &wh::gbdt_dart_lds_nodes);
   m.def("gbdt_dart_max_f", [] { return (int64_t)wh::kDartMaxF; });
   m.def("gbdt_dart_max_trees", [] { return (int64_t)wh::kDartMaxTrees; });
+  m.def("gbdt_leaf_limits", &gbdt_leaf_limits, py::arg("max_leaves"), py::arg("max_depth"));
+  m.def("gbdt_leaf_depth_cap", &wh::gbdt_leaf_depth_cap);
+  m.def("gbdt_dart_max_depth", [] { return (int64_t)wh::kDartMaxDepth; });
+  m.def("gbdt_shap_max_path", [] { return (int64_t)wh::kShapMaxPath; });
+  m.def("gbdt_leaf_max_leaves", [] { return (int64_t)wh::kLeafMaxLeaves; });
+  m.def("gbdt_leaf_pick", &gbdt_leaf_pick, py::arg("node"), py::arg("depth"), py::arg("gain"),
+        py::arg("rt_eps"), py::arg("depth_cap"));
   m.def("gbdt_dart_grid", &gbdt_dart_grid, py::arg("n"), py::arg("f"), py::arg("ntree"),
         py::arg("nnode"), py::arg("rows"));
   m.def("gbdt_dart_walk", &gbdt_dart_walk, py::arg("B"), py::arg("table"), py::arg("tree_off"),

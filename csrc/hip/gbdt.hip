@@ -1732,7 +1732,421 @@ __global__ __launch_bounds__(1024) void k_gd_children(
   if (sl == 0) *ntask = tot * G;
 }
 
+// ---- the best-first leaf loop on the device (gbdt_grow_leaf) ---------------
+// grow_policy=lossguide: step k (k = 0, 1, ...) splits ONE open leaf into
+// nodes 2k + 1 and 2k + 2. Every per-node table is indexed by node id -- the
+// best splits so [NN x 6], the totals tot [NN x 2], the weight intervals bnd
+// [NN x 2], the group sets state [NN], meta [NN x 4] = {open, depth, begin,
+// end} and a node's histogram (slot = node id) -- so the host, which does not
+// know which leaf a step picks, still knows where the step's children live
+// and enqueues every launch without a wait. Node record (doubles): {left
+// child id or -1 (the right one is left + 1), feat, bin, defl, gain, cover,
+// base weight, leaf, begin, end}. The words one step's kernels hand on, ws
+// [kLeafWs] int32, are rewritten by every step's pick:
+//   0 feat (-1: the step is idle) | 1 bin | 2 defl | 3 left cursor | 4 right
+//   cursor | 5 begin | 6 end | 7 left child id | 8 children need histograms
+//   12..15 the reduce's sibling entry {0, begin, end, build_left} | 16 the
+//   parent's histogram slot | 17 histogram task count | 18, 19 built child's rows
+constexpr int kLeafWs = 20;
+constexpr int kLeafThreads = 256;
+
+// The weight of a node with totals (G, H) inside its interval, and the
+// intervals of a split's children: gd_apply's arithmetic, operation for
+// operation, so both loops give a node the same bits.
+template <bool MONO>
+__device__ __forceinline__ double leaf_weight(double G, double H, double alpha, double lambda,
+                                              double mcw, double lo, double hi) {
+  double bw = gbdt_weight0(G, H, alpha, lambda, mcw);
+  if (MONO) bw = bw < lo ? lo : (bw > hi ? hi : bw);
+  return bw;
+}
+
+__device__ __forceinline__ void leaf_record(double* q, double left, double cover, double bw,
+                                            double eta, double b, double e) {
+  q[0] = left;
+  q[1] = -1.0;
+  q[2] = q[3] = q[4] = 0.0;
+  q[5] = cover;
+  q[6] = bw;
+  q[7] = eta * bw;
+  q[8] = b;
+  q[9] = e;
+}
+
+// The root: its totals from the device, its interval (-top, top), its group
+// set, its record (a leaf over [0, n)) and its open entry.
+template <bool MONO, bool INTER>
+__global__ void k_leaf_root(const double* __restrict__ root_tot, int n, double top,
+                            uint64_t root_state, double eta, double alpha, double lambda,
+                            double mcw, double* __restrict__ tot, double* __restrict__ bnd,
+                            uint64_t* __restrict__ state, int32_t* __restrict__ meta,
+                            double* __restrict__ nodes) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const double G = root_tot[0], H = root_tot[1];
+  tot[0] = G;
+  tot[1] = H;
+  if (MONO) bnd[0] = -top, bnd[1] = top;
+  if (INTER) state[0] = root_state;
+  meta[0] = 1, meta[1] = 0, meta[2] = 0, meta[3] = n;
+  leaf_record(nodes, -1.0, H, leaf_weight<MONO>(G, H, alpha, lambda, mcw, -top, top), eta, 0.0,
+              (double)n);
+}
+
+// One block, step k: the open leaf (of the cnt = 2k + 1 nodes so far) with
+// the largest gain > rt_eps, ties to the smaller id (host/gbdt_leaf_plan.h
+// gbdt_leaf_pick; a leaf at the depth cap was never opened), then its split
+// applied: the node's record, the one-slot partition set-up, the children's
+// totals, intervals, group sets, records and open entries. No eligible leaf:
+// the step is idle (ws[0] = -1, an empty segment, no tasks) and its two node
+// ids stay unreachable leaves. last: the children can never be split (the
+// tree is full after this step), so they are not opened.
+template <bool MONO, bool INTER>
+__device__ __forceinline__ void leaf_pick(
+    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
+    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
+    double* __restrict__ nodes, int32_t* __restrict__ ws, const int8_t* __restrict__ mono,
+    double* __restrict__ bnd, const uint64_t* __restrict__ fmask, uint64_t* __restrict__ state) {
+  __shared__ double s_gain[kLeafThreads];
+  __shared__ int32_t s_id[kLeafThreads];
+  const int cnt = 2 * k + 1;
+  double bg = 0.0;
+  int32_t bi = -1;
+  for (int i = threadIdx.x; i < cnt; i += kLeafThreads) {  // ascending ids per thread
+    const double g = so[(int64_t)i * 6];
+    if (meta[4 * i] != 0 && g > rt_eps && (bi < 0 || g > bg)) bg = g, bi = i;
+  }
+  s_gain[threadIdx.x] = bg;
+  s_id[threadIdx.x] = bi;
+  __syncthreads();
+  for (int o = kLeafThreads / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double g = s_gain[threadIdx.x + o];
+      const int32_t i = s_id[threadIdx.x + o];
+      const int32_t mine = s_id[threadIdx.x];
+      if (i >= 0 && (mine < 0 || g > s_gain[threadIdx.x] ||
+                     (g == s_gain[threadIdx.x] && i < mine))) {
+        s_gain[threadIdx.x] = g;
+        s_id[threadIdx.x] = i;
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  const int nd = s_id[0], l = 2 * k + 1, r = 2 * k + 2;
+  double* ql = nodes + (int64_t)l * kNodeRec;
+  double* qr = nodes + (int64_t)r * kNodeRec;
+  for (int i = 9; i < kLeafWs; ++i) ws[i] = 0;
+  ws[7] = l;
+  if (nd < 0) {  // idle: nothing to split
+    ws[0] = -1;
+    for (int i = 1; i < 7; ++i) ws[i] = 0;
+    ws[8] = 0;
+    for (int c = l; c <= r; ++c) {
+      tot[2 * c] = tot[2 * c + 1] = 0.0;
+      if (MONO) bnd[2 * c] = bnd[2 * c + 1] = 0.0;
+      if (INTER) state[c] = 0;
+      meta[4 * c] = 0, meta[4 * c + 1] = 0, meta[4 * c + 2] = 0, meta[4 * c + 3] = 0;
+    }
+    leaf_record(ql, -1.0, 0.0, 0.0, eta, 0.0, 0.0);
+    leaf_record(qr, -1.0, 0.0, 0.0, eta, 0.0, 0.0);
+    return;
+  }
+  const double* o = so + (int64_t)nd * 6;
+  const double G = tot[2 * nd], H = tot[2 * nd + 1];
+  const double GL = o[4], HL = o[5], GR = G - GL, HR = H - HL;
+  const int feat = (int32_t)o[1];
+  const int b = meta[4 * nd + 2], e = meta[4 * nd + 3], depth = meta[4 * nd + 1] + 1;
+  double* q = nodes + (int64_t)nd * kNodeRec;
+  q[0] = (double)l;
+  q[1] = o[1];
+  q[2] = o[2];
+  q[3] = o[3];
+  q[4] = o[0];
+  meta[4 * nd] = 0;
+  double lo = 0.0, hi = 0.0, llo = 0.0, lhi = 0.0, rlo = 0.0, rhi = 0.0;
+  if (MONO) {
+    lo = bnd[2 * nd];
+    hi = bnd[2 * nd + 1];
+    llo = lo, lhi = hi, rlo = lo, rhi = hi;
+    const int c = mono[feat];
+    if (c != 0) {
+      double wl = gbdt_weight0(GL, HL, alpha, lambda, mcw);
+      double wr = gbdt_weight0(GR, HR, alpha, lambda, mcw);
+      wl = wl < lo ? lo : (wl > hi ? hi : wl);
+      wr = wr < lo ? lo : (wr > hi ? hi : wr);
+      const double mid = (wl + wr) / 2;
+      if (c > 0) lhi = mid, rlo = mid;
+      else llo = mid, rhi = mid;
+    }
+    bnd[2 * l] = llo, bnd[2 * l + 1] = lhi, bnd[2 * r] = rlo, bnd[2 * r + 1] = rhi;
+  }
+  if (INTER) state[l] = state[r] = gbdt_child_state(state[nd], fmask[feat]);
+  tot[2 * l] = GL, tot[2 * l + 1] = HL, tot[2 * r] = GR, tot[2 * r + 1] = HR;
+  const int open = !last && depth < depth_cap ? 1 : 0;
+  meta[4 * l] = open, meta[4 * l + 1] = depth;
+  meta[4 * r] = open, meta[4 * r + 1] = depth;
+  // (the children's rows: k_leaf_children, after the partition)
+  leaf_record(ql, -1.0, HL, leaf_weight<MONO>(GL, HL, alpha, lambda, mcw, llo, lhi), eta, 0.0, 0.0);
+  leaf_record(qr, -1.0, HR, leaf_weight<MONO>(GR, HR, alpha, lambda, mcw, rlo, rhi), eta, 0.0, 0.0);
+  const int bl = HL <= HR ? 1 : 0;  // build the child with the smaller global hessian
+  ws[0] = feat;
+  ws[1] = (int32_t)o[2];
+  ws[2] = (int32_t)o[3];
+  ws[3] = b;
+  ws[4] = e;
+  ws[5] = b;
+  ws[6] = e;
+  ws[8] = open;
+  ws[13] = b, ws[14] = e, ws[15] = bl;
+  ws[16] = nd;
+}
+
+__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick(
+    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
+    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
+    double* __restrict__ nodes, int32_t* __restrict__ ws) {
+  leaf_pick<false, false>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
+                          ws, nullptr, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_mono(
+    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
+    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
+    double* __restrict__ nodes, int32_t* __restrict__ ws, const int8_t* __restrict__ mono,
+    double* __restrict__ bnd) {
+  leaf_pick<true, false>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
+                         ws, mono, bnd, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_inter(
+    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
+    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
+    double* __restrict__ nodes, int32_t* __restrict__ ws, const uint64_t* __restrict__ fmask,
+    uint64_t* __restrict__ state) {
+  leaf_pick<false, true>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
+                         ws, nullptr, nullptr, fmask, state);
+}
+
+__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_mono_inter(
+    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
+    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
+    double* __restrict__ nodes, int32_t* __restrict__ ws, const int8_t* __restrict__ mono,
+    double* __restrict__ bnd, const uint64_t* __restrict__ fmask, uint64_t* __restrict__ state) {
+  leaf_pick<true, true>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
+                        ws, mono, bnd, fmask, state);
+}
+
+// The partition of ONE segment, read from the device (ws): k_part_cursor's
+// stable in-tile split on positions [begin, end) only. The grid is the upper
+// bound ceil(n / tile); a block whose tile starts past the end exits, so a
+// small leaf costs a launch, not a pass over n. Rows go to `out` at the same
+// positions (left rows from the segment's start, right rows from its end
+// down, one cursor reservation per block and side); k_leaf_copy brings them
+// back, so ridx always holds every leaf's rows contiguously.
+__global__ __launch_bounds__(kPcThreads) void k_leaf_part(
+    const uint8_t* __restrict__ B, const uint8_t* __restrict__ Bc, int64_t nrows, int f,
+    const int32_t* __restrict__ ridx, int32_t* __restrict__ ws, int32_t* __restrict__ out) {
+  __shared__ int32_t s_base[2];
+  __shared__ uint32_t s_wl[kPcThreads / 64];
+  __shared__ int32_t s_rows[kPcTile];
+  const int feat = ws[0];
+  if (feat < 0) return;
+  const int64_t e = ws[6];
+  const int64_t p0 = (int64_t)ws[5] + (int64_t)blockIdx.x * kPcTile;
+  if (p0 >= e) return;
+  const int bin = ws[1], defl = ws[2];
+  const int64_t ib = p0 + (int64_t)threadIdx.x * kPcPer;
+  const int nv = (int)max((int64_t)0, min((int64_t)kPcPer, e - ib));  // valid positions
+  int32_t rw[kPcPer];
+#pragma unroll
+  for (int u = 0; u < kPcPer; ++u) rw[u] = u < nv ? ridx[ib + u] : 0;
+  int bv[kPcPer];
+#pragma unroll
+  for (int u = 0; u < kPcPer; ++u)  // every gather in flight before the first is used
+    bv[u] = u < nv ? (Bc ? Bc[(int64_t)feat * nrows + rw[u]] : B[(int64_t)rw[u] * f + feat]) : 0;
+  uint32_t lm = 0;  // left flags of the thread's positions
+#pragma unroll
+  for (int u = 0; u < kPcPer; ++u) {
+    const int l = bv[u] == kMissing ? defl : (bv[u] <= bin ? 1 : 0);
+    lm |= (u < nv && l) ? 1u << u : 0u;
+  }
+  const uint32_t nl = (uint32_t)__popc(lm);
+  uint32_t inc = nl;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_wl[wid] = inc;
+  __syncthreads();
+  uint32_t lbefore = inc - nl, ltot = 0;
+#pragma unroll
+  for (int w = 0; w < kPcThreads / 64; ++w) {
+    if (w < wid) lbefore += s_wl[w];
+    ltot += s_wl[w];
+  }
+  const int64_t vtot = min((int64_t)kPcTile, e - p0);
+  if (threadIdx.x == 0) {
+    const int rtot = (int)(vtot - ltot);
+    s_base[0] = ltot ? atomicAdd(&ws[3], (int)ltot) : 0;
+    s_base[1] = rtot ? atomicSub(&ws[4], rtot) - rtot : 0;
+  }
+  // staged through LDS in child order (left rows, then right rows), then
+  // stored as two contiguous runs
+  int lo = (int)lbefore;
+  int ro = (int)ltot + (int)(min((int64_t)threadIdx.x * kPcPer, vtot) - lbefore);
+#pragma unroll
+  for (int u = 0; u < kPcPer; ++u) {
+    if (u >= nv) continue;
+    if ((lm >> u) & 1u) s_rows[lo++] = rw[u];
+    else s_rows[ro++] = rw[u];
+  }
+  __syncthreads();
+  const int bl = s_base[0], br = s_base[1] - (int)ltot;
+  for (int i = threadIdx.x; i < (int)vtot; i += kPcThreads)
+    out[(i < (int)ltot ? bl : br) + i] = s_rows[i];
+}
+
+// ridx [begin, end) = the partitioned rows (same grid rule as k_leaf_part)
+__global__ __launch_bounds__(kPcThreads) void k_leaf_copy(const int32_t* __restrict__ ws,
+                                                          const int32_t* __restrict__ part,
+                                                          int32_t* __restrict__ ridx) {
+  if (ws[0] < 0) return;
+  const int64_t e = ws[6];
+  const int64_t p0 = (int64_t)ws[5] + (int64_t)blockIdx.x * kPcTile;
+  for (int64_t i = p0 + threadIdx.x; i < min(p0 + kPcTile, e); i += kPcThreads) ridx[i] = part[i];
+}
+
+// One block, after the partition: the children's rows (meta and records),
+// the built child's segment and its histogram tasks from the device-side row
+// count -- ceil(rows / chunk) chunks x G feature groups, all into slot 0 of
+// the step's two-slot histogram view -- the task count and the G reduce
+// entries. No tasks when the step is idle or its children were not opened
+// (the last step, the depth cap): nothing will read their histograms.
+__global__ __launch_bounds__(kLeafThreads) void k_leaf_children(
+    int32_t* __restrict__ ws, int32_t* __restrict__ meta, double* __restrict__ nodes,
+    const int32_t* __restrict__ fg, int G, int chunk, HistTask* __restrict__ tasks,
+    HistReduce* __restrict__ red) {
+  const int feat = ws[0];
+  int32_t db = 0, de = 0;
+  if (feat >= 0) {
+    const int32_t b = ws[5], e = ws[6], m = ws[3];  // the left cursor after the partition
+    const int l = ws[7], r = l + 1;
+    if (threadIdx.x == 0) {
+      meta[4 * l + 2] = b, meta[4 * l + 3] = m, meta[4 * r + 2] = m, meta[4 * r + 3] = e;
+      nodes[(int64_t)l * kNodeRec + 8] = b, nodes[(int64_t)l * kNodeRec + 9] = m;
+      nodes[(int64_t)r * kNodeRec + 8] = m, nodes[(int64_t)r * kNodeRec + 9] = e;
+    }
+    if (ws[8] != 0) {
+      const bool bl = ws[15] != 0;
+      db = bl ? b : m;
+      de = bl ? m : e;
+    }
+  }
+  const int32_t nch = (de - db + chunk - 1) / chunk;
+  for (int q = threadIdx.x; q < nch * G; q += kLeafThreads) {
+    const int c = q / G, gi = q - c * G;
+    HistTask t;
+    t.node = 0;
+    t.fbeg = fg[2 * gi];
+    t.fcnt = fg[2 * gi + 1];
+    t.rbeg = c;
+    t.rend = chunk;
+    tasks[q] = t;
+  }
+  for (int gi = threadIdx.x; gi < G; gi += kLeafThreads) {
+    HistReduce rd;
+    rd.node = 0;
+    rd.fbeg = fg[2 * gi];
+    rd.fcnt = fg[2 * gi + 1];
+    rd.t0 = gi;
+    rd.nt = nch;
+    rd.tstride = G;
+    red[gi] = rd;
+  }
+  if (threadIdx.x == 0) {
+    ws[17] = nch * G;
+    ws[18] = db;
+    ws[19] = de;
+  }
+}
+
+// explicit-child node records -> the row walk's arrays (k_heap_tree's
+// counterpart): a node splits when its record names a left child
+__global__ __launch_bounds__(256) void k_leaf_tree(const double* __restrict__ nodes, int nn,
+                                                   int32_t* __restrict__ feat,
+                                                   int32_t* __restrict__ bin,
+                                                   uint8_t* __restrict__ defl,
+                                                   int32_t* __restrict__ left,
+                                                   int32_t* __restrict__ right,
+                                                   float* __restrict__ leaf) {
+  for (int h = blockIdx.x * blockDim.x + threadIdx.x; h < nn; h += gridDim.x * blockDim.x) {
+    const double* q = nodes + (int64_t)h * kNodeRec;
+    const int l = (int)q[0];
+    const bool split = l > h && l + 1 < nn && q[1] >= 0.0;
+    feat[h] = split ? (int32_t)q[1] : -1;
+    bin[h] = split ? (int32_t)q[2] : 0;
+    defl[h] = split ? (uint8_t)q[3] : 0;
+    left[h] = split ? l : -1;
+    right[h] = split ? l + 1 : -1;
+    leaf[h] = (float)q[7];
+  }
+}
+
 }  // namespace
+
+int gbdt_leaf_ws() { return kLeafWs; }
+
+void gbdt_leaf_root(const double* root_tot, int n, double top, uint64_t root_state, double eta,
+                    double alpha, double lambda, double mcw, double* tot, double* bnd,
+                    uint64_t* state, int32_t* meta, double* nodes, hipStream_t s) {
+  auto kern = bnd ? (state ? k_leaf_root<true, true> : k_leaf_root<true, false>)
+                  : (state ? k_leaf_root<false, true> : k_leaf_root<false, false>);
+  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, s, root_tot, n, top, root_state, eta, alpha, lambda,
+                     mcw, tot, bnd, state, meta, nodes);
+}
+
+void gbdt_leaf_pick(int k, int depth_cap, bool last, const double* so, double* tot, int32_t* meta,
+                    double eta, double alpha, double lambda, double mcw, double rt_eps,
+                    double* nodes, int32_t* ws, hipStream_t s, const int8_t* mono, double* bnd,
+                    const uint64_t* fmask, uint64_t* state) {
+  const dim3 g(1), b(kLeafThreads);
+  const int la = last ? 1 : 0;
+  if (fmask && mono)
+    hipLaunchKernelGGL(k_leaf_pick_mono_inter, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta,
+                       alpha, lambda, mcw, rt_eps, nodes, ws, mono, bnd, fmask, state);
+  else if (fmask)
+    hipLaunchKernelGGL(k_leaf_pick_inter, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha,
+                       lambda, mcw, rt_eps, nodes, ws, fmask, state);
+  else if (mono)
+    hipLaunchKernelGGL(k_leaf_pick_mono, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha,
+                       lambda, mcw, rt_eps, nodes, ws, mono, bnd);
+  else
+    hipLaunchKernelGGL(k_leaf_pick, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha, lambda,
+                       mcw, rt_eps, nodes, ws);
+}
+
+void gbdt_leaf_partition(const uint8_t* B, const uint8_t* Bc, int64_t nrows, int f, int32_t* ridx,
+                         int64_t n, int32_t* ws, int32_t* scratch, hipStream_t s) {
+  if (n <= 0) return;
+  const dim3 g((unsigned)((n + kPcTile - 1) / kPcTile)), b(kPcThreads);
+  hipLaunchKernelGGL(k_leaf_part, g, b, 0, s, B, Bc, nrows, f, ridx, ws, scratch);
+  hipLaunchKernelGGL(k_leaf_copy, g, b, 0, s, ws, scratch, ridx);
+}
+
+void gbdt_leaf_children(int32_t* ws, int32_t* meta, double* nodes, const int32_t* fg, int G,
+                        int chunk, int32_t* tasks, int32_t* red, hipStream_t s) {
+  hipLaunchKernelGGL(k_leaf_children, dim3(1), dim3(kLeafThreads), 0, s, ws, meta, nodes, fg, G,
+                     chunk, reinterpret_cast<HistTask*>(tasks), reinterpret_cast<HistReduce*>(red));
+}
+
+void gbdt_leaf_tree(const double* nodes, int nn, int32_t* feat, int32_t* bin, uint8_t* defl,
+                    int32_t* left, int32_t* right, float* leaf, hipStream_t s) {
+  if (nn <= 0) return;
+  hipLaunchKernelGGL(k_leaf_tree, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, nodes, nn,
+                     feat, bin, defl, left, right, leaf);
+}
 
 void gbdt_heap_tree(const double* nodes, int nn, int32_t* feat, int32_t* bin, uint8_t* defl,
                     int32_t* left, int32_t* right, float* leaf, hipStream_t s) {

@@ -578,6 +578,32 @@ bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const ui
                        int32_t* seg_next, uint8_t* alive_next, int32_t* dseg, int32_t* sp,
                        int32_t* par, int32_t* tasks, int32_t* ntask, int32_t* red,
                        hipStream_t s);
+// ---- the best-first leaf loop on the device (gbdt_grow_leaf in
+// csrc/bind/gbdt_ops.cc; gbdt.hip describes the tables, all indexed by node
+// id, and the gbdt_leaf_ws() int32 words one step's kernels hand on; node
+// records are gbdt_node_rec() doubles with the left child's id first)
+int gbdt_leaf_ws();
+// the root's totals, interval (-top, top; bnd may be null), group set (state
+// may be null), open entry and record
+void gbdt_leaf_root(const double* root_tot, int n, double top, uint64_t root_state, double eta,
+                    double alpha, double lambda, double mcw, double* tot, double* bnd,
+                    uint64_t* state, int32_t* meta, double* nodes, hipStream_t s);
+// step k: pick the open leaf of the largest gain among nodes 0..2k and apply
+// its split (children 2k + 1, 2k + 2), or mark the step idle
+void gbdt_leaf_pick(int k, int depth_cap, bool last, const double* so, double* tot, int32_t* meta,
+                    double eta, double alpha, double lambda, double mcw, double rt_eps,
+                    double* nodes, int32_t* ws, hipStream_t s, const int8_t* mono, double* bnd,
+                    const uint64_t* fmask, uint64_t* state);
+// partition the picked segment only (through scratch [n], copied back)
+void gbdt_leaf_partition(const uint8_t* B, const uint8_t* Bc, int64_t nrows, int f, int32_t* ridx,
+                         int64_t n, int32_t* ws, int32_t* scratch, hipStream_t s);
+// the children's rows; the built child's tasks [<= (ceil(n / chunk) + 1) G x
+// 5], their count (ws) and the reduce entries [G x 6]
+void gbdt_leaf_children(int32_t* ws, int32_t* meta, double* nodes, const int32_t* fg, int G,
+                        int chunk, int32_t* tasks, int32_t* red, hipStream_t s);
+// explicit-child node records [nn x gbdt_node_rec()] -> the leaf walk's arrays
+void gbdt_leaf_tree(const double* nodes, int nn, int32_t* feat, int32_t* bin, uint8_t* defl,
+                    int32_t* left, int32_t* right, float* leaf, hipStream_t s);
 // dseg (optional) [slots x 2] device row segments: a task's {rbeg, rend} is
 // then {chunk index, chunk rows} inside its slot's segment (empty past it)
 // level bookkeeping of the device-resident tree grower (see gbdt.hip)

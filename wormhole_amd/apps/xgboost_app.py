@@ -13,7 +13,8 @@ num_class (the multi:
 objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
-gamma, min_child_weight, max_depth, lambda, alpha, base_score, max_bin,
+gamma, min_child_weight, max_depth, grow_policy, max_leaves, lambda, alpha,
+base_score, max_bin,
 subsample, colsample_bytree, monotone_constraints, interaction_constraints,
 max_delta_step, scale_pos_weight, tweedie_variance_power, huber_slope, seed,
 eval_metric, num_round, save_period,
@@ -118,6 +119,20 @@ dart model stores one weight per tree after the trees; task=pred, eval and
 dump need no booster=, and task=dump prints the effective leaf values
 (weight x leaf; xgboost prints the unweighted ones). model_in continues a
 gbtree model with dart and a dart model with gbtree (docs/bsp_apps.md "DART").
+
+Growth policy: ``grow_policy=depthwise`` (default) grows level by level to
+max_depth; ``grow_policy=lossguide`` (task=train) grows best-first: of the open
+leaves whose best split has a gain, the one with the largest gain is split
+next (ties: the smaller node id), until the tree has max_leaves leaves or no
+leaf can be split. max_leaves is an integer in [0, 32768], default 0 (no limit
+of its own). Under lossguide max_depth=0 means no depth limit (the deepest tree
+the model's consumers take: depth 62), max_depth=D > 0 never splits a node at
+depth D, max_leaves=0 with max_depth=D means min(2^D, 32768) leaves, and
+max_leaves=0 with max_depth=0 is an error; so are an unknown grow_policy, a
+max_leaves that is no integer in range, and max_leaves > 0 under depthwise.
+With max_depth=D and max_leaves >= 2^D the model equals the depth-wise one.
+Neither parameter is stored in the model: task=pred, eval and dump need none
+(docs/bsp_apps.md "Growth policy").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -400,6 +415,7 @@ def main(argv):
     # adaptive objective refuses)
     if param.objective in G.ADAPTIVE_OBJECTIVES and not model_in:
         G.make_objective(param.objective, 0, param).check_combination(param)
+    param.leaf_limits()  # (grow_policy / max_leaves / max_depth: what is refused)
     train_raw = load(data)
     eval_raw = [(name, load(path)) for name, path in evals]
     ncol = max([int(r[0].max().item()) + 1 if r[0].numel() else 0

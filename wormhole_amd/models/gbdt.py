@@ -53,6 +53,10 @@ LEAF_WALK_LDS = True  # the LDS-resident tree walk when it fits (False: global w
 DEFER_TREES = True  # device trees: host lists one tree later (False: read every tree at once)
 HOST_GROWER = False  # the per-level host grower instead of the device level loop
 DART_BIN_WALK = True  # booster=dart: dropped trees walked on the bins from LDS (False: forest kernels)
+LEAF_LOOP_DEV = True  # grow_policy=lossguide: the leaf loop on the device (False: the Python leaf loop)
+# bytes of node histograms the device leaf loop may hold (one per node id, 2 x
+# max_leaves - 1 of them); a larger tree takes the Python leaf loop
+LEAF_POOL_BYTES = 4 << 30
 
 
 def _h2d(t, dev):
@@ -355,6 +359,8 @@ class _LevelGrower:
         # (host; gbdt_objective.py interaction_vector), None when not set
         self.fmask = param.interaction_vector(self.F)
         self._fmask_dev = None
+        # grow_policy=lossguide: (leaves, depth) in effect; None: depth-wise
+        self.limits = param.leaf_limits()
 
     def _fmask(self):
         if self.fmask is not None and self._fmask_dev is None:
@@ -415,9 +421,139 @@ class _LevelGrower:
             # differ): native only if every rank can, decided once, together
             ok = self.gpu and self.dm.n > 0 and not self.dm.sparse
             self._native = bool(self.bsp.allreduce_scalar(1.0 if ok else 0.0, "min") > 0)
+        if self.limits is not None:  # grow_policy=lossguide
+            if self._native and self._leaf_dev():
+                return self._build_leaf_native(gpair, margin, refresh)
+            return self._build_leafwise(gpair, margin, refresh)
         if self._native:
             return self._build_native(gpair, margin, refresh)
         return self._build_py(gpair, margin, refresh)
+
+    def _leaf_dev(self):
+        """True when the device leaf loop grows this builder's trees: the
+        dense GPU matrix (``_native``) on one rank, with a histogram per node
+        id within LEAF_POOL_BYTES."""
+        return False
+
+    def _build_leafwise(self, gpair, margin, refresh=None):
+        """grow_policy=lossguide: best-first growth, one split per step, over
+        the same hooks as :meth:`_build_py` -- on the CPU, on CSR data, on
+        several ranks (either histogram exchange) and, with the GPU kernels
+        behind the hooks, on the GPU (there it is the device leaf loop's
+        reference, :meth:`TreeBuilder._build_leaf_native`). The open leaves keep their histograms
+        and best splits; a step picks the one with the largest gain (gain >
+        RT_EPS, depth below the cap; ties: the smaller node id --
+        csrc/host/gbdt_leaf_plan.h), makes nodes 2k + 1 and 2k + 2 of it,
+        partitions its rows, builds the histogram of the child with the
+        smaller global hessian, derives the sibling's and searches both. It
+        ends at ``max_leaves`` leaves or when no leaf is eligible. A step
+        passes over all n positions (``_pos_node`` / ``_partition``) and, on
+        the GPU, waits for the host once: accepted for a host-driven loop."""
+        p = self.p
+        n = self.dm.n
+        dev = self.device
+        max_leaves, depth_cap = self.limits
+        pick = _native.hip().gbdt_leaf_pick
+        tree = RegTree()
+        root = tree.add(-1)
+        ridx = torch.arange(n, dtype=torch.int32, device=dev)
+        tot = gpair_stats(gpair)[0] if n else torch.zeros(2, dtype=torch.float64, device=dev)
+        self.bsp.allreduce(tot)
+        totals = {root: tot.cpu()}
+        top = self.max_delta_step if self.max_delta_step > 0 else float("inf")
+        bounds = {root: (-top, top)} if self.mono is not None else None
+        state = {root: INTERACTION_ROOT} if self.fmask is not None else None
+        fmask_h = self.fmask.tolist() if self.fmask is not None else None
+        seg = {root: (0, n)}  # every current leaf's ridx segment
+        depth = {root: 0}
+        if self.gpu:
+            self._qscale = self._hist_scale(gpair)
+        cuts_v, cuts_o = self._cut_lists
+
+        def weigh(nd):
+            G, H = float(totals[nd][0]), float(totals[nd][1])
+            tree.cover[nd] = H
+            tree.base_weight[nd] = (p.calc_weight(G, H) if bounds is None else
+                                    p.calc_weight_bounded(G, H, *bounds[nd]))
+            tree.leaf[nd] = p.eta * tree.base_weight[nd]
+
+        def search(nodes, H_all):
+            """The best splits of ``nodes`` (histograms H_all, in their
+            order): rows of the host split table."""
+            T_all = _h2d(torch.stack([totals[nd] for nd in nodes]), H_all.device)
+            B_all = S_all = None
+            if bounds is not None:
+                B_all = torch.tensor([bounds[nd] for nd in nodes], dtype=torch.float64)
+            if state is None:
+                return self._find_splits(H_all, T_all, B_all)
+            S_all = torch.tensor([state[nd] for nd in nodes], dtype=torch.int64)
+            return self._find_splits(H_all, T_all, B_all, S_all)
+
+        weigh(root)
+        # open leaves: node -> (histogram, its row of the split table); a leaf
+        # that can never be split (at the depth cap, or made by the last step)
+        # is not searched and is not open
+        open_ = {}
+        if max_leaves > 1:
+            h = self._reduce_hist(self._build_hist(ridx, gpair, [seg[root]], [0], 1))
+            open_[root] = (h[0], search([root], h)[0])
+        leaves = 1
+        while leaves < max_leaves:
+            ids = list(open_)
+            k = pick(node=ids, depth=[depth[nd] for nd in ids],
+                     gain=[float(open_[nd][1][0]) for nd in ids], rt_eps=RT_EPS,
+                     depth_cap=depth_cap)
+            if k < 0:
+                break
+            nd = ids[k]
+            hist_nd, row = open_.pop(nd)
+            bg, bf, bb, bd, bL = split_fields(row[None])
+            f, b = int(bf[0]), int(bb[0])
+            tree.feat[nd] = f
+            tree.bin[nd] = b
+            tree.cond[nd] = cuts_v[cuts_o[f] + b]
+            tree.defl[nd] = int(bd[0])
+            tree.gain[nd] = float(bg[0])
+            l, r = tree.add(nd), tree.add(nd)
+            tree.left[nd], tree.right[nd] = l, r
+            totals[l] = bL[0].double()
+            totals[r] = (totals[nd] - bL[0]).double()
+            if bounds is not None:
+                lo, hi = bounds[nd]
+                wl = p.calc_weight_bounded(float(totals[l][0]), float(totals[l][1]), lo, hi)
+                wr = p.calc_weight_bounded(float(totals[r][0]), float(totals[r][1]), lo, hi)
+                bounds[l], bounds[r] = child_bounds(int(self.mono[f]), lo, hi, wl, wr)
+            if state is not None:
+                state[l] = state[r] = interaction_child(state[nd], fmask_h[f])
+            depth[l] = depth[r] = depth[nd] + 1
+            weigh(l), weigh(r)
+            leaves += 1
+            # ---- partition the node's rows (every other position stays put)
+            nnode = len(tree.feat)
+            node_feat = torch.full((nnode,), -1, dtype=torch.int32)
+            node_bin = torch.zeros(nnode, dtype=torch.int32)
+            node_defl = torch.zeros(nnode, dtype=torch.uint8)
+            seg_beg = torch.zeros(nnode, dtype=torch.int32)
+            seg_end = torch.zeros(nnode, dtype=torch.int32)
+            node_feat[nd], node_bin[nd], node_defl[nd] = f, b, tree.defl[nd]
+            beg, end = seg.pop(nd)
+            seg_beg[nd], seg_end[nd] = beg, end
+            ridx, nleft = self._partition(ridx, self._pos_node({nd: (beg, end)}, n), node_feat,
+                                          node_bin, node_defl, seg_beg, seg_end)
+            nl = int(nleft[nd])
+            seg[l], seg[r] = (beg, beg + nl), (beg + nl, end)
+            # ---- the children's histograms and best splits, unless neither
+            # can be split again (the same decision on every rank)
+            if leaves == max_leaves or depth[l] >= depth_cap:
+                continue
+            small = l if float(totals[l][1]) <= float(totals[r][1]) else r
+            hsmall = self._reduce_hist(self._build_hist(ridx, gpair, [seg[small]], [0], 1))[0]
+            hbig = hist_nd - hsmall
+            hl, hr = (hsmall, hbig) if small == l else (hbig, hsmall)
+            found = search([l, r], torch.stack([hl, hr]))
+            open_[l], open_[r] = (hl, found[0]), (hr, found[1])
+        self._finish(tree, ridx, margin, n, seg, refresh)
+        return tree
 
     def _build_py(self, gpair, margin, refresh=None):
         p = self.p
@@ -844,6 +980,43 @@ class TreeBuilder(_LevelGrower):
                 prev.materialize()  # (its copy finished during this tree's levels)
             return tree
         tree = RegTree.from_lists(grown)
+        self._finish(tree, ridx, margin, n, {nd: (b, e) for nd, b, e in grown[11]}, refresh)
+        return tree
+
+    def _leaf_dev(self):
+        slots = 2 * self.limits[0] - 1
+        return (LEAF_LOOP_DEV and self.bsp.world == 1
+                and slots * self.F * self.nbin * 16 <= LEAF_POOL_BYTES)
+
+    def _build_leaf_native(self, gpair, margin, refresh=None):
+        """The leaf loop on the device (``_hip.gbdt_grow_leaf``): every step
+        of the tree enqueued without a host wait, the node table read once.
+        Same tree as :meth:`_build_leafwise`. Without pruning and without a
+        leaf refresh the margins are walked from the device table before
+        that read; else :meth:`_finish` takes the lists and the leaves' row
+        segments. (Trees are not deferred: the host lists are built at once.)"""
+        p = self.p
+        n = self.dm.n
+        tot = gpair_stats(gpair)[0]
+        self.bsp.allreduce(tot)
+        self._qscale = self._hist_scale(gpair)
+        walk = self._walks(n) and p.gamma <= 0 and refresh is None
+        extra = {}
+        if self.fmask is not None:
+            extra["fmask"] = self._fmask()
+        if self.max_delta_step > 0:
+            extra["max_delta_step"] = self.max_delta_step
+        grown, ridx = _native.hip().gbdt_grow_leaf(
+            B=self.B, Bc=self._feature_major(), ridx0=self._iota(n), gpair=gpair,
+            qscale=self._qscale, valid=self._valid(), nbin=self.nbin, fgroups=self.fgroups,
+            max_fcnt=self.max_fcnt, root_tot=tot.contiguous(), cut_vals=self._cut_lists[0],
+            cut_off=self._cut_lists[1], eta=float(p.eta), alpha=float(p.alpha),
+            reg_lambda=float(p.reg_lambda), min_child_weight=float(p.min_child_weight),
+            max_leaves=int(self.limits[0]), depth_cap=int(self.limits[1]), rt_eps=RT_EPS,
+            mono=self._mono(), walk_margin=margin if walk else None, lds=LEAF_WALK_LDS, **extra)
+        tree = RegTree.from_lists(grown)
+        if walk:  # (gamma <= 0: nothing to prune; the table is breadth-first already)
+            return tree.compact()
         self._finish(tree, ridx, margin, n, {nd: (b, e) for nd, b, e in grown[11]}, refresh)
         return tree
 

@@ -48,6 +48,11 @@ class GBDTParam:
         # reg:quantileerror: the outputs' quantiles, in the order given ([]:
         # not set); any other objective ignores them
         self.quantile_alpha = []
+        # tree growth (training only, not stored in the model): depthwise grows
+        # level by level; lossguide splits the open leaf of the largest gain
+        # until max_leaves leaves (0: no limit of its own) -- :meth:`leaf_limits`
+        self.grow_policy = "depthwise"
+        self.max_leaves = 0
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -73,6 +78,20 @@ class GBDTParam:
             if val not in ("gbtree", "dart"):
                 raise SystemExit("booster=%s is not supported: booster is gbtree or dart" % val)
             self.booster = val
+        elif name == "grow_policy":
+            if val not in ("depthwise", "lossguide"):
+                raise SystemExit("grow_policy=%s is not supported: grow_policy is depthwise or "
+                                 "lossguide" % val)
+            self.grow_policy = val
+        elif name == "max_leaves":
+            try:
+                x = int(str(val).strip())
+            except ValueError:
+                x = -1
+            if not 0 <= x <= _native.hip().gbdt_leaf_max_leaves():
+                raise SystemExit("max_leaves must be an integer in [0, %d], got %s"
+                                 % (_native.hip().gbdt_leaf_max_leaves(), val))
+            self.max_leaves = x
         elif name in ("rate_drop", "skip_drop"):
             try:
                 x = float(val)
@@ -97,6 +116,26 @@ class GBDTParam:
         else:
             return False
         return True
+
+    def leaf_limits(self):
+        """What grow_policy, max_leaves and max_depth put into effect, checked
+        (training only; the same answer on every rank): None under depthwise,
+        where max_leaves > 0 is refused; under lossguide (leaves, depth) -- the
+        tree stops at ``leaves`` leaves and a node at depth ``depth`` is never
+        split (csrc/host/gbdt_leaf_plan.h gbdt_leaf_limits: max_depth=0 is
+        the deepest tree the model's consumers take, depth 62; max_leaves=0
+        is min(2^max_depth, 32768); both 0 is refused)."""
+        if self.grow_policy != "lossguide":
+            if self.max_leaves > 0:
+                raise SystemExit("max_leaves=%d needs grow_policy=lossguide: grow_policy=depthwise "
+                                 "does not limit the leaves" % self.max_leaves)
+            return None
+        try:
+            return tuple(_native.hip().gbdt_leaf_limits(max_leaves=int(self.max_leaves),
+                                                        max_depth=int(self.max_depth)))
+        except ValueError as e:
+            raise SystemExit("grow_policy=lossguide with max_leaves=%d max_depth=%d: %s"
+                             % (self.max_leaves, self.max_depth, e))
 
     def delta_step(self):
         """max_delta_step in effect: as set, else xgboost's 0.7 for
