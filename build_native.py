@@ -12,11 +12,11 @@ Two shared objects are produced next to the Python sources:
   (reference learn/tool/), wrapped by ``bin/convert.dmlc`` / ``bin/text2crb.dmlc``.
 * ``bin/native/{host_selftest,gbdt_rank_plan_test,gbdt_shap_plan_test,
   gbdt_shap_inter_test,gbdt_dart_plan_test,gbdt_quantile_plan_test,
-  gbdt_leaf_plan_test}`` --
+  gbdt_leaf_plan_test,gbdt_survival_plan_test}`` --
   stand-alone tests of host code (``--sanitize`` / ``--sanitize-rank-plan`` /
   ``--sanitize-shap-plan`` / ``--sanitize-shap-inter`` / ``--sanitize-dart-plan``
-  / ``--sanitize-quantile-plan`` / ``--sanitize-leaf-plan`` build them under
-  sanitizers).
+  / ``--sanitize-quantile-plan`` / ``--sanitize-leaf-plan`` /
+  ``--sanitize-survival-plan`` build them under sanitizers).
 * ``wormhole_amd/_host.so`` -- the native C++ runtime (``csrc/host/*.cc``):
   proto-text config parser, data parsers (libsvm / criteo / adfea / crb),
   CityHash64, LZ4 block codec, RecordIO, workload pool, control-plane
@@ -168,6 +168,11 @@ def gen_ninja():
     lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, LEAF_PLAN_TEST_SRC)))
     lines.append("build %s: link_tool %s" % (
         os.path.join(ROOT, "bin", "native", "gbdt_leaf_plan_test"), obj))
+    # survival plan and AFT pair test (header only): bin/native/gbdt_survival_plan_test
+    obj = os.path.join(BUILD, "tool", "gbdt_survival_plan_test.o")
+    lines.append("build %s: tool %s" % (obj, os.path.join(ROOT, SURVIVAL_PLAN_TEST_SRC)))
+    lines.append("build %s: link_tool %s" % (
+        os.path.join(ROOT, "bin", "native", "gbdt_survival_plan_test"), obj))
     lines.append("build %s: link_hip %s" % (os.path.join(PKG, "_hip.so"), " ".join(hip_objs)))
     lines.append("build %s: link_host %s" % (os.path.join(PKG, "_host.so"), " ".join(host_objs)))
     os.makedirs(BUILD, exist_ok=True)
@@ -181,6 +186,7 @@ SHAP_INTER_TEST_SRC = "csrc/tests/gbdt_shap_inter_test.cc"
 DART_PLAN_TEST_SRC = "csrc/tests/gbdt_dart_plan_test.cc"
 QUANTILE_PLAN_TEST_SRC = "csrc/tests/gbdt_quantile_plan_test.cc"
 LEAF_PLAN_TEST_SRC = "csrc/tests/gbdt_leaf_plan_test.cc"
+SURVIVAL_PLAN_TEST_SRC = "csrc/tests/gbdt_survival_plan_test.cc"
 SELFTEST_SRCS = ("csrc/tests/host_selftest.cc", "csrc/host/parsers.cc", "csrc/host/io.cc",
                  "csrc/host/remote_fs.cc", "csrc/host/lz4.cc", "csrc/host/cityhash.cc", "csrc/host/workload_pool.cc",
                  "csrc/host/conf_parser.cc", "csrc/host/van.cc", "csrc/host/json.cc")
@@ -263,6 +269,14 @@ def build_leaf_plan_sanitized():
     return _build_plan_test_sanitized("leaf-plan", LEAF_PLAN_TEST_SRC)
 
 
+def build_survival_plan_sanitized():
+    """The survival plan and AFT pair test (csrc/host/gbdt_survival_plan.h,
+    csrc/host/gbdt_aft.h, its own main) under -fsanitize=address,undefined:
+    build/san-survival-plan/gbdt_survival_plan_test. The plain build is
+    bin/native/gbdt_survival_plan_test."""
+    return _build_plan_test_sanitized("survival-plan", SURVIVAL_PLAN_TEST_SRC)
+
+
 def build(jobs=None, clean=False, verbose=False):
     if clean and os.path.isdir(BUILD):
         shutil.rmtree(BUILD)
@@ -295,7 +309,12 @@ if __name__ == "__main__":
                     help="build the quantile select plan test under address,undefined instead")
     ap.add_argument("--sanitize-leaf-plan", action="store_true",
                     help="build the best-first growth plan test under address,undefined instead")
+    ap.add_argument("--sanitize-survival-plan", action="store_true",
+                    help="build the survival plan test under address,undefined instead")
     a = ap.parse_args()
+    if a.sanitize_survival_plan:
+        print(build_survival_plan_sanitized())
+        sys.exit(0)
     if a.sanitize_leaf_plan:
         print(build_leaf_plan_sanitized())
         sys.exit(0)

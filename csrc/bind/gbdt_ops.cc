@@ -12,6 +12,7 @@
 #include <tuple>
 #include <utility>
 
+#include "host/gbdt_aft.h"
 #include "host/gbdt_dart_plan.h"
 #include "host/gbdt_leaf_plan.h"
 #include "host/gbdt_forest_plan.h"
@@ -21,6 +22,7 @@
 #include "host/gbdt_quantile_plan.h"
 #include "host/gbdt_rank_plan.h"
 #include "host/gbdt_shap_plan.h"
+#include "host/gbdt_survival_plan.h"
 
 namespace wh_bind {
 namespace {
@@ -349,6 +351,172 @@ Tensor gbdt_obj_eval(const Tensor& margin, const Tensor& label,
                       tweedie_variance_power, huber_slope,
                       obj_scratch(margin, 1, wh::gbdt_obj_eval_scratch()), ptr<double>(out),
                       cur_stream(margin));
+  return out;
+}
+
+// ---- survival:cox. The plan of a matrix' labels (y > 0: an event at y, else
+// censored at |y|) and weights, on the labels' device (CPU tensors too: the
+// torch path shares it): the stable ascending order of t = |y| (int32), t,
+// delta (uint8) and the weights (or an empty tensor) in that order, the tie
+// runs (wh::gbdt_cox_runs, on the host: once per matrix) and the kernels'
+// zeroed workspace and ticket words.
+py::dict gbdt_cox_plan(const Tensor& label, const c10::optional<Tensor>& weight) {
+  CHECK_CONT(label);
+  CHECK_DT(label, torch::kFloat32);
+  const int64_t n = label.numel();
+  TORCH_CHECK(label.dim() == 1 && n < (int64_t)1 << 31, "gbdt_cox_plan: label must be [n], n < 2^31");
+  TORCH_CHECK(n == 0 || label.isfinite().all().item<bool>(),
+              "gbdt_cox_plan: label must be finite");
+  const bool weighted = weight.has_value() && weight->defined();
+  if (weighted)
+    TORCH_CHECK(weight->numel() == n && weight->scalar_type() == torch::kFloat32 &&
+                    weight->device() == label.device(),
+                "gbdt_cox_plan: weight must be float32 [n] on the labels' device");
+  c10::DeviceGuard g(label.device());
+  auto sorted = torch::sort(label.abs(), /*stable=*/true, /*dim=*/0, /*descending=*/false);
+  const Tensor ts = std::get<0>(sorted).contiguous(), order = std::get<1>(sorted);
+  const Tensor delta = (label > 0).to(torch::kUInt8).index_select(0, order).contiguous();
+  const auto i32 = torch::TensorOptions().dtype(torch::kInt32);
+  Tensor head = torch::empty({n}, i32), tail = torch::empty({n}, i32), ev = torch::empty({n}, i32);
+  const Tensor ts_h = ts.cpu(), delta_h = delta.cpu();
+  const int64_t events =
+      wh::gbdt_cox_runs(ts_h.data_ptr<float>(), delta_h.data_ptr<uint8_t>(), n,
+                        head.data_ptr<int32_t>(), tail.data_ptr<int32_t>(), ev.data_ptr<int32_t>());
+  py::dict p;
+  p["n"] = n;
+  p["events"] = events;
+  p["order"] = order.to(torch::kInt32).contiguous();
+  p["t"] = ts;
+  p["delta"] = delta;
+  p["weight"] = weighted ? weight->index_select(0, order).contiguous()
+                         : torch::empty({0}, label.options());
+  p["head"] = head.to(label.device());
+  p["tail"] = tail.to(label.device());
+  p["run_events"] = ev.to(label.device());
+  p["ws"] = torch::zeros({wh::gbdt_cox_ws(n).size}, label.options().dtype(torch::kFloat64));
+  p["ticket"] = torch::zeros({label.is_cuda() ? wh::gbdt_cox_ticket_words() : 0},
+                             label.options().dtype(torch::kInt32));
+  return p;
+}
+
+namespace {
+struct CoxArgs {
+  int64_t n;
+  const float* weight = nullptr;
+};
+CoxArgs cox_args(const char* op, const Tensor& margin, const Tensor& order, const Tensor& delta,
+                 const c10::optional<Tensor>& weight, const Tensor& run_events, const Tensor& ws,
+                 const Tensor& ticket) {
+  CHECK_IN(margin, torch::kFloat32);
+  CHECK_IN(order, torch::kInt32);
+  CHECK_IN(delta, torch::kUInt8);
+  CHECK_IN(run_events, torch::kInt32);
+  CHECK_IN(ws, torch::kFloat64);
+  CHECK_IN(ticket, torch::kInt32);
+  CoxArgs a;
+  a.n = margin.numel();
+  TORCH_CHECK(a.n < (int64_t)1 << 31 && order.numel() == a.n && delta.numel() == a.n &&
+                  run_events.numel() == a.n && ws.numel() == wh::gbdt_cox_ws(a.n).size &&
+                  ticket.numel() == wh::gbdt_cox_ticket_words(),
+              op, ": the plan does not fit the ", a.n, " margins");
+  if (weight.has_value() && weight->defined() && weight->numel() > 0) {
+    CHECK_IN((*weight), torch::kFloat32);
+    TORCH_CHECK(weight->numel() == a.n, op, ": weight size mismatch");
+    a.weight = ptr<float>(*weight);
+  }
+  return a;
+}
+}  // namespace
+
+// (gpair f32 [n, 2] in row order, stats f64 [4]) as gbdt_gpair; the other
+// arguments are a gbdt_cox_plan's.
+std::vector<Tensor> gbdt_gpair_cox(const Tensor& margin, const Tensor& order, const Tensor& delta,
+                                   const c10::optional<Tensor>& weight, const Tensor& run_events,
+                                   const Tensor& ws, const Tensor& ticket) {
+  const CoxArgs a = cox_args("gbdt_gpair_cox", margin, order, delta, weight, run_events, ws, ticket);
+  c10::DeviceGuard g(margin.device());
+  auto gp = torch::empty({a.n, 2}, margin.options());
+  auto st = torch::zeros({4}, margin.options().dtype(torch::kFloat64));
+  wh::gbdt_gpair_cox(a.n, ptr<float>(margin), ptr<int32_t>(order), ptr<uint8_t>(delta), a.weight,
+                     ptr<int32_t>(run_events), ptr<double>(ws), ptr<unsigned int>(ticket),
+                     ptr<float>(gp), ptr<double>(st), cur_stream(margin));
+  return {gp, st};
+}
+
+// For benchmarks/bench_gbdt_survival.py only: the first `stages` (1..3) of the
+// launches the pair and the metric share (m*, e, S), into the plan's
+// workspace; returns nothing.
+void gbdt_cox_scan_stages(const Tensor& margin, const Tensor& order, const Tensor& delta,
+                          const Tensor& run_events, const Tensor& ws, const Tensor& ticket,
+                          int64_t stages) {
+  const CoxArgs a =
+      cox_args("gbdt_cox_scan_stages", margin, order, delta, c10::nullopt, run_events, ws, ticket);
+  TORCH_CHECK(stages >= 1 && stages <= 3, "gbdt_cox_scan_stages: stages in [1, 3]");
+  c10::DeviceGuard g(margin.device());
+  wh::gbdt_cox_scan(a.n, ptr<float>(margin), ptr<int32_t>(order), ptr<int32_t>(run_events),
+                    ptr<double>(ws), ptr<unsigned int>(ticket), (int)stages, cur_stream(margin));
+}
+
+// f64 [2] = {sum over the events of ln D(t_i) - (m_i - m*), the events}
+Tensor gbdt_cox_eval(const Tensor& margin, const Tensor& order, const Tensor& delta,
+                     const Tensor& run_events, const Tensor& ws, const Tensor& ticket) {
+  const CoxArgs a =
+      cox_args("gbdt_cox_eval", margin, order, delta, c10::nullopt, run_events, ws, ticket);
+  c10::DeviceGuard g(margin.device());
+  auto out = torch::zeros({2}, margin.options().dtype(torch::kFloat64));
+  wh::gbdt_cox_eval(a.n, ptr<float>(margin), ptr<int32_t>(order), ptr<uint8_t>(delta),
+                    ptr<int32_t>(run_events), ptr<double>(ws), ptr<unsigned int>(ticket),
+                    ptr<double>(out), cur_stream(margin));
+  return out;
+}
+
+// ---- survival:aft (host/gbdt_aft.h): the rows' intervals [lower, upper]
+namespace {
+const float* aft_args(const char* op, const Tensor& margin, const Tensor& lower,
+                      const Tensor& upper, const c10::optional<Tensor>& weight, int64_t dist,
+                      double sigma) {
+  CHECK_IN(lower, torch::kFloat32);
+  CHECK_IN(upper, torch::kFloat32);
+  TORCH_CHECK(upper.numel() == lower.numel(), op, ": bound size mismatch");
+  TORCH_CHECK(dist >= 0 && dist < wh::kAftDistCount, op, ": unknown distribution id ", dist);
+  TORCH_CHECK(sigma > 0, op, ": aft_loss_distribution_scale > 0");
+  return obj_args(op, margin, lower, weight);
+}
+
+double* aft_scratch(const Tensor& like, int slot) {
+  static std::vector<Tensor> scratch(2 * 64);
+  Tensor& t = scratch[2 * like.device().index() + slot];
+  if (!t.defined())
+    t = torch::zeros({wh::gbdt_aft_scratch()}, like.options().dtype(torch::kFloat64));
+  return ptr<double>(t);
+}
+}  // namespace
+
+// (gpair f32 [n, 2], stats f64 [4]) as gbdt_gpair; dist: a wh::GbdtAftDist id
+std::vector<Tensor> gbdt_gpair_aft(const Tensor& margin, const Tensor& lower, const Tensor& upper,
+                                   const c10::optional<Tensor>& weight, int64_t dist,
+                                   double sigma) {
+  const float* wp = aft_args("gbdt_gpair_aft", margin, lower, upper, weight, dist, sigma);
+  const int64_t n = margin.numel();
+  c10::DeviceGuard g(margin.device());
+  auto gp = torch::empty({n, 2}, margin.options());
+  auto st = torch::zeros({4}, margin.options().dtype(torch::kFloat64));
+  const bool ok = wh::gbdt_gpair_aft((int)dist, n, ptr<float>(margin), ptr<float>(lower),
+                                     ptr<float>(upper), wp, (float)sigma, ptr<float>(gp),
+                                     aft_scratch(margin, 0), ptr<double>(st), cur_stream(margin));
+  TORCH_CHECK(ok, "gbdt_gpair_aft: no kernel for distribution id ", dist);
+  return {gp, st};
+}
+
+// f64 [4] = {sum w nll, sum w, rows with lower <= exp(m) <= upper, rows}
+Tensor gbdt_aft_eval(const Tensor& margin, const Tensor& lower, const Tensor& upper,
+                     const c10::optional<Tensor>& weight, int64_t dist, double sigma) {
+  const float* wp = aft_args("gbdt_aft_eval", margin, lower, upper, weight, dist, sigma);
+  c10::DeviceGuard g(margin.device());
+  auto out = torch::zeros({4}, margin.options().dtype(torch::kFloat64));
+  wh::gbdt_aft_eval((int)dist, margin.numel(), ptr<float>(margin), ptr<float>(lower),
+                    ptr<float>(upper), wp, sigma, aft_scratch(margin, 1), ptr<double>(out),
+                    cur_stream(margin));
   return out;
 }
 
@@ -2188,6 +2356,20 @@ void bind_gbdt(py::module_& m) {
   m.def("gbdt_obj_eval", &gbdt_obj_eval, py::arg("margin"), py::arg("label"), py::arg("weight"),
         py::arg("link"), py::arg("mask"), py::arg("tweedie_variance_power") = 1.5,
         py::arg("huber_slope") = 1.0);
+  // survival: the plan and the tile need no GPU
+  m.def("gbdt_cox_plan", &gbdt_cox_plan, py::arg("label"), py::arg("weight") = py::none());
+  m.def("gbdt_cox_tile", &wh::gbdt_cox_tile);
+  m.def("gbdt_gpair_cox", &gbdt_gpair_cox, py::arg("margin"), py::arg("order"), py::arg("delta"),
+        py::arg("weight"), py::arg("run_events"), py::arg("ws"), py::arg("ticket"));
+  m.def("gbdt_cox_scan_stages", &gbdt_cox_scan_stages, py::arg("margin"), py::arg("order"),
+        py::arg("delta"), py::arg("run_events"), py::arg("ws"), py::arg("ticket"),
+        py::arg("stages"));
+  m.def("gbdt_cox_eval", &gbdt_cox_eval, py::arg("margin"), py::arg("order"), py::arg("delta"),
+        py::arg("run_events"), py::arg("ws"), py::arg("ticket"));
+  m.def("gbdt_gpair_aft", &gbdt_gpair_aft, py::arg("margin"), py::arg("lower"), py::arg("upper"),
+        py::arg("weight"), py::arg("dist"), py::arg("sigma") = 1.0);
+  m.def("gbdt_aft_eval", &gbdt_aft_eval, py::arg("margin"), py::arg("lower"), py::arg("upper"),
+        py::arg("weight"), py::arg("dist"), py::arg("sigma") = 1.0);
   m.def("gbdt_gpair_softmax", &gbdt_gpair_softmax);
   m.def("gbdt_softmax_out", &gbdt_softmax_out);
   m.def("gbdt_multi_eval", &gbdt_multi_eval);

@@ -697,6 +697,35 @@ int gbdt_obj_eval_out();
 void gbdt_obj_eval(int64_t n, const float* margin, const float* label, const float* weight,
                    int link, int mask, double rho, double delta, double* scratch, double* out,
                    hipStream_t s);
+// survival:cox (gbdt_survival.hip; the plan: host/gbdt_survival_plan.h). order
+// [n]: the rows in ascending t; delta, weight_sorted (or null) and run_events
+// are in that order. ws: gbdt_cox_ws(n).size doubles; ticket: kArriveWords
+// zeroed words (left zeroed). The pairs in row order + the statistics of
+// gbdt_gpair. gbdt_cox_eval: out [2] = {sum over the events of ln D(t_i) -
+// (m_i - m*), the events}. gbdt_cox_scan: the first upto (1..3) of the stages
+// both share (m*, e, S), into ws. Nothing runs for n <= 0.
+void gbdt_cox_scan(int64_t n, const float* margin, const int32_t* order,
+                   const int32_t* run_events, double* ws, unsigned int* ticket, int upto,
+                   hipStream_t s);
+void gbdt_gpair_cox(int64_t n, const float* margin, const int32_t* order, const uint8_t* delta,
+                    const float* weight_sorted, const int32_t* run_events, double* ws,
+                    unsigned int* ticket, float* gpair, double* stats, hipStream_t s);
+void gbdt_cox_eval(int64_t n, const float* margin, const int32_t* order, const uint8_t* delta,
+                   const int32_t* run_events, double* ws, unsigned int* ticket, double* out,
+                   hipStream_t s);
+int64_t gbdt_cox_ticket_words();
+// survival:aft (host/gbdt_aft.h; dist: a GbdtAftDist id, false for any other
+// value): the clamped pairs of the rows' intervals [lower, upper] + the
+// statistics of gbdt_gpair; gbdt_aft_eval: out [4] = {sum w nll, sum w, rows
+// with lower <= exp(m) <= upper, rows}. scratch: gbdt_aft_scratch() doubles,
+// zeroed once. Nothing runs for n <= 0.
+int64_t gbdt_aft_scratch();
+bool gbdt_gpair_aft(int dist, int64_t n, const float* margin, const float* lower,
+                    const float* upper, const float* weight, float sigma, float* gpair,
+                    double* scratch, double* stats, hipStream_t s);
+void gbdt_aft_eval(int dist, int64_t n, const float* margin, const float* lower,
+                   const float* upper, const float* weight, double sigma, double* scratch,
+                   double* out, hipStream_t s);
 // multi-class softmax, class-major margin [K, n] / gpair [K, n, 2]: the pairs
 // of all K trees of a round + stats [K, 4] (per class as gbdt_gpair's) in one
 // launch; predictions (arg-max ids [n], or probabilities [n, K]); evaluation

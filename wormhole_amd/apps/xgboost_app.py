@@ -8,8 +8,9 @@ below), objective
 (binary:logistic, binary:logitraw, reg:logistic, reg:linear,
 reg:squarederror, multi:softmax, multi:softprob, rank:pairwise, rank:ndcg,
 count:poisson, reg:gamma, reg:tweedie, binary:hinge, reg:pseudohubererror,
-reg:squaredlogerror, reg:absoluteerror, reg:quantileerror), quantile_alpha,
-num_class (the multi:
+reg:squaredlogerror, reg:absoluteerror, reg:quantileerror, survival:cox,
+survival:aft), quantile_alpha, aft_loss_distribution,
+aft_loss_distribution_scale, num_class (the multi:
 objectives: K >= 2, labels 0..K-1, K trees per round, tree t of the model
 belongs to class t % K; metrics merror | mlogloss; task=pred writes n class
 ids for multi:softmax, n x K row-major probabilities for multi:softprob), eta,
@@ -133,6 +134,29 @@ max_leaves that is no integer in range, and max_leaves > 0 under depthwise.
 With max_depth=D and max_leaves >= 2^D the model equals the depth-wise one.
 Neither parameter is stored in the model: task=pred, eval and dump need none
 (docs/bsp_apps.md "Growth policy").
+
+Survival: survival:cox reads a label y > 0 as an event at time y and y <= 0
+as a row right-censored at |y| (labels must be finite). Its gradient is that
+of the Breslow partial likelihood; rows with equal times share one risk set
+(xgboost gives a tied row only the events sorted before it: without ties the
+two agree). The prediction is exp(margin), the hazard ratio; base_score > 0
+enters as its logarithm; the metric cox-nloglik (default, unweighted, nan for a
+set without an event) goes with this objective only. With several ranks every
+rank's rows are a stratum with risk sets of their own. survival:aft takes a
+row's interval [lower, upper] from ``<path>.label_lower_bound`` and
+``<path>.label_upper_bound`` beside data, test:data (task=eval) and every
+eval[name] path (task=pred needs none): one number per line, ``inf`` allowed in
+the upper file, lower finite and >= 0, upper > 0, lower <= upper; equal bounds
+are an uncensored row; the libsvm label column is ignored. Missing files for a
+set the objective trains on or its metrics are evaluated on, a wrong count or
+a value outside those rules end the run with an error that names the file.
+aft_loss_distribution=normal (default) | logistic | extreme and
+aft_loss_distribution_scale=sigma > 0 (default 1) are not stored in the
+model: task=eval takes them from the command line. The prediction is
+exp(margin), the survival time; the metrics aft-nloglik (default; the weighted
+mean of -ln max(likelihood, 1e-12)) and interval-regression-accuracy (the
+unweighted share of rows with lower <= prediction <= upper) go with this
+objective only (docs/bsp_apps.md "Survival").
 
 Learning to rank: the rank: objectives and the metrics ndcg, ndcg@k, map,
 map@k (each optionally with a trailing ``-``: a group without a relevant row
@@ -330,6 +354,66 @@ def main(argv):
         local = local[local > 0]
         return torch.cat([torch.zeros(1, dtype=torch.int64), local.cumsum(0)])
 
+    def load_bounds(path, nlocal):
+        """survival:aft's intervals of this rank's nlocal rows of ``path``
+        from ``<path>.label_lower_bound`` and ``<path>.label_upper_bound``
+        (one number per line, in file order; ``inf`` is allowed in the upper
+        file) -> (lower, upper) float32 [nlocal], or None when neither file
+        is there. Read only where the objective is survival:aft (its metrics
+        go with no other). The rank takes its slice as load_group does. A file
+        without its pair, a wrong count, a NaN, a lower bound that is
+        negative or not finite, an upper bound <= 0 or below its lower bound
+        end the run with an error that names the file (the flag is allreduced
+        before anyone raises)."""
+        base = path.split("#", 1)[0]
+        paths = [base + ".label_lower_bound", base + ".label_upper_bound"]
+        have = [host.file_size(q) > 0 for q in paths]
+        if not any(have):
+            return None
+        counts = bsp.comm.allgather_object(int(nlocal))
+        first, total = sum(counts[:bsp.rank]), sum(counts)
+        err, vals = None, []
+        for q, there in zip(paths, have):
+            if not there:
+                err = "%s: the file is missing (the other bound file is there)" % q
+                break
+            try:
+                v = torch.tensor([float(t) for t in open_uri(q).read().split()],
+                                 dtype=torch.float64).float()
+            except ValueError as e:
+                err = "%s: %s" % (q, e)
+                break
+            if v.numel() != total:
+                err = "%s: %d bounds, the data has %d rows" % (q, v.numel(), total)
+                break
+            if bool(torch.isnan(v).any()):
+                err = "%s: a bound is NaN" % q
+                break
+            vals.append(v)
+        if err is None:
+            lo, up = vals
+            if bool(((lo < 0) | ~torch.isfinite(lo)).any()):
+                err = "%s: a lower bound must be finite and not negative" % paths[0]
+            elif bool((up <= 0).any()):
+                err = "%s: an upper bound must be positive" % paths[1]
+            elif bool((lo > up).any()):
+                err = "%s: an upper bound lies below its lower bound" % paths[1]
+        if bsp.allreduce_scalar(1.0 if err else 0.0, "max") > 0:
+            raise SystemExit(err or "a bound file was refused on another rank")
+        return lo[first:first + nlocal].contiguous(), up[first:first + nlocal].contiguous()
+
+    def check_aft_data(obj, metrics, sets):
+        """What survival:aft asks of the data: sets as check_rank_data's. A
+        set the objective trains on, or aft-nloglik /
+        interval-regression-accuracy is evaluated on, needs its bound files."""
+        want = [m for m in metrics if m in ("aft-nloglik", "interval-regression-accuracy")]
+        for name, path, d, trains, evaluated in sets:
+            for who, needs in (("objective " + obj.name, obj.aft and trains),
+                               ("eval_metric " + (want or [""])[0], bool(want) and evaluated)):
+                if needs and d.lower is None:
+                    raise SystemExit("%s needs the rows' bounds: there is no %s.label_lower_bound "
+                                     "(the %s data)" % (who, path.split("#", 1)[0], name))
+
     def check_rank_data(obj, metrics, sets):
         """What ranking asks of the data: sets = [(name, path, matrix,
         trains, evaluated)]. A set the rank objective trains on, or a rank
@@ -362,7 +446,9 @@ def main(argv):
         path = test_data or data
         raw = load(path)
         group = load_group(path, raw[3].numel()) if task == "eval" else None
-        dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse, group=group)
+        bounds = load_bounds(path, raw[3].numel()) if task == "eval" and b.obj.aft else None
+        dm = G.make_dmatrix(*raw, ncol=b.num_feature, device=dev, sparse=dsparse, group=group,
+                            bounds=bounds)
         # ntree_limit counts boosting rounds (K trees each); 0 or more than
         # the model has: every tree
         limit = ntree_limit * b.obj.n_group
@@ -371,8 +457,10 @@ def main(argv):
             metrics = param.eval_metric or [b.obj.default_metric()]
             b.obj.check_metrics(metrics)
             check_rank_data(b.obj, metrics, [("test", path, dm, False, True)])
+            check_aft_data(b.obj, metrics, [("test", path, dm, False, True)])
             b.obj.check_labels(dm.label, bsp)
-            vals = b.obj.metrics(metrics, margin, dm.label, dm.weight, bsp, dm.rank_groups())
+            vals = b.obj.metrics(metrics, margin, dm.label, dm.weight, bsp, dm.rank_groups(),
+                                 data=dm)
             s = "".join("\ttest-%s:%f" % (m, v) for m, v in zip(metrics, vals))
             bsp.tracker_print(s.lstrip("\t"))
         else:
@@ -443,8 +531,13 @@ def main(argv):
         print("restart from version=%d (round %d)" % (version, start), flush=True)
     metrics = param.eval_metric or [obj.default_metric()]
     obj.check_metrics(metrics)
-    check_rank_data(obj, metrics, [("train", data, dtrain, True, bool(eval_train))] + [
-        (name, path, d, False, True) for (name, d), (_, path) in zip(deval, evals)])
+    sets = [("train", data, dtrain, True, bool(eval_train))] + [
+        (name, path, d, False, True) for (name, d), (_, path) in zip(deval, evals)]
+    if obj.aft:  # (the objective is known only now: a continued model brings its own)
+        for _, path, d, _, _ in sets:
+            d.set_bounds(*(load_bounds(path, d.n) or (None, None)))
+    check_rank_data(obj, metrics, sets)
+    check_aft_data(obj, metrics, sets)
     for d in [dtrain] + [d for _, d in deval]:
         obj.check_labels(d.label, bsp)
     margin = booster.predict_margin(dtrain)
@@ -453,7 +546,7 @@ def main(argv):
     hess = None
     if dtrain.n:
         hess = obj.gpair(margin, dtrain.label, None, dtrain.rank_groups(),
-                         pos_weight=False)[..., 1]
+                         pos_weight=False, data=dtrain)[..., 1]
         hess = hess.sum(0) if K > 1 else hess
     cuts = G.Cuts.build(dtrain, param.max_bin, bsp, hess=hess)
     B = cuts.bin(dtrain)
@@ -479,11 +572,11 @@ def main(argv):
                 for k, tree in enumerate(new):
                     d.predict_tree(tree, em[k] if K > 1 else em)
             for m, v in zip(metrics, obj.metrics(metrics, em, d.label, d.weight, bsp,
-                                                 d.rank_groups())):
+                                                 d.rank_groups(), data=d)):
                 msg += "\t%s-%s:%f" % (name, m, v)
         if eval_train:
             for m, v in zip(metrics, obj.metrics(metrics, margin, dtrain.label, dtrain.weight,
-                                                 bsp, dtrain.rank_groups())):
+                                                 bsp, dtrain.rank_groups(), data=dtrain)):
                 msg += "\ttrain-%s:%f" % (m, v)
         bsp.tracker_print(msg)
         if save_period and (r + 1) % save_period == 0 and bsp.rank == 0:

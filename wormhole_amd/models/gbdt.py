@@ -38,6 +38,9 @@ from .gbdt_objective import (ADAPTIVE_OBJECTIVES, AdaptiveObjective, GBDTParam, 
                              multi_eval_sums, obj_eval_sums, obj_gpair_torch, parse_obj_metric,
                              parse_rank_metric, rank_eval, rank_eval_torch, rank_gpair_torch,
                              rank_metric, softmax_gpair_torch)
+from .gbdt_survival import (AFT_DISTS, SURVIVAL_METRICS, SURVIVAL_OBJECTIVES, CoxPlan,  # noqa: F401
+                            aft_eval_sums, aft_eval_torch, aft_gpair, aft_gpair_torch,
+                            cox_eval_sums, cox_eval_torch, cox_gpair, cox_gpair_torch)
 from .gbdt_data import MISSING_BIN, CSRMatrix, Cuts, DMatrix, make_dmatrix  # noqa: F401
 from .gbdt_tree import Booster, RegTree, _DeviceTree, load_fmap  # noqa: F401
 from .gbdt_quantile import (leaf_quantiles, leaf_quantiles_ref, parse_quantile_alpha,  # noqa: F401
@@ -1128,7 +1131,8 @@ def grow_round(obj, builder, dm, at, into, gen=None, fgen=None):
     K = obj.n_group
     obj.check_combination(p)
     # (a rank objective's query groups: the matrix's, with their cached task plan)
-    gp = obj.gpair(at, dm.label, dm.weight, dm.rank_groups())
+    # (survival:cox takes the matrix's plan, survival:aft its bounds)
+    gp = obj.gpair(at, dm.label, dm.weight, dm.rank_groups(), data=dm)
     new = []
     for k in range(K):
         gk, mk = (class_gpair(gp, k), into[k]) if K > 1 else (gp, into)

@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from .gbdt_survival import SurvivalData
 
 MISSING_BIN = 255
 
@@ -33,12 +34,13 @@ class _QueryGroups:
 
 
 # ------------------------------------------------------------------- data
-class DMatrix(_QueryGroups):
+class DMatrix(_QueryGroups, SurvivalData):
     """A rank's rows as a dense device matrix with NaN = missing."""
 
     sparse = False
 
-    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None):
+    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None,
+                 bounds=None):
         n = offset.numel() - 1
         self.n = n
         self.ncol = int(ncol)
@@ -55,6 +57,7 @@ class DMatrix(_QueryGroups):
         self.weight = weight.to(device).float() if weight is not None else None
         self.B = None
         self.set_group(group)
+        self.set_bounds(*(bounds or (None, None)))
 
     @staticmethod
     def from_dense(X, label, device, group=None):
@@ -122,7 +125,7 @@ class DMatrix(_QueryGroups):
         return _native.hip().gbdt_shap_inter_rows(X=self.X[a:b].contiguous(), **model)
 
 
-class CSRMatrix(_QueryGroups):
+class CSRMatrix(_QueryGroups, SurvivalData):
     """A rank's rows kept sparse (libsvm data with a wide feature space:
     a dense n x ncol matrix would not fit). Row feature ids are sorted
     ascending within each row; a feature a row does not store is missing
@@ -130,7 +133,8 @@ class CSRMatrix(_QueryGroups):
 
     sparse = True
 
-    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None):
+    def __init__(self, keys, offset, val, label, weight, ncol, device, group=None,
+                 bounds=None):
         n = offset.numel() - 1
         self.n, self.ncol, self.device = n, int(ncol), device
         off = offset.to(torch.int64)
@@ -148,6 +152,7 @@ class CSRMatrix(_QueryGroups):
         self.weight = weight.to(device).float() if weight is not None else None
         self.gbin = None
         self.set_group(group)
+        self.set_bounds(*(bounds or (None, None)))
 
     def entry_rows(self):
         return torch.repeat_interleave(torch.arange(self.n, device=self.device),
@@ -218,17 +223,19 @@ class CSRMatrix(_QueryGroups):
         return X
 
 
-def make_dmatrix(keys, offset, val, label, weight, ncol, device, sparse=None, group=None):
+def make_dmatrix(keys, offset, val, label, weight, ncol, device, sparse=None, group=None,
+                 bounds=None):
     """Dense device matrix, or CSR when asked (sparse=True) or when the dense
     form would be large and mostly missing (auto: sparse=None). group: the
-    rows' query group offsets [Q + 1] (learning to rank) or None."""
+    rows' query group offsets [Q + 1] (learning to rank) or None. bounds:
+    survival:aft's (lower, upper), one entry per row each, or None."""
     n = offset.numel() - 1
     if sparse is None:
         cells = n * max(int(ncol), 1)
         sparse = int(ncol) > 4096 or (cells > (1 << 28) and keys.numel() < cells // 8)
     if sparse:
-        return CSRMatrix(keys, offset, val, label, weight, ncol, device, group)
-    return DMatrix(keys, offset, val, label, weight, ncol, device, group)
+        return CSRMatrix(keys, offset, val, label, weight, ncol, device, group, bounds)
+    return DMatrix(keys, offset, val, label, weight, ncol, device, group, bounds)
 
 
 class Cuts:

@@ -1,12 +1,14 @@
-"""GBDT parameters, objectives (single-output, multi-class softmax and
-learning to rank over query groups, with their gradient pairs) and globally
-reduced metrics; models/gbdt.py grows the trees."""
+"""GBDT parameters, objectives (single-output, multi-class softmax, learning
+to rank over query groups and survival, with their gradient pairs) and
+globally reduced metrics; models/gbdt.py grows the trees."""
 import math
 import re
 
 import torch
 
 from .. import _native
+from .gbdt_survival import (SURVIVAL_METRICS, SURVIVAL_OBJECTIVES, aft_eval_sums, aft_gpair,
+                            check_aft_params, cox_eval_sums, cox_gpair)
 
 
 # ------------------------------------------------------------------ params
@@ -53,6 +55,9 @@ class GBDTParam:
         # until max_leaves leaves (0: no limit of its own) -- :meth:`leaf_limits`
         self.grow_policy = "depthwise"
         self.max_leaves = 0
+        # survival:aft (not stored in the model): normal | logistic | extreme, sigma > 0
+        self.aft_loss_distribution = "normal"
+        self.aft_loss_distribution_scale = 1.0
 
     def set(self, name, val):
         name = self.ALIASES.get(name, name)
@@ -69,6 +74,15 @@ class GBDTParam:
                       "huber_slope"):
             setattr(self, name, float(val))
             check_objective_scalars(self)
+        elif name == "aft_loss_distribution":
+            self.aft_loss_distribution = str(val).strip()
+            check_aft_params(self)
+        elif name == "aft_loss_distribution_scale":
+            try:
+                self.aft_loss_distribution_scale = float(val)
+            except ValueError:
+                raise SystemExit("aft_loss_distribution_scale=%s: must be a positive number" % val)
+            check_aft_params(self)
         elif name in ("eta", "gamma", "min_child_weight", "alpha", "base_score", "subsample",
                       "colsample_bytree"):
             setattr(self, name, float(val))
@@ -318,7 +332,8 @@ OBJ_IDS = {"count:poisson": 1, "reg:gamma": 2, "reg:tweedie": 3, "binary:hinge":
 # of the residuals (models/gbdt_quantile.py)
 OBJ_ABSOLUTE, OBJ_QUANTILE = 8, 9
 ADAPTIVE_OBJECTIVES = ("reg:absoluteerror", "reg:quantileerror")
-LOG_LINK_OBJECTIVES = ("count:poisson", "reg:gamma", "reg:tweedie")  # prediction exp(margin)
+# prediction exp(margin); base_score > 0 enters as its logarithm
+LOG_LINK_OBJECTIVES = ("count:poisson", "reg:gamma", "reg:tweedie") + SURVIVAL_OBJECTIVES
 FLT_MIN = 1.1754943508222875e-38
 SQUARED_LOG_MIN_MARGIN = -1.0 + 1e-6
 # The metrics of the one-launch evaluation kernel ``gbdt_obj_eval`` (GbdtMetric
@@ -368,7 +383,9 @@ class Objective:
     same [K, n] layout (reg:absoluteerror: one, alpha 0.5); both are
     ``adaptive``: their trees' leaves are refreshed with residual quantiles
     (models/gbdt_quantile.py), for which :func:`grow_round` hands the growers
-    the residual inputs."""
+    the residual inputs. survival:cox and survival:aft (models/gbdt_survival.py)
+    keep one margin per row and predict exp(margin); their pairs and metrics
+    take the Cox plan resp. the AFT bounds from the rows' matrix (``data``)."""
 
     # the names a subclass adds to the ones this class takes
     EXTRA_NAMES = ()
@@ -381,7 +398,7 @@ class Objective:
         file's; the alphas are not stored and may be absent)."""
         if name not in ("binary:logistic", "reg:logistic", "reg:linear", "reg:squarederror",
                         "binary:logitraw", "multi:softmax", "multi:softprob") + RANK_OBJECTIVES \
-                + self.EXTRA_NAMES and name not in OBJ_IDS:
+                + SURVIVAL_OBJECTIVES + self.EXTRA_NAMES and name not in OBJ_IDS:
             raise ValueError("unknown objective " + name)
         self.name = name
         # the adaptive objectives: alphas [K] (0.5 for reg:absoluteerror; None
@@ -397,6 +414,10 @@ class Objective:
             self.alphas = given or None
             self.n_out = int(n_out) if n_out is not None else len(given)
         self.rank = name in RANK_OBJECTIVES
+        # survival:cox takes the matrix's plan, survival:aft its bounds (``data``
+        # of gpair / metrics); the AFT distribution and scale are not stored
+        self.cox, self.aft = name == "survival:cox", name == "survival:aft"
+        self.aft_dist, self.aft_sigma = check_aft_params(param)
         self.logistic = name in ("binary:logistic", "reg:logistic", "binary:logitraw")
         self.multi = name.startswith("multi:")
         if self.multi and int(num_class) < 2:
@@ -458,7 +479,7 @@ class Objective:
                 "binary:hinge": (lambda y: (y != 0) & (y != 1), "label must be 0 or 1"),
                 "reg:squaredlogerror": (lambda y: y <= -1, "label must be greater than -1"),
                 }.get(self.name)
-        if self.adaptive:  # (the residuals' keys have no place for NaN)
+        if self.adaptive or self.cox:  # (no place for NaN: the residuals' keys, the sort of t)
             rule = (lambda y: ~torch.isfinite(y), "label must be finite")
         if rule is not None:  # (a NaN label fails every rule's complement too)
             bad = bool((rule[0](label) | (label != label)).any()) if label.numel() else False
@@ -476,6 +497,10 @@ class Objective:
             if m == "quantile":
                 if self.name != "reg:quantileerror":
                     raise ValueError("eval_metric quantile does not fit objective %s" % self.name)
+                continue
+            if m in SURVIVAL_METRICS:
+                if not (self.cox if m == "cox-nloglik" else self.aft):
+                    raise ValueError("eval_metric %s does not fit objective %s" % (m, self.name))
                 continue
             if self.n_out > 1:
                 raise ValueError("eval_metric %s does not fit objective %s with %d outputs per "
@@ -503,11 +528,18 @@ class Objective:
             return math.log(base)
         return base
 
-    def gpair(self, margin, label, weight, group=None, pos_weight=True):
+    def gpair(self, margin, label, weight, group=None, pos_weight=True, data=None):
         """group: the rank objectives' query groups, a :class:`RankGroups`
         (``DMatrix.group``) or the int32 offsets [Q + 1]. pos_weight=False
         leaves scale_pos_weight out, as weight=None leaves the instance
-        weights out (the hessians of the quantile sketch)."""
+        weights out (the hessians of the quantile sketch). data: the matrix
+        the rows belong to; survival:cox takes its cached plan from it (None:
+        a plan is built for this call), survival:aft its bounds."""
+        if self.cox:
+            return cox_gpair(margin, label, weight, data.cox_plan() if data is not None else None)
+        if self.aft:
+            lower, upper = self._bounds(data)
+            return aft_gpair(margin, lower, upper, weight, self.aft_dist, self.aft_sigma)
         if self.rank:
             return self._gpair_rank(margin, label, weight, group)
         if self.multi:
@@ -534,6 +566,12 @@ class Objective:
         if weight is not None:
             g, h = g * weight, h * weight
         return torch.stack([g, h], 1).float().contiguous()
+
+    def _bounds(self, data):
+        if data is None or getattr(data, "lower", None) is None:
+            raise ValueError("objective survival:aft and its metrics need the rows' bounds (a "
+                             "<data>.label_lower_bound and a <data>.label_upper_bound file)")
+        return data.lower, data.upper
 
     def _gpair_obj(self, oid, margin, label, weight):
         """The objectives of ``OBJ_IDS`` and the logistic family under
@@ -650,6 +688,8 @@ class Objective:
             return "map"
         if self.adaptive:
             return "mae" if self.name == "reg:absoluteerror" else "quantile"
+        if self.cox or self.aft:
+            return "cox-nloglik" if self.cox else "aft-nloglik"
         own = {"count:poisson": "poisson-nloglik", "reg:gamma": "gamma-nloglik",
                "reg:tweedie": "tweedie-nloglik@%g" % self.rho, "binary:hinge": "error",
                "reg:pseudohubererror": "mphe", "reg:squaredlogerror": "rmsle"}.get(self.name)
@@ -692,7 +732,28 @@ class Objective:
                     math.sqrt(x) if base == "rmsle" else x)
         return out
 
-    def metrics(self, names, margin, label, weight, bsp, group=None):
+    def _survival_metrics(self, names, margin, label, weight, bsp, data):
+        """{name: value} of the survival metrics among ``names``. cox-nloglik:
+        every rank's rows are one stratum; one allreduce of {sum loss,
+        events}, nan without an event. aft-nloglik (the weighted mean) and
+        interval-regression-accuracy (the unweighted share) from one
+        evaluation and one allreduce of its four sums."""
+        out = {}
+        if "cox-nloglik" in names:
+            v = cox_eval_sums(margin, label, data.cox_plan() if data is not None else None)
+            bsp.allreduce(v)
+            v = v.tolist()
+            out["cox-nloglik"] = v[0] / v[1] if v[1] > 0 else float("nan")
+        if "aft-nloglik" in names or "interval-regression-accuracy" in names:
+            lower, upper = self._bounds(data)
+            v = aft_eval_sums(margin, lower, upper, weight, self.aft_dist, self.aft_sigma)
+            bsp.allreduce(v)
+            v = v.tolist()
+            out["aft-nloglik"] = v[0] / (v[1] if v[1] > 0 else 1.0)
+            out["interval-regression-accuracy"] = v[2] / (v[3] if v[3] > 0 else 1.0)
+        return out
+
+    def metrics(self, names, margin, label, weight, bsp, group=None, data=None):
         """Globally reduced metrics of a set from its margins. The ranking
         metrics (ndcg, map, with ``@k`` and ``-``) are the unweighted mean of
         the per-group values over the non-empty groups of every rank: one
@@ -714,12 +775,16 @@ class Objective:
             if self.n_out > 1:
                 return [qv for _ in names]
             rest = [m for m in names if m != "quantile"]
-            vals = iter(self.metrics(rest, margin, label, weight, bsp, group) if rest else [])
+            vals = iter(self.metrics(rest, margin, label, weight, bsp, group, data)
+                        if rest else [])
             return [qv if m == "quantile" else next(vals) for m in names]
         if not self.multi:
             parsed = {m: parse_obj_metric(m) for m in names}
             parsed = {m: v for m, v in parsed.items() if v is not None}
             own = self._obj_metrics(parsed, margin, label, weight, bsp) if parsed else {}
+            if any(m in SURVIVAL_METRICS for m in names):
+                sv = self._survival_metrics(names, margin, label, weight, bsp, data)
+                own.update({m: v for m, v in sv.items() if m in names})
             p = self.pred(margin) if len(own) < len(names) else None
             return [own[m] if m in own else
                     rank_metric(m, margin, label, group, bsp) if parse_rank_metric(m)
