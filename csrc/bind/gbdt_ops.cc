@@ -18,6 +18,7 @@
 #include "host/gbdt_forest_plan.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
+#include "host/gbdt_node_rule.h"
 #include "host/gbdt_objective.h"
 #include "host/gbdt_quantile_plan.h"
 #include "host/gbdt_rank_plan.h"
@@ -113,55 +114,94 @@ void gbdt_hist(const Tensor& B, int64_t nbin, const Tensor& ridx, const Tensor& 
 // The best split of each of S slots into out [S, 6] {gain, feature, bin, dir,
 // GL, HL}: hist [S, F, nbin, 2], totals [S x 2] and the [F x nbin] candidate
 // mask on hist's device. False: the kernel refused (nbin > 1024 or no input).
-// monotone_constraints: mono (int8 per feature of hist, else null) and the
-// slots' weight intervals bounds [S x 2]. interaction_constraints: fmask (a
-// group bit set per feature of hist, else null) and the slots' state [S].
+// c: the constraints over hist's features and these slots (wh_kernels.h).
 bool split_search(const Tensor& hist, const double* totals, const uint8_t* valid, int S,
                   double alpha, double lambda, double mcw, const Tensor& out, hipStream_t s,
-                  const int8_t* mono = nullptr, const double* bounds = nullptr,
-                  const uint64_t* fmask = nullptr, const uint64_t* state = nullptr) {
+                  const wh::GbdtCons& c) {
   auto cand = torch::empty({std::max<int64_t>(S * hist.size(1) * 4, 1)}, hist.options());
   return wh::gbdt_split(ptr<double>(hist), totals, valid, S, (int)hist.size(1), (int)hist.size(2),
-                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s, mono, bounds,
-                        fmask, state);
+                        alpha, lambda, mcw, ptr<double>(cand), ptr<double>(out), s, c);
 }
 
-// the optional (mono [F] int8, bounds [S, 2] float64) pair of a split search
-// on `like`'s device: both or neither
-void check_mono(const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds,
-                const Tensor& like, int64_t S, int64_t F) {
-  TORCH_CHECK(mono.has_value() == bounds.has_value(), "mono and bounds go together");
-  if (!mono.has_value()) return;
-  CHECK_IN(*mono, torch::kInt8);
-  CHECK_IN(*bounds, torch::kFloat64);
-  TORCH_CHECK(mono->device() == like.device() && bounds->device() == like.device(),
-              "mono / bounds on another device");
-  TORCH_CHECK(mono->numel() == F, "mono must be [F]");
-  TORCH_CHECK(bounds->numel() == 2 * S, "bounds must be [S, 2]");
+// An array of a constraint, when `given`: `name` must be a contiguous GPU
+// tensor of dtype dt (CHECK_IN's texts, under the tensor's and the caller's
+// names) with n elements on like's device. Null when it is not given.
+template <typename T>
+const T* cons_array(bool given, const c10::optional<Tensor>& t, c10::ScalarType dt, int64_t n,
+                    const Tensor& like, const char* who, const char* name, const char* shape) {
+  if (!given) return nullptr;
+  TORCH_CHECK(t->is_cuda(), who, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t->is_contiguous(), who, ": ", name, " must be contiguous");
+  TORCH_CHECK(t->scalar_type() == dt, who, ": ", name, " has wrong dtype ", t->scalar_type());
+  TORCH_CHECK(t->device() == like.device(), who, ": ", name, " on another device");
+  TORCH_CHECK(t->numel() == n, who, ": ", name, " must be ", shape);
+  return reinterpret_cast<const T*>(t->data_ptr());
 }
 
-// the optional (fmask [F], state [S]) pair of a split search on `like`'s
-// device, int64 bit patterns (host/gbdt_level_plan.h): both or neither
-void check_inter(const c10::optional<Tensor>& fmask, const c10::optional<Tensor>& state,
-                 const Tensor& like, int64_t S, int64_t F) {
-  TORCH_CHECK(fmask.has_value() == state.has_value(), "fmask and state go together");
-  if (!fmask.has_value()) return;
-  CHECK_IN(*fmask, torch::kInt64);
-  CHECK_IN(*state, torch::kInt64);
-  TORCH_CHECK(fmask->device() == like.device() && state->device() == like.device(),
-              "fmask / state on another device");
-  TORCH_CHECK(fmask->numel() == F, "fmask must be [F]");
-  TORCH_CHECK(state->numel() == S, "state must be [S]");
+// The constraints of a stand-alone split search (`who`): the optional pairs
+// (mono [F] int8, bounds [S, 2] float64) and (fmask [F], state [S], int64 bit
+// patterns), each both or neither
+wh::GbdtCons split_cons(const c10::optional<Tensor>& mono, const c10::optional<Tensor>& bounds,
+                        const c10::optional<Tensor>& fmask, const c10::optional<Tensor>& state,
+                        const Tensor& like, int64_t S, int64_t F, const char* who) {
+  const bool m = mono.has_value(), i = fmask.has_value();
+  TORCH_CHECK(m == bounds.has_value(), who, ": mono and bounds go together");
+  TORCH_CHECK(i == state.has_value(), who, ": fmask and state go together");
+  wh::GbdtCons c;
+  c.mono = cons_array<int8_t>(m, mono, torch::kInt8, F, like, who, "mono", "[F]");
+  c.bnd = cons_array<double>(m, bounds, torch::kFloat64, 2 * S, like, who, "bounds", "[S, 2]");
+  c.fmask = cons_array<uint64_t>(i, fmask, torch::kInt64, F, like, who, "fmask", "[F]");
+  c.state = cons_array<uint64_t>(i, state, torch::kInt64, S, like, who, "state", "[S]");
+  return c;
 }
 
-// the feature masks of a grower: int64 [F] on B's device, or null
-const uint64_t* grower_fmask(const c10::optional<Tensor>& fmask, const Tensor& B, int F) {
-  if (!present(fmask)) return nullptr;
-  CHECK_IN(*fmask, torch::kInt64);
-  TORCH_CHECK(fmask->numel() == F && fmask->device() == B.device(),
-              "fmask must be [F] on B's device");
-  return optptr<uint64_t>(fmask);
-}
+// The constraints of a grower, checked once: mono [F] int8
+// (monotone_constraints) and fmask [F] int64 (interaction_constraints) on B's
+// device, each optional and over ALL features, and max_delta_step, which
+// bounds the root's interval and therefore needs mono (all zero for no signs).
+struct GrowCons {
+  const int8_t* mono;
+  const uint64_t* fmask;
+  bool mono_on, inter_on;
+  double top;  // the root's interval is (-top, top)
+
+  GrowCons(const c10::optional<Tensor>& mono_, const c10::optional<Tensor>& fmask_,
+           double max_delta_step, const Tensor& B, int F, const char* who)
+      : mono(cons_array<int8_t>(present(mono_), mono_, torch::kInt8, F, B, who, "mono", "[F]")),
+        fmask(cons_array<uint64_t>(present(fmask_), fmask_, torch::kInt64, F, B, who, "fmask",
+                                   "[F]")),
+        mono_on(mono != nullptr), inter_on(fmask != nullptr),
+        top(max_delta_step > 0 ? max_delta_step : std::numeric_limits<double>::infinity()) {
+    TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on), who,
+                ": max_delta_step >= 0, and it needs mono (all zero for no signs)");
+  }
+
+  // a split search over the slots whose intervals start at bnd [. x 2] and
+  // whose group sets start at state [.] (neither is read when its constraint
+  // is off) and over the features from f_lo on
+  wh::GbdtCons at(const double* bnd, const uint64_t* state, int64_t f_lo = 0) const {
+    wh::GbdtCons c;
+    if (mono_on) c.mono = mono + f_lo, c.bnd = bnd;
+    if (inter_on) c.fmask = fmask + f_lo, c.state = state;
+    return c;
+  }
+  // (the same from slot0 of two tables, undefined when their constraint is off)
+  wh::GbdtCons at(const Tensor& bnd, const Tensor& state, int64_t slot0 = 0,
+                  int64_t f_lo = 0) const {
+    return at(mono_on ? ptr<double>(bnd) + 2 * slot0 : nullptr,
+              inter_on ? ptr<uint64_t>(state) + slot0 : nullptr, f_lo);
+  }
+
+  // a bookkeeping step, which also writes: the children's tables (undefined
+  // when there are none), or the leaf loop's own in place
+  wh::GbdtCons step(const Tensor& bnd, const Tensor& state, const Tensor& bnd_out,
+                    const Tensor& state_out) const {
+    wh::GbdtCons c = at(bnd, state);
+    if (mono_on && bnd_out.defined()) c.bnd_out = ptr<double>(bnd_out);
+    if (inter_on && state_out.defined()) c.state_out = ptr<uint64_t>(state_out);
+    return c;
+  }
+};
 
 Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid, double alpha,
                   double lambda, double min_child_weight, const c10::optional<Tensor>& mono,
@@ -176,12 +216,9 @@ Tensor gbdt_split(const Tensor& hist, const Tensor& totals, const Tensor& valid,
   TORCH_CHECK(totals.numel() == 2 * (int64_t)S, "totals must be [S, 2]");
   TORCH_CHECK(valid.numel() == (int64_t)F * nbin, "valid must be [F, nbin]");
   auto out = torch::empty({S, 6}, hist.options());
-  check_mono(mono, bounds, hist, S, F);
-  check_inter(fmask, state, hist, S, F);
   TORCH_CHECK(split_search(hist, ptr<double>(totals), ptr<uint8_t>(valid), S, alpha, lambda,
-                           min_child_weight, out, cur_stream(hist), optptr<int8_t>(mono),
-                           optptr<double>(bounds), optptr<uint64_t>(fmask),
-                           optptr<uint64_t>(state)),
+                           min_child_weight, out, cur_stream(hist),
+                           split_cons(mono, bounds, fmask, state, hist, S, F, "gbdt_split")),
               "gbdt_split: nbin > 1024 or empty input");
   return out;
 }
@@ -805,12 +842,10 @@ Tensor gbdt_split_csr(const Tensor& hist, const Tensor& totals, const Tensor& cu
   const int F = (int)cut_off.numel() - 1;
   auto out = torch::empty({S, 6}, hist.options());
   auto cand = torch::empty({std::max<int64_t>((int64_t)S * F * 5, 1)}, hist.options());
-  check_mono(mono, bounds, hist, S, F);
-  check_inter(fmask, state, hist, S, F);
   wh::gbdt_split_csr(ptr<double>(hist), hist.size(1), ptr<double>(totals), ptr<int32_t>(cut_off),
                      optptr<uint8_t>(fvalid), S, F, alpha, lambda, mcw, ptr<double>(cand),
-                     ptr<double>(out), cur_stream(hist), optptr<int8_t>(mono),
-                     optptr<double>(bounds), optptr<uint64_t>(fmask), optptr<uint64_t>(state));
+                     ptr<double>(out), cur_stream(hist),
+                     split_cons(mono, bounds, fmask, state, hist, S, F, "gbdt_split_csr"));
   return out;
 }
 
@@ -1511,11 +1546,6 @@ Tensor gbdt_rank_eval(const Tensor& margin, const Tensor& label, const Tensor& g
 // down as one pinned upload per level. (The Python level loop it replaces
 // left the GPU idle ~60% of each tree on per-node Python work and two syncs
 // per level.)
-static double l1_threshold(double g, double alpha) {
-  if (alpha <= 0) return g;
-  return g > alpha ? g - alpha : (g < -alpha ? g + alpha : 0.0);
-}
-
 // What the two growers share: the checked inputs, the row and feature-group
 // counts, the rows per histogram task and the dtype options of B's device.
 struct GrowCtx : HistCtx {
@@ -1579,48 +1609,37 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
   const bool reduce = !allreduce.is_none();
   // monotone_constraints: the signs on the device (the split search) and on
   // the host (the children's intervals), and every node's weight interval
-  const bool mono_on = present(mono);
+  const GrowCons cons(mono, fmask, max_delta_step, B, F, "gbdt_grow");
+  const bool mono_on = cons.mono_on, inter_on = cons.inter_on;
   std::vector<int8_t> mono_h;
   if (mono_on) {
-    CHECK_IN(*mono, torch::kInt8);
-    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(), "mono must be [F] on B's device");
     auto mh = mono->cpu();
     mono_h.assign(mh.data_ptr<int8_t>(), mh.data_ptr<int8_t>() + F);
   }
   // interaction_constraints: the features' group bit sets on the device (the
   // split search) and on the host (the children's states), and every node's
-  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
-  const bool inter_on = d_fmask != nullptr;
   std::vector<uint64_t> fmask_h;
   if (inter_on) {
     auto fh = fmask->cpu();
     const auto* q = reinterpret_cast<const uint64_t*>(fh.data_ptr<int64_t>());
     fmask_h.assign(q, q + F);
   }
-  const double inf = std::numeric_limits<double>::infinity();
   // host tree
   TreeLists t;
   std::vector<std::array<double, 2>> tot;
   std::vector<wh::GbdtBounds> bnd;
   std::vector<uint64_t> state;
+  // (max_delta_step: the root's interval; the children's are cut inside it)
   auto add = [&](int par) {
-    return tot.push_back({0, 0}), bnd.push_back({-inf, inf}), state.push_back(wh::kGbdtInterRoot),
-           t.add(par);
+    return tot.push_back({0, 0}), bnd.push_back({-cons.top, cons.top}),
+           state.push_back(wh::kGbdtInterRoot), t.add(par);
   };
-  auto weight0 = [&](double G_, double H_) {
-    return H_ < mcw ? 0.0 : -l1_threshold(G_, alpha) / (H_ + lambda);
-  };
-  // a node's weight: clamped to its interval ({-inf, inf} without constraints)
-  auto weight = [&](int nd) {
-    const double w = weight0(tot[nd][0], tot[nd][1]);
-    return mono_on ? wh::gbdt_clamp_weight(w, bnd[nd]) : w;
+  // a node's weight inside an interval ((-inf, inf) without constraints)
+  auto weight = [&](int nd, const wh::GbdtBounds& b) {
+    return wh::gbdt_weight(tot[nd][0], tot[nd][1], alpha, lambda, mcw, b);
   };
   const int root = add(-1);
   tot[root] = {root_tot[0], root_tot[1]};
-  // max_delta_step: the root's interval (the children's are cut inside it)
-  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
-              "gbdt_grow: max_delta_step >= 0, and it needs mono (all zero for no signs)");
-  if (max_delta_step > 0) bnd[root] = {-max_delta_step, max_delta_step};
   std::map<int, std::pair<int, int>> seg;  // live frontier segments (node -> [b, e))
   seg[root] = {0, (int)n};
   py::list segs;  // finished leaves: (node, b, e)
@@ -1691,17 +1710,16 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       for (int k = 0; k < S; ++k) th[2 * k] = tot[frontier[k]][0], th[2 * k + 1] = tot[frontier[k]][1];
       if (mono_on)
         for (int k = 0; k < S; ++k)
-          th[w_bnd + 2 * k] = bnd[frontier[k]][0], th[w_bnd + 2 * k + 1] = bnd[frontier[k]][1];
+          th[w_bnd + 2 * k] = bnd[frontier[k]].lo, th[w_bnd + 2 * k + 1] = bnd[frontier[k]].hi;
       if (inter_on)
         for (int k = 0; k < S; ++k) std::memcpy(th + w_state + k, &state[frontier[k]], 8);
       auto T = up.tensor().narrow(0, 0, 8 * (int64_t)nw).to(B.device(), true).view(torch::kFloat64);
       up.mark(s);
       split_out = torch::empty({S, 6}, f64);
       TORCH_CHECK(split_search(H_front, ptr<double>(T), ptr<uint8_t>(valid), S, alpha, lambda, mcw,
-                               split_out, s, optptr<int8_t>(mono),
-                               mono_on ? ptr<double>(T) + w_bnd : nullptr, d_fmask,
-                               inter_on ? reinterpret_cast<const uint64_t*>(ptr<double>(T) + w_state)
-                                        : nullptr),
+                               split_out, s,
+                               cons.at(ptr<double>(T) + w_bnd,
+                                       reinterpret_cast<const uint64_t*>(ptr<double>(T) + w_state))),
                   "gbdt_split failed");
     }
     // the level's one synchronisation: split results + previous partition counts
@@ -1716,7 +1734,7 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
     resolve_pending(nl_h);
     for (int nd : frontier) {
       t.cover[nd] = tot[nd][1];
-      t.bw[nd] = weight(nd);
+      t.bw[nd] = weight(nd, bnd[nd]);
       t.leaf[nd] = eta * t.bw[nd];
     }
     if (last) break;
@@ -1733,10 +1751,8 @@ py::tuple gbdt_grow(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, cons
       tot[r] = {tot[nd][0] - o[4], tot[nd][1] - o[5]};
       if (mono_on) {
         const wh::GbdtBounds pb = bnd[nd];  // (bnd grew: no reference into it)
-        const auto cb = wh::gbdt_child_bounds(
-            mono_h[f], pb, wh::gbdt_clamp_weight(weight0(tot[l][0], tot[l][1]), pb),
-            wh::gbdt_clamp_weight(weight0(tot[r][0], tot[r][1]), pb));
-        bnd[l] = cb[0], bnd[r] = cb[1];
+        const auto cb = wh::gbdt_child_bounds(mono_h[f], pb, weight(l, pb), weight(r, pb));
+        bnd[l] = cb.left, bnd[r] = cb.right;
       }
       if (inter_on) state[l] = state[r] = wh::gbdt_child_state(state[nd], fmask_h[f]);
       split_k.push_back(k);
@@ -1877,9 +1893,25 @@ py::tuple gbdt_tree_from_nodes(const Tensor& hn, const std::vector<float>& cut_v
   return t.pack(cut_vals, cut_off, segs);
 }
 
-// margin += the leaf value each row reaches in a device grower's heap node
-// table (device float64 [NN, REC]): the table becomes the walk's compact
-// arrays on the device (one small kernel), then the usual row walk
+// margin += the leaf value each row reaches in a device grower's node table
+// (device float64 [NN, REC]): the table becomes the walk's compact arrays on
+// the device (one small kernel, to_arrays: wh::gbdt_heap_tree for the level
+// loop's heap table, wh::gbdt_leaf_tree for the leaf loop's), then the usual
+// row walk
+void walk_nodes(decltype(&wh::gbdt_heap_tree) to_arrays, const Tensor& B, const Tensor& nodes,
+                const Tensor& margin, bool lds) {
+  const int64_t NN = nodes.size(0);
+  auto buf = torch::empty({6 * NN}, B.options().dtype(torch::kInt32));
+  int32_t* b = ptr<int32_t>(buf);
+  int32_t *feat = b, *bin = b + NN, *left = b + 2 * NN, *right = b + 3 * NN;
+  float* leaf = reinterpret_cast<float*>(b + 4 * NN);
+  uint8_t* defl = reinterpret_cast<uint8_t*>(b + 5 * NN);
+  auto s = cur_stream(B);
+  to_arrays(ptr<double>(nodes), (int)NN, feat, bin, defl, left, right, leaf, s);
+  wh::gbdt_leaf_walk(ptr<uint8_t>(B), B.size(0), (int)B.size(1), (int)NN, feat, bin, defl, left,
+                     right, leaf, ptr<float>(margin), s, lds);
+}
+
 void gbdt_walk_heap(const Tensor& B, const Tensor& nodes, const Tensor& margin, bool lds) {
   CHECK_IN(B, torch::kUInt8);
   CHECK_IN(nodes, torch::kFloat64);
@@ -1890,16 +1922,7 @@ void gbdt_walk_heap(const Tensor& B, const Tensor& nodes, const Tensor& margin, 
               "gbdt_walk_heap: a heap node table");
   TORCH_CHECK(B.dim() == 2 && margin.numel() == B.size(0), "gbdt_walk_heap: B must be [n, f]");
   c10::DeviceGuard g(B.device());
-  const int64_t NN = nodes.size(0);
-  auto buf = torch::empty({6 * NN}, B.options().dtype(torch::kInt32));
-  int32_t* b = ptr<int32_t>(buf);
-  int32_t *feat = b, *bin = b + NN, *left = b + 2 * NN, *right = b + 3 * NN;
-  float* leaf = reinterpret_cast<float*>(b + 4 * NN);
-  uint8_t* defl = reinterpret_cast<uint8_t*>(b + 5 * NN);
-  auto s = cur_stream(B);
-  wh::gbdt_heap_tree(ptr<double>(nodes), (int)NN, feat, bin, defl, left, right, leaf, s);
-  wh::gbdt_leaf_walk(ptr<uint8_t>(B), B.size(0), (int)B.size(1), (int)NN, feat, bin, defl, left,
-                     right, leaf, ptr<float>(margin), s, lds);
+  walk_nodes(wh::gbdt_heap_tree, B, nodes, margin, lds);
 }
 
 py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, const Tensor& gpair,
@@ -1931,27 +1954,17 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
   // monotone_constraints: mono [F] int8 (all features: the split search reads
   // this rank's slice, the apply kernel the picked, global feature) and the
   // slots' weight intervals, ping-ponged level by level like the totals
-  const bool mono_on = present(mono);
-  if (mono_on) {
-    CHECK_IN(*mono, torch::kInt8);
-    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(),
-                "gbdt_grow_dev: mono must be [F] on B's device");
-  }
-  const int8_t* d_mono = optptr<int8_t>(mono);
+  const GrowCons cons(mono, fmask, max_delta_step, B, F, "gbdt_grow_dev");
+  const bool mono_on = cons.mono_on, inter_on = cons.inter_on;
   Tensor bounds_cur;
-  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
-              "gbdt_grow_dev: max_delta_step >= 0, and it needs mono (all zero for no signs)");
   if (mono_on) {
     // the root's interval: max_delta_step on either side of 0, else unbounded
-    const double hi = max_delta_step > 0 ? max_delta_step : std::numeric_limits<double>::infinity();
     bounds_cur = torch::empty({1, 2}, f64);
-    bounds_cur.select(1, 0).fill_(-hi);
-    bounds_cur.select(1, 1).fill_(hi);
+    bounds_cur.select(1, 0).fill_(-cons.top);
+    bounds_cur.select(1, 1).fill_(cons.top);
   }
   // interaction_constraints: fmask [F] int64 (all features, as mono) and the
   // slots' group sets, ping-ponged like the weight intervals
-  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
-  const bool inter_on = d_fmask != nullptr;
   const auto i64 = f64.dtype(torch::kInt64);
   Tensor state_cur;
   if (inter_on) state_cur = torch::full({1}, (int64_t)wh::kGbdtInterRoot, i64);
@@ -2025,10 +2038,7 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
       so = torch::empty({S, 6}, f64);
       if (Fl > 0) {
         TORCH_CHECK(split_search(H_front, ptr<double>(tot_cur), vp + (int64_t)f_lo * nbin, S, alpha,
-                                 lambda, mcw, so, s, mono_on ? d_mono + f_lo : nullptr,
-                                 mono_on ? ptr<double>(bounds_cur) : nullptr,
-                                 inter_on ? d_fmask + f_lo : nullptr,
-                                 inter_on ? ptr<uint64_t>(state_cur) : nullptr),
+                                 lambda, mcw, so, s, cons.at(bounds_cur, state_cur, 0, f_lo)),
                     "gbdt_split failed");
       } else {  // (more ranks than features: this rank owns none)
         so.zero_();
@@ -2052,11 +2062,8 @@ py::tuple gbdt_grow_dev(const Tensor& B, const Tensor& Bc, const Tensor& ridx0, 
                        ptr<int32_t>(seg_cur), ptr<uint8_t>(alive_cur), eta, alpha, lambda, mcw,
                        rt_eps, ptr<double>(nodes), pfeat, pfeat + S, pdefl, pfeat + 2 * S,
                        pfeat + 3 * S, pdefl + S, pdefl + 2 * S,
-                       last ? nullptr : ptr<double>(tot_next), nullptr, s, d_mono,
-                       mono_on ? ptr<double>(bounds_cur) : nullptr,
-                       bounds_next.defined() ? ptr<double>(bounds_next) : nullptr, d_fmask,
-                       inter_on ? ptr<uint64_t>(state_cur) : nullptr,
-                       state_next.defined() ? ptr<uint64_t>(state_next) : nullptr);
+                       last ? nullptr : ptr<double>(tot_next), nullptr, s,
+                       cons.step(bounds_cur, state_cur, bounds_next, state_next));
     if (last) break;
     // walk: the caller adds the leaf values by walking the tree over each
     // row's bins (models/gbdt.py _finish), so the level whose children are
@@ -2181,17 +2188,7 @@ py::tuple gbdt_grow_leaf(const Tensor& B, const Tensor& Bc, const Tensor& ridx0,
   const int F = cx.F, G = cx.G, chunk = cx.chunk;
   const auto &f64 = cx.f64, &i32 = cx.i32;
   TORCH_CHECK(n > 0 && B.size(0) == n && G >= 1, "gbdt_grow_leaf: B must be [n, f], n > 0");
-  const bool mono_on = present(mono);
-  if (mono_on) {
-    CHECK_IN(*mono, torch::kInt8);
-    TORCH_CHECK(mono->numel() == F && mono->device() == B.device(),
-                "gbdt_grow_leaf: mono must be [F] on B's device");
-  }
-  TORCH_CHECK(max_delta_step >= 0 && (max_delta_step == 0 || mono_on),
-              "gbdt_grow_leaf: max_delta_step >= 0, and it needs mono (all zero for no signs)");
-  const int8_t* d_mono = optptr<int8_t>(mono);
-  const uint64_t* d_fmask = grower_fmask(fmask, B, F);
-  const bool inter_on = d_fmask != nullptr;
+  const GrowCons cons(mono, fmask, max_delta_step, B, F, "gbdt_grow_leaf");
   const int L = (int)max_leaves, NN = (int)wh::gbdt_leaf_pool_slots(L), REC = wh::gbdt_node_rec();
   const int WS = wh::gbdt_leaf_ws();
   const int64_t per = (int64_t)F * nbin * 2;
@@ -2226,22 +2223,18 @@ py::tuple gbdt_grow_leaf(const Tensor& B, const Tensor& Bc, const Tensor& ridx0,
   auto tot = torch::zeros({NN, 2}, f64);
   auto meta = torch::zeros({NN, 4}, i32);
   auto ws = torch::zeros({WS}, i32);
-  Tensor bnd = mono_on ? torch::zeros({NN, 2}, f64) : Tensor();
-  Tensor state = inter_on ? torch::zeros({NN}, f64.dtype(torch::kInt64)) : Tensor();
+  Tensor bnd = cons.mono_on ? torch::zeros({NN, 2}, f64) : Tensor();
+  Tensor state = cons.inter_on ? torch::zeros({NN}, f64.dtype(torch::kInt64)) : Tensor();
   auto pool = torch::empty({NN, F, nbin, 2}, f64);  // a node's histogram: slot = node id
-  double* d_bnd = mono_on ? ptr<double>(bnd) : nullptr;
-  uint64_t* d_state = inter_on ? ptr<uint64_t>(state) : nullptr;
-  const double top = max_delta_step > 0 ? max_delta_step : std::numeric_limits<double>::infinity();
-  wh::gbdt_leaf_root(ptr<double>(root_tot), (int)n, top, (uint64_t)wh::kGbdtInterRoot, eta, alpha,
-                     lambda, mcw, ptr<double>(tot), d_bnd, d_state, ptr<int32_t>(meta),
-                     ptr<double>(nodes), s);
+  const wh::GbdtCons tables = cons.step(bnd, state, bnd, state);  // in place
+  wh::gbdt_leaf_root(ptr<double>(root_tot), (int)n, cons.top, (uint64_t)wh::kGbdtInterRoot, eta,
+                     alpha, lambda, mcw, ptr<double>(tot), ptr<int32_t>(meta), ptr<double>(nodes), s,
+                     tables);
   const uint8_t* vp = reinterpret_cast<const uint8_t*>(valid.data_ptr());
   Tensor ridx = ridx0.clone();  // partitioned in place, segment by segment
   auto search = [&](int node0, int S) {
     TORCH_CHECK(split_search(pool.narrow(0, node0, S), ptr<double>(tot) + 2 * node0, vp, S, alpha,
-                             lambda, mcw, so.narrow(0, node0, S), s, d_mono,
-                             mono_on ? d_bnd + 2 * node0 : nullptr, d_fmask,
-                             inter_on ? d_state + node0 : nullptr),
+                             lambda, mcw, so.narrow(0, node0, S), s, cons.at(bnd, state, node0)),
                 "gbdt_split failed");
   };
   if (L > 1) {
@@ -2261,7 +2254,7 @@ py::tuple gbdt_grow_leaf(const Tensor& B, const Tensor& Bc, const Tensor& ridx0,
     const bool last = k + 2 == L;  // the tree is full after this step
     wh::gbdt_leaf_pick(k, (int)depth_cap, last, ptr<double>(so), ptr<double>(tot),
                        ptr<int32_t>(meta), eta, alpha, lambda, mcw, rt_eps, ptr<double>(nodes),
-                       d_ws, s, d_mono, d_bnd, d_fmask, d_state);
+                       d_ws, s, tables);
     wh::gbdt_leaf_partition(ptr<uint8_t>(B), ptr<uint8_t>(Bc), B.size(0), F, ptr<int32_t>(ridx), n,
                             d_ws, ptr<int32_t>(scratch), s);
     wh::gbdt_leaf_children(d_ws, ptr<int32_t>(meta), ptr<double>(nodes), d_fg, G, chunk,
@@ -2276,14 +2269,7 @@ py::tuple gbdt_grow_leaf(const Tensor& B, const Tensor& Bc, const Tensor& ridx0,
     const Tensor& margin = *walk_margin;
     CHECK_IN(margin, torch::kFloat32);
     TORCH_CHECK(margin.numel() == n, "gbdt_grow_leaf: walk_margin must be [n]");
-    auto buf = torch::empty({6 * (int64_t)NN}, i32);
-    int32_t* b = ptr<int32_t>(buf);
-    int32_t *feat = b, *bin = b + NN, *left = b + 2 * NN, *right = b + 3 * NN;
-    float* leaf = reinterpret_cast<float*>(b + 4 * NN);
-    uint8_t* defl = reinterpret_cast<uint8_t*>(b + 5 * NN);
-    wh::gbdt_leaf_tree(ptr<double>(nodes), NN, feat, bin, defl, left, right, leaf, s);
-    wh::gbdt_leaf_walk(ptr<uint8_t>(B), n, F, NN, feat, bin, defl, left, right, leaf,
-                       ptr<float>(margin), s, lds);
+    walk_nodes(wh::gbdt_leaf_tree, B, nodes, margin, lds);
   }
   return py::make_tuple(gbdt_leaf_tree_from_nodes(nodes.cpu(), cut_vals, cut_off), ridx);
 }

@@ -10,7 +10,9 @@
 //   gbdt_predict   one lane per row walks a tree on raw values (NaN = missing)
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
+#include "host/gbdt_node_rule.h"
 #include "host/gbdt_objective.h"
 #include "wh_common.h"
 #include "wh_kernels.h"
@@ -1435,31 +1437,39 @@ void gbdt_predict(const float* X, int64_t n, int f, const int32_t* feat, const f
 
 }  // namespace wh
 
-// The L1 threshold T(G) of alpha and the unclamped node weight -T(G) / (H +
-// lambda) (0 below min_child_weight): said once for the level loop's
-// bookkeeping and the bounded split search, which must evaluate the same
-// operations.
+// ---- constrained instantiations ---------------------------------------
+// The split searches, the level loop's apply and the leaf loop's pick are
+// templates over (MONO, INTER): monotone_constraints and
+// interaction_constraints (wh_kernels.h GbdtCons; the rule itself is
+// host/gbdt_node_rule.h). Their kernels end in a parameter pack that holds,
+// per flag that is on, one struct of exactly the pointers that flag's code
+// reads, so the unconstrained launch keeps its argument list (a kernel that
+// carried null pointers there measured 0.2-0.8 % behind,
+// docs/performance.md "GBDT with monotone_constraints").
 namespace {
 
-__device__ __forceinline__ double gbdt_l1(double G, double alpha) {
-  return alpha <= 0 ? G : (G > alpha ? G - alpha : (G < -alpha ? G + alpha : 0.0));
+// the pack's struct of type T, or nulls when its flag is off
+template <class T>
+__device__ __forceinline__ T cons_get() {
+  return T{};
+}
+template <class T, class A, class... R>
+__device__ __forceinline__ T cons_get(const A& a, const R&... r) {
+  if constexpr (std::is_same_v<T, A>) return a;
+  else return cons_get<T>(r...);
 }
 
-__device__ __forceinline__ double gbdt_weight0(double G, double H, double alpha, double lambda,
-                                               double mcw) {
-  return H >= mcw ? -gbdt_l1(G, alpha) / (H + lambda) : 0.0;
-}
-
-// interaction_constraints: a slot may split on a feature iff their group bit
-// sets (host/gbdt_level_plan.h) share a bit.
-__device__ __forceinline__ bool gbdt_admits(uint64_t state, uint64_t fmask) {
-  return (state & fmask) != 0;
-}
-
-// (the children of a split: bit 63, the mark of a feature in no group, is
-// dropped, so nothing is admitted below a split on such a feature)
-__device__ __forceinline__ uint64_t gbdt_child_state(uint64_t state, uint64_t fmask) {
-  return state & fmask & ~(1ull << 63);
+// The one dispatch: the run-time pair (mono given, fmask given) becomes the
+// two compile-time flags, and fn(MONO, INTER, cons...) gets them as
+// std::bool_constant values with the pack of that instantiation.
+template <class M, class I, class Fn>
+void cons_dispatch(const wh::GbdtCons& c, const M& m, const I& i, Fn&& fn) {
+  using T = std::true_type;
+  using F = std::false_type;
+  if (c.mono && c.fmask) fn(T{}, T{}, m, i);
+  else if (c.fmask) fn(F{}, T{}, i);
+  else if (c.mono) fn(T{}, F{}, m);
+  else fn(F{}, F{});
 }
 
 }  // namespace
@@ -1531,11 +1541,10 @@ __device__ __forceinline__ void gd_apply(
     const double* o = so + (int64_t)sl * 6;
     const bool sp = al && !last && o[0] > rt_eps;
     double bw = gbdt_weight0(G, H, alpha, lambda, mcw);
-    double lo = 0.0, hi = 0.0;
+    GbdtBounds iv{0.0, 0.0};
     if (MONO) {
-      lo = bnd[2 * sl];
-      hi = bnd[2 * sl + 1];
-      bw = bw < lo ? lo : (bw > hi ? hi : bw);
+      iv = {bnd[2 * sl], bnd[2 * sl + 1]};
+      bw = gbdt_clamp_weight(bw, iv);
     }
     nd[0] = al ? 1.0 : 0.0;
     nd[1] = sp ? o[1] : -1.0;
@@ -1563,21 +1572,13 @@ __device__ __forceinline__ void gd_apply(
       tot_next[4 * sl + 3] = HR;
     }
     if (MONO && bnd_next) {
-      double llo = lo, lhi = hi, rlo = lo, rhi = hi;
-      const int c = sp ? mono[(int32_t)o[1]] : 0;
-      if (c != 0) {
-        double wl = gbdt_weight0(GL, HL, alpha, lambda, mcw);
-        double wr = gbdt_weight0(GR, HR, alpha, lambda, mcw);
-        wl = wl < lo ? lo : (wl > hi ? hi : wl);
-        wr = wr < lo ? lo : (wr > hi ? hi : wr);
-        const double mid = (wl + wr) / 2;
-        if (c > 0) lhi = mid, rlo = mid;
-        else llo = mid, rhi = mid;
-      }
-      bnd_next[4 * sl] = llo;
-      bnd_next[4 * sl + 1] = lhi;
-      bnd_next[4 * sl + 2] = rlo;
-      bnd_next[4 * sl + 3] = rhi;
+      const GbdtChildBounds cb = gbdt_child_bounds(
+          sp ? mono[(int32_t)o[1]] : 0, iv, gbdt_weight(GL, HL, alpha, lambda, mcw, iv),
+          gbdt_weight(GR, HR, alpha, lambda, mcw, iv));
+      bnd_next[4 * sl] = cb.left.lo;
+      bnd_next[4 * sl + 1] = cb.left.hi;
+      bnd_next[4 * sl + 2] = cb.right.lo;
+      bnd_next[4 * sl + 3] = cb.right.hi;
     }
     if (INTER && state_next) {
       const uint64_t c = sp ? gbdt_child_state(state[sl], fmask[(int32_t)o[1]]) : 0;
@@ -1587,60 +1588,32 @@ __device__ __forceinline__ void gd_apply(
   }
 }
 
-// (two entry points, so that the unconstrained launch keeps its argument list)
+struct ApplyMono {
+  const int8_t* mono;
+  const double* bnd;
+  double* bnd_next;
+};
+struct ApplyInter {
+  const uint64_t* fmask;
+  const uint64_t* state;
+  uint64_t* state_next;
+};
+
+template <bool MONO, bool INTER, class... C>
 __global__ __launch_bounds__(256) void k_gd_apply(
     int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
     const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
     double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
     int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
     int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
-    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft) {
-  gd_apply<false, false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
-                         pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void k_gd_apply_mono(
-    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
-    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
-    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
-    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
-    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
     uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
-    const int8_t* __restrict__ mono, const double* __restrict__ bnd,
-    double* __restrict__ bnd_next) {
-  gd_apply<true, false>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
-                        pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd,
-                        bnd_next, nullptr, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void k_gd_apply_inter(
-    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
-    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
-    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
-    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
-    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
-    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
-    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state,
-    uint64_t* __restrict__ state_next) {
-  gd_apply<false, true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
-                        pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, nullptr,
-                        nullptr, nullptr, fmask, state, state_next);
-}
-
-__global__ __launch_bounds__(256) void k_gd_apply_mono_inter(
-    int S, int node0, int last, const double* __restrict__ so, const double* __restrict__ tot,
-    const int32_t* __restrict__ seg, const uint8_t* __restrict__ alive, double eta, double alpha,
-    double lambda, double mcw, double rt_eps, double* __restrict__ nodes,
-    int32_t* __restrict__ pfeat, int32_t* __restrict__ pbin, uint8_t* __restrict__ pdefl,
-    int32_t* __restrict__ lcur, int32_t* __restrict__ rcur, uint8_t* __restrict__ split,
-    uint8_t* __restrict__ build_left, double* __restrict__ tot_next, int32_t* __restrict__ nleft,
-    const int8_t* __restrict__ mono, const double* __restrict__ bnd,
-    double* __restrict__ bnd_next, const uint64_t* __restrict__ fmask,
-    const uint64_t* __restrict__ state, uint64_t* __restrict__ state_next) {
-  gd_apply<true, true>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
-                       pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, mono, bnd,
-                       bnd_next, fmask, state, state_next);
+    C... cons) {
+  static_assert(sizeof...(C) == int(MONO) + int(INTER), "one struct per flag that is on");
+  const ApplyMono m = cons_get<ApplyMono>(cons...);
+  const ApplyInter i = cons_get<ApplyInter>(cons...);
+  gd_apply<MONO, INTER>(S, node0, last, so, tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes,
+                        pfeat, pbin, pdefl, lcur, rcur, split, build_left, tot_next, nleft, m.mono,
+                        m.bnd, m.bnd_next, i.fmask, i.state, i.state_next);
 }
 
 // One block (S <= 1024 slots): the next level's segments / alive flags, the
@@ -1750,15 +1723,11 @@ __global__ __launch_bounds__(1024) void k_gd_children(
 constexpr int kLeafWs = 20;
 constexpr int kLeafThreads = 256;
 
-// The weight of a node with totals (G, H) inside its interval, and the
-// intervals of a split's children: gd_apply's arithmetic, operation for
-// operation, so both loops give a node the same bits.
+// The weight of a node with totals (G, H), inside its interval under MONO
 template <bool MONO>
 __device__ __forceinline__ double leaf_weight(double G, double H, double alpha, double lambda,
-                                              double mcw, double lo, double hi) {
-  double bw = gbdt_weight0(G, H, alpha, lambda, mcw);
-  if (MONO) bw = bw < lo ? lo : (bw > hi ? hi : bw);
-  return bw;
+                                              double mcw, const GbdtBounds& iv) {
+  return MONO ? gbdt_weight(G, H, alpha, lambda, mcw, iv) : gbdt_weight0(G, H, alpha, lambda, mcw);
 }
 
 __device__ __forceinline__ void leaf_record(double* q, double left, double cover, double bw,
@@ -1788,7 +1757,7 @@ __global__ void k_leaf_root(const double* __restrict__ root_tot, int n, double t
   if (MONO) bnd[0] = -top, bnd[1] = top;
   if (INTER) state[0] = root_state;
   meta[0] = 1, meta[1] = 0, meta[2] = 0, meta[3] = n;
-  leaf_record(nodes, -1.0, H, leaf_weight<MONO>(G, H, alpha, lambda, mcw, -top, top), eta, 0.0,
+  leaf_record(nodes, -1.0, H, leaf_weight<MONO>(G, H, alpha, lambda, mcw, {-top, top}), eta, 0.0,
               (double)n);
 }
 
@@ -1863,22 +1832,13 @@ __device__ __forceinline__ void leaf_pick(
   q[3] = o[3];
   q[4] = o[0];
   meta[4 * nd] = 0;
-  double lo = 0.0, hi = 0.0, llo = 0.0, lhi = 0.0, rlo = 0.0, rhi = 0.0;
+  GbdtChildBounds cb{{0.0, 0.0}, {0.0, 0.0}};
   if (MONO) {
-    lo = bnd[2 * nd];
-    hi = bnd[2 * nd + 1];
-    llo = lo, lhi = hi, rlo = lo, rhi = hi;
-    const int c = mono[feat];
-    if (c != 0) {
-      double wl = gbdt_weight0(GL, HL, alpha, lambda, mcw);
-      double wr = gbdt_weight0(GR, HR, alpha, lambda, mcw);
-      wl = wl < lo ? lo : (wl > hi ? hi : wl);
-      wr = wr < lo ? lo : (wr > hi ? hi : wr);
-      const double mid = (wl + wr) / 2;
-      if (c > 0) lhi = mid, rlo = mid;
-      else llo = mid, rhi = mid;
-    }
-    bnd[2 * l] = llo, bnd[2 * l + 1] = lhi, bnd[2 * r] = rlo, bnd[2 * r + 1] = rhi;
+    const GbdtBounds iv{bnd[2 * nd], bnd[2 * nd + 1]};
+    cb = gbdt_child_bounds(mono[feat], iv, gbdt_weight(GL, HL, alpha, lambda, mcw, iv),
+                           gbdt_weight(GR, HR, alpha, lambda, mcw, iv));
+    bnd[2 * l] = cb.left.lo, bnd[2 * l + 1] = cb.left.hi;
+    bnd[2 * r] = cb.right.lo, bnd[2 * r + 1] = cb.right.hi;
   }
   if (INTER) state[l] = state[r] = gbdt_child_state(state[nd], fmask[feat]);
   tot[2 * l] = GL, tot[2 * l + 1] = HL, tot[2 * r] = GR, tot[2 * r + 1] = HR;
@@ -1886,8 +1846,8 @@ __device__ __forceinline__ void leaf_pick(
   meta[4 * l] = open, meta[4 * l + 1] = depth;
   meta[4 * r] = open, meta[4 * r + 1] = depth;
   // (the children's rows: k_leaf_children, after the partition)
-  leaf_record(ql, -1.0, HL, leaf_weight<MONO>(GL, HL, alpha, lambda, mcw, llo, lhi), eta, 0.0, 0.0);
-  leaf_record(qr, -1.0, HR, leaf_weight<MONO>(GR, HR, alpha, lambda, mcw, rlo, rhi), eta, 0.0, 0.0);
+  leaf_record(ql, -1.0, HL, leaf_weight<MONO>(GL, HL, alpha, lambda, mcw, cb.left), eta, 0.0, 0.0);
+  leaf_record(qr, -1.0, HR, leaf_weight<MONO>(GR, HR, alpha, lambda, mcw, cb.right), eta, 0.0, 0.0);
   const int bl = HL <= HR ? 1 : 0;  // build the child with the smaller global hessian
   ws[0] = feat;
   ws[1] = (int32_t)o[2];
@@ -1901,39 +1861,26 @@ __device__ __forceinline__ void leaf_pick(
   ws[16] = nd;
 }
 
+// (the tables are read and written in place: one pointer each)
+struct LeafMono {
+  const int8_t* mono;
+  double* bnd;
+};
+struct LeafInter {
+  const uint64_t* fmask;
+  uint64_t* state;
+};
+
+template <bool MONO, bool INTER, class... C>
 __global__ __launch_bounds__(kLeafThreads) void k_leaf_pick(
     int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
     int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
-    double* __restrict__ nodes, int32_t* __restrict__ ws) {
-  leaf_pick<false, false>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
-                          ws, nullptr, nullptr, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_mono(
-    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
-    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
-    double* __restrict__ nodes, int32_t* __restrict__ ws, const int8_t* __restrict__ mono,
-    double* __restrict__ bnd) {
-  leaf_pick<true, false>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
-                         ws, mono, bnd, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_inter(
-    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
-    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
-    double* __restrict__ nodes, int32_t* __restrict__ ws, const uint64_t* __restrict__ fmask,
-    uint64_t* __restrict__ state) {
-  leaf_pick<false, true>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
-                         ws, nullptr, nullptr, fmask, state);
-}
-
-__global__ __launch_bounds__(kLeafThreads) void k_leaf_pick_mono_inter(
-    int k, int depth_cap, int last, const double* __restrict__ so, double* __restrict__ tot,
-    int32_t* __restrict__ meta, double eta, double alpha, double lambda, double mcw, double rt_eps,
-    double* __restrict__ nodes, int32_t* __restrict__ ws, const int8_t* __restrict__ mono,
-    double* __restrict__ bnd, const uint64_t* __restrict__ fmask, uint64_t* __restrict__ state) {
-  leaf_pick<true, true>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
-                        ws, mono, bnd, fmask, state);
+    double* __restrict__ nodes, int32_t* __restrict__ ws, C... cons) {
+  static_assert(sizeof...(C) == int(MONO) + int(INTER), "one struct per flag that is on");
+  const LeafMono m = cons_get<LeafMono>(cons...);
+  const LeafInter i = cons_get<LeafInter>(cons...);
+  leaf_pick<MONO, INTER>(k, depth_cap, last, so, tot, meta, eta, alpha, lambda, mcw, rt_eps, nodes,
+                         ws, m.mono, m.bnd, i.fmask, i.state);
 }
 
 // The partition of ONE segment, read from the device (ws): k_part_cursor's
@@ -2099,32 +2046,23 @@ __global__ __launch_bounds__(256) void k_leaf_tree(const double* __restrict__ no
 int gbdt_leaf_ws() { return kLeafWs; }
 
 void gbdt_leaf_root(const double* root_tot, int n, double top, uint64_t root_state, double eta,
-                    double alpha, double lambda, double mcw, double* tot, double* bnd,
-                    uint64_t* state, int32_t* meta, double* nodes, hipStream_t s) {
-  auto kern = bnd ? (state ? k_leaf_root<true, true> : k_leaf_root<true, false>)
-                  : (state ? k_leaf_root<false, true> : k_leaf_root<false, false>);
-  hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, s, root_tot, n, top, root_state, eta, alpha, lambda,
-                     mcw, tot, bnd, state, meta, nodes);
+                    double alpha, double lambda, double mcw, double* tot, int32_t* meta,
+                    double* nodes, hipStream_t s, const GbdtCons& c) {
+  cons_dispatch(c, 0, 0, [&](auto M, auto I, auto...) {
+    hipLaunchKernelGGL((k_leaf_root<M(), I()>), dim3(1), dim3(64), 0, s, root_tot, n, top,
+                       root_state, eta, alpha, lambda, mcw, tot, c.bnd_out, c.state_out, meta, nodes);
+  });
 }
 
 void gbdt_leaf_pick(int k, int depth_cap, bool last, const double* so, double* tot, int32_t* meta,
                     double eta, double alpha, double lambda, double mcw, double rt_eps,
-                    double* nodes, int32_t* ws, hipStream_t s, const int8_t* mono, double* bnd,
-                    const uint64_t* fmask, uint64_t* state) {
-  const dim3 g(1), b(kLeafThreads);
-  const int la = last ? 1 : 0;
-  if (fmask && mono)
-    hipLaunchKernelGGL(k_leaf_pick_mono_inter, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta,
-                       alpha, lambda, mcw, rt_eps, nodes, ws, mono, bnd, fmask, state);
-  else if (fmask)
-    hipLaunchKernelGGL(k_leaf_pick_inter, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha,
-                       lambda, mcw, rt_eps, nodes, ws, fmask, state);
-  else if (mono)
-    hipLaunchKernelGGL(k_leaf_pick_mono, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha,
-                       lambda, mcw, rt_eps, nodes, ws, mono, bnd);
-  else
-    hipLaunchKernelGGL(k_leaf_pick, g, b, 0, s, k, depth_cap, la, so, tot, meta, eta, alpha, lambda,
-                       mcw, rt_eps, nodes, ws);
+                    double* nodes, int32_t* ws, hipStream_t s, const GbdtCons& c) {
+  cons_dispatch(c, LeafMono{c.mono, c.bnd_out}, LeafInter{c.fmask, c.state_out},
+                [&](auto M, auto I, auto... cs) {
+                  hipLaunchKernelGGL((k_leaf_pick<M(), I(), decltype(cs)...>), dim3(1),
+                                     dim3(kLeafThreads), 0, s, k, depth_cap, last ? 1 : 0, so, tot,
+                                     meta, eta, alpha, lambda, mcw, rt_eps, nodes, ws, cs...);
+                });
 }
 
 void gbdt_leaf_partition(const uint8_t* B, const uint8_t* Bc, int64_t nrows, int f, int32_t* ridx,
@@ -2162,25 +2100,14 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     double lambda, double mcw, double rt_eps, double* nodes, int32_t* pfeat,
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
                     uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
-                    const int8_t* mono, const double* bnd, double* bnd_next,
-                    const uint64_t* fmask, const uint64_t* state, uint64_t* state_next) {
-  if (fmask && mono)
-    hipLaunchKernelGGL(k_gd_apply_mono_inter, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so,
-                       tot, seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl,
-                       lcur, rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next, fmask,
-                       state, state_next);
-  else if (fmask)
-    hipLaunchKernelGGL(k_gd_apply_inter, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot,
-                       seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur,
-                       rcur, split, build_left, tot_next, nleft, fmask, state, state_next);
-  else if (mono)
-    hipLaunchKernelGGL(k_gd_apply_mono, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot,
-                       seg, alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur,
-                       rcur, split, build_left, tot_next, nleft, mono, bnd, bnd_next);
-  else
-    hipLaunchKernelGGL(k_gd_apply, dim3(1), dim3(256), 0, s, S, node0, last ? 1 : 0, so, tot, seg,
-                       alive, eta, alpha, lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur, rcur,
-                       split, build_left, tot_next, nleft);
+                    const GbdtCons& c) {
+  cons_dispatch(c, ApplyMono{c.mono, c.bnd, c.bnd_out}, ApplyInter{c.fmask, c.state, c.state_out},
+                [&](auto M, auto I, auto... cs) {
+                  hipLaunchKernelGGL((k_gd_apply<M(), I(), decltype(cs)...>), dim3(1), dim3(256), 0,
+                                     s, S, node0, last ? 1 : 0, so, tot, seg, alive, eta, alpha,
+                                     lambda, mcw, rt_eps, nodes, pfeat, pbin, pdefl, lcur, rcur,
+                                     split, build_left, tot_next, nleft, cs...);
+                });
 }
 
 bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const uint8_t* build_left,
@@ -2224,21 +2151,14 @@ __device__ __forceinline__ double split_gain(double G, double H, const SplitPara
 // a clamped one scores -(2 T(G) w + (H + lambda) w w). The host grower and
 // the torch reference evaluate exactly these operations, so no contraction
 // into fused multiply-adds here: the growers must pick equal split indexes.
-__device__ __forceinline__ double split_weight(double G, double H, const SplitParam& p, double lo,
-                                               double hi, double* w0_out = nullptr) {
-  const double w0 = gbdt_weight0(G, H, p.alpha, p.lambda, p.mcw);
-  if (w0_out) *w0_out = w0;
-  return w0 < lo ? lo : (w0 > hi ? hi : w0);
-}
-
 __device__ __forceinline__ double split_gain_bounded(double G, double H, const SplitParam& p,
                                                      double lo, double hi, double* w_out) {
 #pragma clang fp contract(off)
-  double w0;
-  const double w = split_weight(G, H, p, lo, hi, &w0);
+  const double w0 = wh::gbdt_weight0(G, H, p.alpha, p.lambda, p.mcw);
+  const double w = wh::gbdt_clamp_weight(w0, {lo, hi});
   *w_out = w;
   if (w == w0) return split_gain(G, H, p);
-  const double g = gbdt_l1(G, p.alpha);
+  const double g = wh::gbdt_l1(G, p.alpha);
   const double d = H + p.lambda;
   const double a = 2.0 * g * w;
   const double b = d * w * w;
@@ -2281,7 +2201,7 @@ __device__ __forceinline__ void split_feat(
     const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
   const int s = blockIdx.x / F, f = blockIdx.x % F;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  if (INTER && !gbdt_admits(state[s], fmask[f])) {
+  if (INTER && !wh::gbdt_admits(state[s], fmask[f])) {
     if (t == 0) {
       double* c = cand + ((int64_t)s * F + f) * 4;
       c[0] = -INFINITY;
@@ -2403,34 +2323,26 @@ __device__ __forceinline__ void split_feat(
   }
 }
 
-// (two entry points, so that the unconstrained launch keeps its argument list)
+// (what both split searches read under each flag)
+struct SplitMono {
+  const int8_t* mono;
+  const double* bounds;
+};
+struct SplitInter {
+  const uint64_t* fmask;
+  const uint64_t* state;
+};
+
+template <bool MONO, bool INTER, class... C>
 __global__ __launch_bounds__(kSplitThreads) void k_split_feat(
     const double* __restrict__ hist, const double* __restrict__ totals,
-    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand) {
-  split_feat<false, false>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr, nullptr,
-                           nullptr);
-}
-
-__global__ __launch_bounds__(kSplitThreads) void k_split_feat_mono(
-    const double* __restrict__ hist, const double* __restrict__ totals,
     const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
-    const int8_t* __restrict__ mono, const double* __restrict__ bounds) {
-  split_feat<true, false>(hist, totals, valid, F, nbin, p, cand, mono, bounds, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(kSplitThreads) void k_split_feat_inter(
-    const double* __restrict__ hist, const double* __restrict__ totals,
-    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
-    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
-  split_feat<false, true>(hist, totals, valid, F, nbin, p, cand, nullptr, nullptr, fmask, state);
-}
-
-__global__ __launch_bounds__(kSplitThreads) void k_split_feat_mono_inter(
-    const double* __restrict__ hist, const double* __restrict__ totals,
-    const uint8_t* __restrict__ valid, int F, int nbin, SplitParam p, double* __restrict__ cand,
-    const int8_t* __restrict__ mono, const double* __restrict__ bounds,
-    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
-  split_feat<true, true>(hist, totals, valid, F, nbin, p, cand, mono, bounds, fmask, state);
+    C... cons) {
+  static_assert(sizeof...(C) == int(MONO) + int(INTER), "one struct per flag that is on");
+  const SplitMono m = cons_get<SplitMono>(cons...);
+  const SplitInter i = cons_get<SplitInter>(cons...);
+  split_feat<MONO, INTER>(hist, totals, valid, F, nbin, p, cand, m.mono, m.bounds, i.fmask,
+                          i.state);
 }
 
 __global__ __launch_bounds__(64) void k_split_node(const double* __restrict__ cand, int F,
@@ -2478,22 +2390,15 @@ namespace wh {
 
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s, const int8_t* mono, const double* bounds, const uint64_t* fmask,
-                const uint64_t* state) {
+                hipStream_t s, const GbdtCons& c) {
   if (nbin > kSplitThreads * kSplitMaxPer || S <= 0 || F <= 0) return false;
   const SplitParam p{alpha, lambda, mcw};
-  if (fmask && mono)
-    hipLaunchKernelGGL(k_split_feat_mono_inter, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s,
-                       hist, totals, valid, F, nbin, p, cand, mono, bounds, fmask, state);
-  else if (fmask)
-    hipLaunchKernelGGL(k_split_feat_inter, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
-                       totals, valid, F, nbin, p, cand, fmask, state);
-  else if (mono)
-    hipLaunchKernelGGL(k_split_feat_mono, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
-                       totals, valid, F, nbin, p, cand, mono, bounds);
-  else
-    hipLaunchKernelGGL(k_split_feat, dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
-                       totals, valid, F, nbin, p, cand);
+  cons_dispatch(c, SplitMono{c.mono, c.bnd}, SplitInter{c.fmask, c.state},
+                [&](auto M, auto I, auto... cs) {
+                  hipLaunchKernelGGL((k_split_feat<M(), I(), decltype(cs)...>),
+                                     dim3((unsigned)(S * F)), dim3(kSplitThreads), 0, s, hist,
+                                     totals, valid, F, nbin, p, cand, cs...);
+                });
   hipLaunchKernelGGL(k_split_node, dim3((unsigned)S), dim3(64), 0, s, cand, F, nbin, out);
   return true;
 }
@@ -2620,43 +2525,17 @@ __device__ __forceinline__ void split_csr_feat(const double* __restrict__ hist, 
   c[0] = best, c[1] = bb, c[2] = bd, c[3] = gl, c[4] = hl;
 }
 
+template <bool MONO, bool INTER, class... C>
 __global__ void k_split_csr_feat(const double* __restrict__ hist, int64_t tb,
                                  const double* __restrict__ totals,
                                  const int32_t* __restrict__ cut_off,
                                  const uint8_t* __restrict__ fvalid, int F, SplitParam p,
-                                 double* __restrict__ cand) {
-  split_csr_feat<false, false>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr,
-                               nullptr, nullptr);
-}
-
-__global__ void k_split_csr_feat_mono(const double* __restrict__ hist, int64_t tb,
-                                      const double* __restrict__ totals,
-                                      const int32_t* __restrict__ cut_off,
-                                      const uint8_t* __restrict__ fvalid, int F, SplitParam p,
-                                      double* __restrict__ cand, const int8_t* __restrict__ mono,
-                                      const double* __restrict__ bounds) {
-  split_csr_feat<true, false>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds, nullptr,
-                              nullptr);
-}
-
-__global__ void k_split_csr_feat_inter(const double* __restrict__ hist, int64_t tb,
-                                       const double* __restrict__ totals,
-                                       const int32_t* __restrict__ cut_off,
-                                       const uint8_t* __restrict__ fvalid, int F, SplitParam p,
-                                       double* __restrict__ cand,
-                                       const uint64_t* __restrict__ fmask,
-                                       const uint64_t* __restrict__ state) {
-  split_csr_feat<false, true>(hist, tb, totals, cut_off, fvalid, F, p, cand, nullptr, nullptr,
-                              fmask, state);
-}
-
-__global__ void k_split_csr_feat_mono_inter(
-    const double* __restrict__ hist, int64_t tb, const double* __restrict__ totals,
-    const int32_t* __restrict__ cut_off, const uint8_t* __restrict__ fvalid, int F, SplitParam p,
-    double* __restrict__ cand, const int8_t* __restrict__ mono, const double* __restrict__ bounds,
-    const uint64_t* __restrict__ fmask, const uint64_t* __restrict__ state) {
-  split_csr_feat<true, true>(hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds, fmask,
-                             state);
+                                 double* __restrict__ cand, C... cons) {
+  static_assert(sizeof...(C) == int(MONO) + int(INTER), "one struct per flag that is on");
+  const SplitMono m = cons_get<SplitMono>(cons...);
+  const SplitInter i = cons_get<SplitInter>(cons...);
+  split_csr_feat<MONO, INTER>(hist, tb, totals, cut_off, fvalid, F, p, cand, m.mono, m.bounds,
+                              i.fmask, i.state);
 }
 
 __global__ __launch_bounds__(256) void k_split_csr_node(const double* __restrict__ cand, int F,
@@ -2785,23 +2664,15 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
                     double lambda, double mcw, double* cand, double* out, hipStream_t s,
-                    const int8_t* mono, const double* bounds, const uint64_t* fmask,
-                    const uint64_t* state) {
+                    const GbdtCons& c) {
   if (S <= 0 || F <= 0) return;
   const SplitParam p{alpha, lambda, mcw};
-  const dim3 grid((unsigned)((F + 255) / 256), S);
-  if (fmask && mono)
-    hipLaunchKernelGGL(k_split_csr_feat_mono_inter, grid, dim3(256), 0, s, hist, tb, totals,
-                       cut_off, fvalid, F, p, cand, mono, bounds, fmask, state);
-  else if (fmask)
-    hipLaunchKernelGGL(k_split_csr_feat_inter, grid, dim3(256), 0, s, hist, tb, totals, cut_off,
-                       fvalid, F, p, cand, fmask, state);
-  else if (mono)
-    hipLaunchKernelGGL(k_split_csr_feat_mono, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0,
-                       s, hist, tb, totals, cut_off, fvalid, F, p, cand, mono, bounds);
-  else
-    hipLaunchKernelGGL(k_split_csr_feat, dim3((unsigned)((F + 255) / 256), S), dim3(256), 0, s,
-                       hist, tb, totals, cut_off, fvalid, F, p, cand);
+  cons_dispatch(c, SplitMono{c.mono, c.bnd}, SplitInter{c.fmask, c.state},
+                [&](auto M, auto I, auto... cs) {
+                  hipLaunchKernelGGL((k_split_csr_feat<M(), I(), decltype(cs)...>),
+                                     dim3((unsigned)((F + 255) / 256), S), dim3(256), 0, s, hist,
+                                     tb, totals, cut_off, fvalid, F, p, cand, cs...);
+                });
   hipLaunchKernelGGL(k_split_csr_node, dim3((unsigned)S), dim3(256), 0, s, cand, F, out);
 }
 

@@ -552,6 +552,35 @@ void gbdt_hist(const uint8_t* B, int f, int nbin, const int32_t* ridx, const flo
 // int32 (see k_hist)
 // ntask_dev (optional): the task count of a device-built list (ntask is then
 // its upper bound; the reduce entries carry exact task counts)
+
+// The constraints of a split search or of a grower's bookkeeping step over
+// slots (or nodes) s and features f; all null: no constraints. The rule is
+// host/gbdt_node_rule.h. Every launcher picks its kernel by mono and fmask
+// alone.
+struct GbdtCons {
+  // monotone_constraints: given iff mono is
+  const int8_t* mono = nullptr;   // [F] signs in {-1, 0, 1}. The split searches read it per
+                                  // candidate feature, gbdt_dev_apply and gbdt_leaf_pick by the
+                                  // split feature (global feature ids)
+  const double* bnd = nullptr;    // [S x 2] the slots' weight intervals. The split searches take
+                                  // their gains at the clamped weights and drop a candidate whose
+                                  // children are ordered against its feature's sign;
+                                  // gbdt_dev_apply clamps the recorded weight
+  double* bnd_out = nullptr;      // gbdt_dev_apply: [2S x 2] (optional) receives the children's
+                                  // intervals. The leaf loop: the node table [NN x 2] itself, read
+                                  // and written in place by gbdt_leaf_root and gbdt_leaf_pick,
+                                  // which use no other; bnd must point into the same table for
+                                  // the loop's split searches (its slots' rows)
+  // interaction_constraints: given iff fmask is
+  const uint64_t* fmask = nullptr;  // [F] the features' group bit sets; read like mono
+  const uint64_t* state = nullptr;  // [S] the slots' group sets. Slot s may split on feature f
+                                    // iff state[s] & fmask[f] != 0; a pair that may not has no
+                                    // candidate and its histogram is not read
+  uint64_t* state_out = nullptr;    // as bnd_out: the children's sets [2S] (0 below a slot that
+                                    // stays a leaf), or the leaf loop's table [NN] (state points
+                                    // into it likewise)
+};
+
 // ---- the level loop on the device (gbdt_grow_dev in csrc/bind/gbdt_ops.cc)
 int gbdt_node_rec();
 // heap node records [nn x gbdt_node_rec()] -> the leaf walk's tree arrays
@@ -562,15 +591,7 @@ void gbdt_dev_apply(int S, int node0, bool last, const double* so, const double*
                     double lambda, double mcw, double rt_eps, double* nodes, int32_t* pfeat,
                     int32_t* pbin, uint8_t* pdefl, int32_t* lcur, int32_t* rcur, uint8_t* split,
                     uint8_t* build_left, double* tot_next, int32_t* nleft, hipStream_t s,
-                    const int8_t* mono = nullptr, const double* bnd = nullptr,
-                    double* bnd_next = nullptr, const uint64_t* fmask = nullptr,
-                    const uint64_t* state = nullptr, uint64_t* state_next = nullptr);
-// (mono [F] int8, given under monotone_constraints: bnd [S x 2] are the slots'
-// weight intervals, the recorded weight is clamped to them, and bnd_next
-// [2S x 2] (optional) receives the children's)
-// (fmask [F], given under interaction_constraints: the features' group bit
-// sets (host/gbdt_level_plan.h), state [S] the slots'; state_next [2S]
-// (optional) receives the children's, gbdt_child_state by the split feature)
+                    const GbdtCons& c);
 // lcur: the split slots' left cursors after the partition (their left
 // children end there; = the segment begin when no partition ran)
 bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const uint8_t* build_left,
@@ -583,17 +604,15 @@ bool gbdt_dev_children(int S, const int32_t* seg, const uint8_t* split, const ui
 // id, and the gbdt_leaf_ws() int32 words one step's kernels hand on; node
 // records are gbdt_node_rec() doubles with the left child's id first)
 int gbdt_leaf_ws();
-// the root's totals, interval (-top, top; bnd may be null), group set (state
-// may be null), open entry and record
+// the root's totals, interval (-top, top), group set, open entry and record
 void gbdt_leaf_root(const double* root_tot, int n, double top, uint64_t root_state, double eta,
-                    double alpha, double lambda, double mcw, double* tot, double* bnd,
-                    uint64_t* state, int32_t* meta, double* nodes, hipStream_t s);
+                    double alpha, double lambda, double mcw, double* tot, int32_t* meta,
+                    double* nodes, hipStream_t s, const GbdtCons& c);
 // step k: pick the open leaf of the largest gain among nodes 0..2k and apply
 // its split (children 2k + 1, 2k + 2), or mark the step idle
 void gbdt_leaf_pick(int k, int depth_cap, bool last, const double* so, double* tot, int32_t* meta,
                     double eta, double alpha, double lambda, double mcw, double rt_eps,
-                    double* nodes, int32_t* ws, hipStream_t s, const int8_t* mono, double* bnd,
-                    const uint64_t* fmask, uint64_t* state);
+                    double* nodes, int32_t* ws, hipStream_t s, const GbdtCons& c);
 // partition the picked segment only (through scratch [n], copied back)
 void gbdt_leaf_partition(const uint8_t* B, const uint8_t* Bc, int64_t nrows, int f, int32_t* ridx,
                          int64_t n, int32_t* ws, int32_t* scratch, hipStream_t s);
@@ -640,14 +659,7 @@ void gbdt_leaf_add(const int32_t* ridx, int64_t n, const int32_t* pos_node, cons
 // [S * F * 4] double scratch. false when nbin > 1024.
 bool gbdt_split(const double* hist, const double* totals, const uint8_t* valid, int S, int F,
                 int nbin, double alpha, double lambda, double mcw, double* cand, double* out,
-                hipStream_t s, const int8_t* mono = nullptr, const double* bounds = nullptr,
-                const uint64_t* fmask = nullptr, const uint64_t* state = nullptr);
-// (mono [F] int8 in {-1, 0, 1}, given under monotone_constraints, with the
-// slots' weight intervals bounds [S x 2]: gains at the clamped weights, and a
-// candidate whose children are ordered against its feature's sign is dropped)
-// (fmask [F] and state [S], given under interaction_constraints: slot s may
-// split on feature f iff state[s] & fmask[f] != 0; a pair that may not has no
-// candidate and its histogram is not read)
+                hipStream_t s, const GbdtCons& c);
 // sparse (CSR) input: global bin ids (cut_off[f] + bin, -1 = unbinned),
 // compact [slots][total bins][2] histograms (tasks [ntask x 3] = {slot,
 // rbeg, rend}, hq: int64 scratch of the histogram's size), split search over
@@ -661,8 +673,7 @@ void gbdt_hist_csr(const int64_t* row_off, const int32_t* gbin, const int32_t* r
 void gbdt_split_csr(const double* hist, int64_t tb, const double* totals,
                     const int32_t* cut_off, const uint8_t* fvalid, int S, int F, double alpha,
                     double lambda, double mcw, double* cand, double* out, hipStream_t s,
-                    const int8_t* mono = nullptr, const double* bounds = nullptr,
-                    const uint64_t* fmask = nullptr, const uint64_t* state = nullptr);
+                    const GbdtCons& c);
 void gbdt_goleft_csr(const int64_t* row_off, const int32_t* fid, const int32_t* gbin,
                      const int32_t* cut_off, const int32_t* ridx, int64_t n,
                      const int32_t* pos_node, const int32_t* node_feat, const int32_t* node_bin,

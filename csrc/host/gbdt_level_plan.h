@@ -42,39 +42,4 @@ struct GbdtNodeTables {
         lc(par + nsplit), rc(lc + nnode), nwords(rc + nnode) {}
 };
 
-// monotone_constraints: a node's weight interval {lo, hi}. A weight is
-// clamped to it; an accepted split on a feature of sign c cuts it at the mean
-// of the children's clamped weights (wl, wr): c > 0 gives the left child
-// {lo, mid} and the right {mid, hi}, c < 0 the mirror image, c == 0 hands the
-// interval down unchanged. The same rule as models/gbdt.py child_bounds and
-// gbdt.hip k_gd_apply.
-using GbdtBounds = std::array<double, 2>;
-
-inline double gbdt_clamp_weight(double w, const GbdtBounds& b) {
-  return w < b[0] ? b[0] : (w > b[1] ? b[1] : w);
-}
-
-inline std::array<GbdtBounds, 2> gbdt_child_bounds(int c, const GbdtBounds& b, double wl,
-                                                   double wr) {
-  const double mid = (wl + wr) / 2;
-  if (c > 0) return {GbdtBounds{b[0], mid}, GbdtBounds{mid, b[1]}};
-  if (c < 0) return {GbdtBounds{mid, b[1]}, GbdtBounds{b[0], mid}};
-  return {b, b};
-}
-
-// interaction_constraints on one 64-bit word: bit i < 63 of a feature's mask
-// says that group i contains it, and a feature in no group holds bit 63 alone.
-// A node's state is the set of groups that contain every feature split on
-// above it: all ones at the root, which therefore admits every feature; a
-// node admits feature f iff state & mask[f] != 0. The children of a split on
-// f narrow the state by mask[f] and drop bit 63, so nothing is admitted below
-// a split on an ungrouped feature. The same rule as models/gbdt_objective.py
-// interaction_child and gbdt.hip k_gd_apply.
-constexpr uint64_t kGbdtInterFree = 1ull << 63;
-constexpr uint64_t kGbdtInterRoot = ~0ull;
-
-inline uint64_t gbdt_child_state(uint64_t state, uint64_t fmask) {
-  return state & fmask & ~kGbdtInterFree;
-}
-
 }  // namespace wh

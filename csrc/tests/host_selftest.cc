@@ -29,6 +29,7 @@
 #include "host/common.h"
 #include "host/gbdt_hist_plan.h"
 #include "host/gbdt_level_plan.h"
+#include "host/gbdt_node_rule.h"
 #include "host/gbdt_objective.h"
 #include "host/io.h"
 #include "host/json.h"
@@ -624,21 +625,73 @@ static void test_gbdt_level_plan() {
   EXPECT(wh::GbdtNodeTables(8, 1, 1).tb == 32 + 2);
   EXPECT(wh::GbdtNodeTables(1, 1, 0).tb == 4 + 1);
   EXPECT(wh::GbdtNodeTables(1, 1, 0).nwords == 5 + 1 + 1 + 0 + 0 + 1 + 1);
+}
+
+// the node weight and the children's constraints (host/gbdt_node_rule.h: the
+// functions every grower and the kernels call)
+static void test_gbdt_node_rule() {
+  const double inf = std::numeric_limits<double>::infinity();
+  auto same = [](const wh::GbdtBounds& a, double lo, double hi) { return a.lo == lo && a.hi == hi; };
+  // the L1 threshold: at |G| = alpha, on either side of it, and without alpha
+  EXPECT(wh::gbdt_l1(2.0, 2.0) == 0.0 && wh::gbdt_l1(-2.0, 2.0) == 0.0);
+  EXPECT(wh::gbdt_l1(2.5, 2.0) == 0.5 && wh::gbdt_l1(-2.5, 2.0) == -0.5);
+  EXPECT(wh::gbdt_l1(1.5, 2.0) == 0.0 && wh::gbdt_l1(-1.5, 2.0) == 0.0);
+  EXPECT(wh::gbdt_l1(1.5, 0.0) == 1.5 && wh::gbdt_l1(-1.5, 0.0) == -1.5);
+  EXPECT(std::signbit(wh::gbdt_l1(-0.0, 0.0)));
+  // the weight: at H == mcw, just below it, and with lambda = 0
+  EXPECT(wh::gbdt_weight0(3.0, 2.0, 0.0, 1.0, 2.0) == -1.0);
+  EXPECT(wh::gbdt_weight0(3.0, std::nextafter(2.0, 0.0), 0.0, 1.0, 2.0) == 0.0);
+  EXPECT(wh::gbdt_weight0(3.0, 2.0, 0.0, 0.0, 2.0) == -1.5);
+  EXPECT(wh::gbdt_weight0(3.0, 2.0, 1.0, 0.0, 0.0) == -1.0);
   // weight intervals under monotone_constraints
-  {
-    const double inf = std::numeric_limits<double>::infinity();
-    const wh::GbdtBounds root{-inf, inf}, b{-1.0, 2.0};
-    EXPECT(wh::gbdt_clamp_weight(0.25, root) == 0.25);
-    EXPECT(wh::gbdt_clamp_weight(-3.0, b) == -1.0 && wh::gbdt_clamp_weight(5.0, b) == 2.0);
-    EXPECT(wh::gbdt_clamp_weight(2.0, b) == 2.0 && wh::gbdt_clamp_weight(-1.0, b) == -1.0);
-    // a negative zero inside the interval stays what it is (leaf text "-0")
-    EXPECT(std::signbit(wh::gbdt_clamp_weight(-0.0, wh::GbdtBounds{0.0, 1.0})));
-    auto up = wh::gbdt_child_bounds(1, root, -0.5, 1.5);
-    EXPECT((up[0] == wh::GbdtBounds{-inf, 0.5}) && (up[1] == wh::GbdtBounds{0.5, inf}));
-    auto down = wh::gbdt_child_bounds(-1, b, 1.0, 0.0);
-    EXPECT((down[0] == wh::GbdtBounds{0.5, 2.0}) && (down[1] == wh::GbdtBounds{-1.0, 0.5}));
-    auto free_ = wh::gbdt_child_bounds(0, b, 1.0, 0.0);
-    EXPECT(free_[0] == b && free_[1] == b);
+  const wh::GbdtBounds root{-inf, inf}, b{-1.0, 2.0};
+  EXPECT(wh::gbdt_clamp_weight(0.25, root) == 0.25);
+  EXPECT(wh::gbdt_clamp_weight(-3.0, b) == -1.0 && wh::gbdt_clamp_weight(5.0, b) == 2.0);
+  EXPECT(wh::gbdt_clamp_weight(2.0, b) == 2.0 && wh::gbdt_clamp_weight(-1.0, b) == -1.0);
+  // a negative zero inside the interval stays what it is (leaf text "-0")
+  EXPECT(std::signbit(wh::gbdt_clamp_weight(-0.0, wh::GbdtBounds{0.0, 1.0})));
+  EXPECT(wh::gbdt_weight(3.0, 2.0, 0.0, 0.0, 2.0, b) == -1.0);
+  auto up = wh::gbdt_child_bounds(1, root, -0.5, 1.5);
+  EXPECT(same(up.left, -inf, 0.5) && same(up.right, 0.5, inf));
+  auto down = wh::gbdt_child_bounds(-1, b, 1.0, 0.0);
+  EXPECT(same(down.left, 0.5, 2.0) && same(down.right, -1.0, 0.5));
+  auto free_ = wh::gbdt_child_bounds(0, b, 1.0, 0.0);
+  EXPECT(same(free_.left, -1.0, 2.0) && same(free_.right, -1.0, 2.0));
+  // a finite root (max_delta_step = 0.7 on either side of 0), children clamped to it
+  const wh::GbdtBounds step{-0.7, 0.7};
+  const double wl = wh::gbdt_clamp_weight(-3.0, step), wr = wh::gbdt_clamp_weight(0.25, step);
+  const double mid = (-0.7 + 0.25) / 2;
+  up = wh::gbdt_child_bounds(1, step, wl, wr);
+  EXPECT(same(up.left, -0.7, mid) && same(up.right, mid, 0.7));
+  down = wh::gbdt_child_bounds(-1, step, wl, wr);
+  EXPECT(same(down.left, mid, 0.7) && same(down.right, -0.7, mid));
+  free_ = wh::gbdt_child_bounds(0, step, wl, wr);
+  EXPECT(same(free_.left, -0.7, 0.7) && same(free_.right, -0.7, 0.7));
+  // group sets under interaction_constraints: an ungrouped feature (bit 63
+  // alone) is admitted at the root only, and nothing below a split on it
+  const uint64_t free_f = wh::kGbdtInterFree, g0 = 1, g1 = 2, g01 = 3;
+  EXPECT(wh::gbdt_admits(wh::kGbdtInterRoot, free_f) && wh::gbdt_admits(wh::kGbdtInterRoot, g1));
+  EXPECT(wh::gbdt_child_state(wh::kGbdtInterRoot, free_f) == 0);
+  EXPECT(!wh::gbdt_admits(wh::gbdt_child_state(wh::kGbdtInterRoot, free_f), free_f));
+  EXPECT(wh::gbdt_child_state(wh::kGbdtInterRoot, g01) == g01);
+  EXPECT(!wh::gbdt_admits(g01, free_f) && wh::gbdt_admits(g01, g1));
+  // disjoint groups: a split on one shuts the other out
+  EXPECT(wh::gbdt_child_state(wh::kGbdtInterRoot, g0) == g0 && !wh::gbdt_admits(g0, g1));
+  EXPECT(wh::gbdt_child_state(g0, g1) == 0 && wh::gbdt_child_state(g01, g1) == g1);
+  // the shared weight against the host grower's former spelling (H < mcw
+  // first, the threshold with an early return)
+  auto old_l1 = [](double g, double alpha) {
+    if (alpha <= 0) return g;
+    return g > alpha ? g - alpha : (g < -alpha ? g + alpha : 0.0);
+  };
+  std::mt19937_64 rng(11);
+  std::uniform_real_distribution<double> ug(-8.0, 8.0), uh(0.0, 4.0);
+  for (int i = 0; i < 400; ++i) {
+    const double G = ug(rng), H = uh(rng), alpha = i % 3 ? uh(rng) : 0.0;
+    const double lambda = i % 5 ? uh(rng) : 0.0, mcw = i % 7 ? uh(rng) : H;
+    const double want = H < mcw ? 0.0 : -old_l1(G, alpha) / (H + lambda);
+    const double got = wh::gbdt_weight0(G, H, alpha, lambda, mcw);
+    EXPECT(std::memcmp(&got, &want, 8) == 0);
   }
 }
 
@@ -929,6 +982,7 @@ int main() {
   test_psx_plan();
   test_gbdt_hist_plan();
   test_gbdt_level_plan();
+  test_gbdt_node_rule();
   test_gbdt_objective();
   test_lz4();
   test_crb();

@@ -94,7 +94,7 @@ DENSE_SHAPES = [(5, 7, 33, 0.0, 1.0), (3, 28, 256, 0.5, 0.1), (2, 4, 1000, 0.0, 
 @pytest.mark.parametrize("with_mono", [False, True])
 @pytest.mark.parametrize("S,F,nbin,alpha,mcw", DENSE_SHAPES)
 def test_split_kernel_with_admission(S, F, nbin, alpha, mcw, with_mono):
-    """k_split_feat_inter / k_split_feat_mono_inter with k_split_node against
+    """k_split_feat<false, true> / <true, true> with k_split_node against
     find_splits_ref: the same feature / bin / direction (the reference's best
     beats its runner-up by more than the tolerance, so the index is well
     defined), gains and left sums to fp64 rounding (rtol = atol = 1e-9, both
@@ -208,7 +208,7 @@ def _check_csr(case, fmask, state, with_mono):
 @pytest.mark.parametrize("with_mono", [False, True])
 @pytest.mark.parametrize("S,alpha,mcw,seed", [(5, 0.0, 1.0, 1), (3, 0.5, 0.1, 2)])
 def test_split_csr_kernel_with_admission(S, alpha, mcw, seed, with_mono):
-    """k_split_csr_feat_inter / _mono_inter on compact bins of uneven counts
+    """k_split_csr_feat<false, true> / <true, true> on compact bins of uneven counts
     (one feature has none, one a single bin, feature 0 is not a candidate)."""
     fmask = torch.tensor([1, 1, 3, 2, 6, 4, BIT63], dtype=torch.int64)
     state = torch.tensor([-1, 0, 1, 2, 4][:S], dtype=torch.int64)

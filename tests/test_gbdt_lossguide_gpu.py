@@ -121,16 +121,31 @@ def test_device_loop_single_leaf(monkeypatch):
     assert [len(t.feat) for t in one] == [1] * TREES
 
 
-def test_device_loop_under_constraints(monkeypatch):
-    trees = _agree(monkeypatch, 20000, 12, 32, 0, groups=GROUPS, mono=MONO, max_delta_step=0.4)
+@pytest.mark.parametrize("cons", ["groups", "mono", "both"])
+def test_device_loop_under_constraints(cons, monkeypatch):
+    """Groups alone, signs alone (with max_delta_step, which needs them) and
+    both: every constrained instantiation of k_leaf_root and k_leaf_pick. A
+    constraint that is off does not hold by accident (the Python leaf loop on
+    the CPU: 95 of 96 splits break the groups under the signs alone, and the
+    signs fail under the groups alone)."""
+    groups = GROUPS if cons != "mono" else None
+    kw = dict(mono=MONO, max_delta_step=0.4) if cons != "groups" else {}
+    trees = _agree(monkeypatch, 20000, 12, 32, 0, groups=groups, **kw)
     assert [L.n_leaves(t) for t in trees] == [32] * TREES
     bad, total = C.broken(trees, GROUPS)
-    assert bad == 0 and total > 3 * 4, (bad, total)
+    if groups:
+        assert bad == 0 and total > 3 * 4, (bad, total)
+    else:
+        assert bad > 0
+    if cons == "groups":
+        assert not M.holds(trees, MONO)
+        return
     assert M.holds(trees, MONO)
     assert sum(k for k, _ in M.structure(trees, MONO).values()) > 6
     assert all(abs(v) <= 0.5 * 0.4 + 1e-12 for t in trees for v in t.leaf)
-    free, _, _ = _grow(monkeypatch, True, 20000, 12, 32, 0)
-    assert C.broken(free, GROUPS)[0] > 0 and not M.holds(free, MONO)
+    if cons == "both":
+        free, _, _ = _grow(monkeypatch, True, 20000, 12, 32, 0)
+        assert C.broken(free, GROUPS)[0] > 0 and not M.holds(free, MONO)
 
 
 # ------------------------------------------------ 2. equivalence on the device

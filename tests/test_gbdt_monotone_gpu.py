@@ -79,7 +79,7 @@ DENSE_SHAPES = [(5, 7, 33, 0.0, 1.0), (3, 28, 256, 0.5, 0.1), (2, 4, 1000, 0.0, 
 
 @pytest.mark.parametrize("S,F,nbin,alpha,mcw", DENSE_SHAPES)
 def test_split_kernel_with_bounds(S, F, nbin, alpha, mcw):
-    """k_split_feat<MONO> / k_split_node against find_splits_ref: the same
+    """k_split_feat<true, false> / k_split_node against find_splits_ref: the same
     feature / bin / direction (the reference's best beats its runner-up by
     more than the tolerance, so the index is well defined), gains and left
     sums to fp64 rounding (rtol = atol = 1e-9, both sides fp64)."""
@@ -138,7 +138,7 @@ def csr_case(S, alpha, mcw, seed):
 
 @pytest.mark.parametrize("S,alpha,mcw,seed", [(5, 0.0, 1.0, 1), (3, 0.5, 0.1, 2)])
 def test_split_csr_kernel_with_bounds(S, alpha, mcw, seed):
-    """k_split_csr_feat<MONO> / k_split_csr_node against the CSR builder's
+    """k_split_csr_feat<true, false> / k_split_csr_node against the CSR builder's
     Python search, on compact bins of uneven counts (one feature has none,
     one a single bin, feature 0 is not a candidate)."""
     G = _G()
